@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """bench.py - headline metric of BASELINE.json: images/sec/GPU, YOLOv8n 640x640 bs=32, forward + Detect decode + NMS.
 
-  python bench.py --gpus N --steps K --warmup W [--dtype bf16|f32] [--batch 32]
+  python bench.py --gpus N --steps K --warmup W [--dtype bf16|f32] [--batch 32] [--dump-outputs DIR] [--full]
   (N > 1: launched by torch.distributed.run, one rank per GPU; batch-sharded replicas, no data-path collective)
 
 A "step" = one pass of the hot path over one batch of 32 synthetic images already resident in HBM:
 model forward (stem + 63 implicit-GEMM convs + SPPF/upsample kernels) -> Detect decode -> batched NMS
 (conf 0.25, iou 0.7, max_det 300: the predict defaults), replayed as ONE hipGraph.
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, timed live with HIP events) and `cpu_baseline`
-(the oracle on this host's cores, bounded sample).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the line; `--full` adds the
+legs the headline figure does not need: the one-step-at-a-time / latency / forked legs, `roofline` (dominant kernel,
+timed live with HIP events), `cpu_baseline` (the oracle on this host's cores, bounded sample) and `parity`.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (same arguments = same inputs).
 """
 
 from __future__ import annotations
@@ -68,6 +70,15 @@ def parse():
                          "0 = autotune: a few (in-flight, micro-batches) pairs are timed for 20 steps, the fastest is used")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: run only the multi-rank plumbing (gloo rendezvous, barriers, max-over-ranks, the JSON line)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the serial / latency / forked one-step legs and the check "
+                         "of the host-visible detections, the per-kernel roofline, the CPU baseline and the parity check against the "
+                         "oracle (train: the weight-gradient profile and the CPU baseline); --no-kernel-profile / --no-cpu-baseline / "
+                         "--no-parity still switch single legs off")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (infer: detections, counts, kept anchor "
+                         "indices; val: the same plus the TP matrix; train: the loss items and the updated parameters) as "
+                         "DIR/<name>.npy in float32 / float64 (rank 0's shard; rows past an image's count are zero)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--opts", default="",
                     help="dispatch overrides of the model's kernel calls (upa_opts fields, include/upa.h) as name=value,... - A/B "
@@ -98,7 +109,10 @@ def parse():
                     help="walk the per-GPU batch as this many concurrent sub-batches (parallel hipGraph branches of ONE "
                          "graph; the whole batch is still processed every step): the latency-bound 20x20/40x40 layers of "
                          "one half overlap the other half's. 0 = autotune together with --in-flight")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dry_run and args.dump_outputs:
+        ap.error("--dump-outputs: a dry run computes nothing")
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -253,6 +267,37 @@ def _crumb(msg: str) -> None:
     print(f"[bench +{time.perf_counter() - _T0:6.1f}s] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_SAMPLE = 1 << 20  # elements kept of a larger array (a fixed, seeded sample): the dump stays far below 64 MB
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _valid_rows(rows, counts, fill=0):
+    """(B, max_det, ...) fixed-shape result rows with the rows past each image's count set to `fill`: a caller reads only the first
+    counts[b] rows, and the rest of the static buffer is whatever an earlier replay left there."""
+    idx = torch.arange(rows.shape[1], device=rows.device)
+    mask = (idx[None, :] < counts.to(rows.device).long()[:, None]).reshape(rows.shape[:2] + (1,) * (rows.dim() - 2))
+    return torch.where(mask, rows, torch.full_like(rows, fill))
+
+
+def dump_outputs(out_dir, arrays) -> None:
+    """--dump-outputs: each array as <out_dir>/<name>.npy, float64 for 32- / 64-bit integers and f64 data (exact), float32 otherwise; an array of more
+    than DUMP_SAMPLE elements is written as the flat sample at sorted indices drawn from a generator seeded with 0."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = a.detach().cpu()
+        a = a.double() if a.dtype in (torch.float64, torch.int64, torch.int32) else a.float()
+        if a.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(0)
+            a = a.reshape(-1)[torch.randperm(a.numel(), generator=g)[:DUMP_SAMPLE].sort().values]
+        total += a.numel() * a.element_size()
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_LIMIT_BYTES >> 20} MB at '{name}'")
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.numpy())
+    _crumb(f"outputs of the last timed step written to {out_dir}: {', '.join(arrays)}")
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -396,7 +441,16 @@ def main():
     value = pb * world * args.steps / dt
     results = run.result if args.micro_batches > 1 else [run.result]
     ndet = [c for (_, counts, _) in results for c in counts.tolist()]
-    if not args.no_host_results:  # the host copies the step itself wrote must equal the device results
+    if args.dump_outputs and rank == 0:
+        # the compiled copy that ran the last timed step (the copies take the steps round-robin) and the rows it handed back
+        last = runner.runs[(runner.i - 1) % len(runner.runs)].result
+        parts = last if args.micro_batches > 1 else [last]
+        counts = torch.cat([p[1] for p in parts])
+        arrays = {"detections": _valid_rows(torch.cat([p[0] for p in parts]), counts), "counts": counts}
+        if parts[0][2] is not None:
+            arrays["keep"] = _valid_rows(torch.cat([p[2] for p in parts]), counts, fill=-1)
+        dump_outputs(args.dump_outputs, arrays)
+    if args.full and not args.no_host_results:  # the host copies the step itself wrote must equal the device results
         for (o_, c_, _) in results:
             hb = host_bufs[o_.data_ptr()]
             cc, oc = c_.cpu(), o_.cpu()
@@ -406,7 +460,7 @@ def main():
 
     roofline, kernels, cpu_baseline, parity, gpu_speed = None, None, None, None, None
     serial_ms = latency_ms = forked_ms = None
-    if rank == 0 and not args.serial:
+    if rank == 0 and args.full and not args.serial:
         # the same step with no concurrency at all (one linear graph, one stream): back-to-back ms/step, and the latency of
         # ONE batch from enqueue to host-visible results
         with torch.no_grad():
@@ -464,9 +518,9 @@ def main():
                     del fk
                 except Exception as e:  # noqa: BLE001 - an extra measurement must not cost the run its headline line
                     print(f"[bench] forked one-step leg skipped: {e}", file=sys.stderr)
-    elif rank == 0:
+    elif rank == 0 and args.serial:
         serial_ms = ms_per_step
-    if rank == 0:
+    if rank == 0 and args.full:
         _crumb("timed region + serial / latency legs done")
         if not args.no_kernel_profile:
             # per-kernel timing of the launches the TIMED region replayed: under the runner's throughput dispatch, if it has one
@@ -638,6 +692,9 @@ def main_val(args):
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:  # what the compiled batch of the last timed step handed back
+        out, counts, tp = runs[(args.steps - 1) % nb].result
+        dump_outputs(args.dump_outputs, {"detections": _valid_rows(out, counts), "counts": counts, "tp": _valid_rows(tp, counts)})
     # end of run: one pass over the set = the statistics of the K compiled batches; gather + AP on every rank
     for (out, counts, tp), (gt, ngt) in zip((r.result for r in runs), labels):
         v.add_batch_stats(out, counts, tp, gt, ngt)
@@ -749,13 +806,16 @@ def main_train(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     value = pb * world * args.steps / dt
+    if args.dump_outputs and rank == 0:  # the loss items of the last timed step and the parameters it left (flat f32 master weights)
+        dump_outputs(args.dump_outputs, {"loss_items": items, "parameters": tr.P})
     exposed = tr.allreduce_exposed_ms()
     seen = ranks_seen(dist, dev)
     roofline = cpu_baseline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         roofline = wgrad_profile(tr, L, R, dev, dtype, cfg_key=f"{args.model} bs={pb} {args.dtype} train")
         if not args.no_cpu_baseline and world == 1:
             cpu_baseline = run_cpu_baseline_bounded(args)
+    if rank == 0:
         nparam = sum(n for _, n, _ in tr.groups)
         print(json.dumps({
             "metric": f"images/sec {args.model} {args.imgsz}x{args.imgsz} training step, per-GPU batch {pb} "

@@ -4,7 +4,7 @@ out=$1; shift
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $root/$out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/prof -- python3 $root/bench.py --no-cpu-baseline --no-kernel-profile "$@" > $root/$out/bench.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/prof -- python3 $root/bench.py --full --no-cpu-baseline --no-kernel-profile "$@" > $root/$out/bench.json 2>/dev/null
 cd $root
 f=$(find $out/prof -name "*kernel_stats.csv" | head -1)
 cp $f $out/kernel_stats.csv

@@ -14,7 +14,7 @@ build w8 -DUPA_GREEDY_NT=512
 cd ../..
 python -m pytest tests/test_hip_ops.py tests/test_hip_e2e.py -x -q -m gpu -k "nms" 2>&1 | tail -1
 for v in chain w8; do UPA_HIP_LIB=/tmp/libupa_hip_$v.so python -m pytest tests/test_hip_ops.py -x -q -m gpu -k "nms" 2>&1 | tail -1; done
-run() { l=$1; shift; python bench.py "$@" 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('$l', d['value'], d['ms_per_step'], d.get('serial_ms_per_step'))"; }
+run() { l=$1; shift; python bench.py --full "$@" 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('$l', d['value'], d['ms_per_step'], d.get('serial_ms_per_step'))"; }
 for r in 1 2 3; do
   for v in chain rows8 w8; do
     lib=/tmp/libupa_hip_$v.so; [ $v = rows8 ] && lib=$PWD/ultralytics_pro_amd/libupa_hip.so
