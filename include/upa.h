@@ -38,9 +38,8 @@ enum { UPA_OK = 0, UPA_EINVAL = -1, UPA_EUNSUPPORTED = -2, UPA_EWORKSPACE = -3, 
  * tools/bench_conv.py sweeps and by A/B measurements; production code passes NULL. */
 typedef struct upa_opts {
   uint32_t size;
-  int32_t conv_big;        /* csrc/conv_big.hip inside upa_conv2d_bias_act: 0 = by the size rule, 1 = never, 2 = every shape it can run, 3 = the rule restricted to maps of < 100000 pixels (at most one tile per workgroup) */
+  int32_t conv_big;        /* csrc/conv_big.hip inside upa_conv2d_bias_act: 0 = by the size rule, 1 = never, 2 = every shape it can run (other values: the size rule) */
   int32_t conv_big_bm;     /* its workgroup pixels: 0 = auto | 128 | 256 | 512 */
-  int32_t conv_force[4];   /* conv_igemm variant WM, WN, MT, NT for every conv whose Cout fits it (0 = none) */
   int32_t conv_ckt;        /* conv_igemm k-tiles per chunk: 0 = auto | 1 | 2 | 4 */
   int32_t no_ws, no_pipe, no_1x1, no_c16, no_upcat;  /* 1 = never dispatch conv_ws / conv3x3_pipe / conv1x1_stream / conv3x3_c16 / the virtual upsample */
   int32_t pipe_all;        /* conv3x3_pipe on every eligible channel count (default: the measured winners) */
@@ -58,10 +57,9 @@ typedef struct upa_opts {
   int32_t stem_wgs, stemf_wgs, stemf_waves, stem_no_mfma;  /* stem kernels: workgroup caps (0 = 1024 / 512), fused-stem waves (0 = 8 | 4) */
   int32_t ablate_conv, ablate_pipe, ablate_c1, ablate_stem;  /* kernel ablation bit masks: honoured by the -DUPA_ABLATE build only (make ablate) */
   int32_t c2f64_max_px;    /* upa_c2f64_fused only up to this many pixels n * h * w (0 = 100000: the 40 x 40 maps at batch 32; -1 = any size) */
-  int32_t conv_ws3;        /* csrc/conv_ws3.hip (persistent 3x3 with register-resident weights, Cin <= 64, Cout 64): 0 = by the size rule, 1 = never, 2 = every shape it can run, 3 = the rule restricted to maps of < 100000 pixels (at most one tile per workgroup) */
+  int32_t conv_ws3;        /* csrc/conv_ws3.hip (persistent 3x3 with register-resident weights, Cin <= 64, Cout 64): 0 = by the size rule, 1 = never, 2 = every shape it can run */
   int32_t no_group;        /* upa_conv2d_bias_act_group / upa_detect_branch_tail_group: 0 = two problems per grid where the instantiations allow, 1 = one launch per problem, 2 = three per grid too (measured slower; A/B) */
   int32_t no_c2f32_up;     /* 1 = upa_c2f32_up_fused refuses (the block then runs as upa_conv1x1_upcat + upa_bottleneck_pair_cv2; A/B) */
-  int32_t conv_mm;         /* csrc/conv_mm.hip (4-wave 32x32x16-MFMA 3x3 kernel for Cin % 64 == 0, Cout % 128 == 0) inside upa_conv2d_bias_act: 2 = every shape it can run (experiment: measured slower than conv_big, see its header), 0 / 1 = never */
   int32_t no_xcd;          /* 1 = tile kernels take tile blockIdx.x instead of the XCD-aware order (each XCD a contiguous tile range: neighbouring halos meet in one L2); A/B */
   int32_t keys_only;       /* upa_detect_branch_tail* / upa_detect_head_tails with best_keys: 1 = the class rows of y are NOT written - only the boxes and the best-class NMS keys, which is all single-label NMS reads (upa_nms_batched_hot); rows 4.. of y are then undefined */
   int32_t conv_p8;         /* csrc/conv_p8.hip (8-wave two-group phased 3x3 stride-1 kernel for Cin % 64 == 0, Cout % 128 == 0: counted vmcnt, 4-slab weight ring, double-buffered halo) inside upa_conv2d_bias_act: 0 = by the size rule, 1 = never, 2 = every shape it can run */

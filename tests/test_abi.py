@@ -89,10 +89,10 @@ def test_dispatch_options_travel_with_the_call_and_the_library_reads_no_environm
     assert L.Opts.from_env({"UPA_NO_PAIR": "0", "UPA_C1_MT": "4", "UPA_CONV_FORCE": "4,1,2,4"}).pair == 2  # tool-side mapping only
 
 
-def test_conv_p8_size_rule_is_host_logic():
+def test_conv_p8_dispatch_rule_is_host_logic():
     """The round-4 dispatch rule of the two-group phased kernel (csrc/conv_p8.hip: one-round layers of 256-pixel x 128-channel tiles with
     Cin >= 256) is pure host logic behind `upa_conv_variant`: the layers it was measured on pick it, their neighbours stay on conv_big,
-    `upa_opts.conv_p8` = 1 / 2 switch it off / force it, and conv_mm is never chosen by default."""
+    `upa_opts.conv_p8` = 1 / 2 switch it off / force it, and bit 25 (the removed conv_mm kernel) is never chosen."""
     import ctypes as C
     from ultralytics_pro_amd import _lib as L
     lib = L.lib()
@@ -110,7 +110,144 @@ def test_conv_p8_size_rule_is_host_logic():
         assert big(v) and not p8(v) and not mm(v), (n, h, w, c1, c2, hex(v))
         assert p8(lib.upa_conv_variant(n, h, w, c1, c2, 3, 1, 1, L.UPA_BF16, C.pointer(L.Opts(conv_p8=2))))
     assert not p8(lib.upa_conv_variant(16, 40, 40, 512, 256, 3, 2, 1, L.UPA_BF16, C.pointer(L.Opts(conv_p8=2))))  # stride 2: never
-    assert mm(lib.upa_conv_variant(16, 40, 40, 512, 256, 3, 1, 1, L.UPA_BF16, C.pointer(L.Opts(conv_mm=2, conv_p8=1))))
+
+
+# upa_conv_variant of every distinct conv shape the five bench.py workloads issue (bf16 at 640 x 640: yolov8n / yolov8s / yolov3-tiny /
+# yolov5-BoT3 at batch 32, yolov3-rtdetr at batch 16; the stem's 3-channel convs run elsewhere; plus yolov8n's stacked 144-channel first
+# Detect conv), recorded before the conv dispatch was folded into one selector: (n, h, w, cin, cout, k, stride, pad, (library defaults,
+# the in-flight runner's upa_opts of engine/pipeline.py, tests/conftest.py's TEST_OPTS))
+CONV_VARIANTS = [
+    (16, 20, 20, 512, 256, 1, 1, 0, (0x400818, 0x800041, 0x400818)),
+    (16, 20, 20, 512, 1024, 3, 1, 1, (0x4000082, 0x4000082, 0x4000082)),
+    (16, 20, 20, 1024, 256, 1, 1, 0, (0x800041, 0x800041, 0x800041)),
+    (16, 20, 20, 1024, 512, 1, 1, 0, (0x800041, 0x800041, 0x800041)),
+    (16, 20, 20, 1024, 512, 3, 1, 1, (0x800041, 0x800041, 0x800041)),
+    (16, 40, 40, 256, 128, 1, 1, 0, (0x400818, 0x800041, 0x400818)),
+    (16, 40, 40, 256, 512, 3, 1, 1, (0x800082, 0x800082, 0x800082)),
+    (16, 40, 40, 512, 256, 1, 1, 0, (0x400818, 0x800081, 0x400818)),
+    (16, 40, 40, 512, 256, 3, 1, 1, (0x4000082, 0x4000082, 0x4000082)),
+    (16, 40, 40, 512, 1024, 3, 2, 1, (0x800081, 0x800081, 0x800081)),
+    (16, 40, 40, 768, 256, 3, 1, 1, (0x4000082, 0x4000082, 0x4000082)),
+    (16, 80, 80, 128, 256, 3, 1, 1, (0x800082, 0x800082, 0x800082)),
+    (16, 80, 80, 256, 128, 3, 1, 1, (0x800082, 0x800082, 0x800082)),
+    (16, 80, 80, 256, 256, 1, 1, 0, (0x400828, 0x800082, 0x400828)),
+    (16, 80, 80, 256, 512, 3, 2, 1, (0x800082, 0x800082, 0x800082)),
+    (16, 80, 80, 384, 128, 3, 1, 1, (0x800082, 0x800082, 0x800082)),
+    (16, 160, 160, 64, 128, 3, 1, 1, (0x800082, 0x800082, 0x800082)),
+    (16, 160, 160, 128, 64, 3, 1, 1, (0x800042, 0x800042, 0x800042)),
+    (16, 160, 160, 128, 256, 3, 2, 1, (0x800082, 0x800082, 0x800082)),
+    (16, 320, 320, 32, 64, 3, 1, 1, (0x200004, 0x800042, 0x200004)),
+    (16, 320, 320, 64, 32, 3, 1, 1, (0x200002, 0x200002, 0x200002)),
+    (16, 320, 320, 64, 128, 3, 2, 1, (0x800082, 0x800082, 0x800082)),
+    (16, 640, 640, 32, 64, 3, 2, 1, (0x12242, 0x800042, 0x12242)),
+    (32, 20, 20, 64, 64, 1, 1, 0, (0x400814, 0x800041, 0x400814)),
+    (32, 20, 20, 64, 64, 3, 1, 1, (0x1000044, 0x800041, 0x1000044)),
+    (32, 20, 20, 80, 80, 1, 1, 0, (0x400815, 0x800061, 0x400815)),
+    (32, 20, 20, 80, 80, 3, 1, 1, (0x800051, 0x800051, 0x800051)),
+    (32, 20, 20, 128, 80, 1, 1, 0, (0x400815, 0x800061, 0x400815)),
+    (32, 20, 20, 128, 128, 1, 1, 0, (0x400818, 0x800041, 0x400818)),
+    (32, 20, 20, 128, 128, 3, 1, 1, (0x800041, 0x800041, 0x800041)),
+    (32, 20, 20, 256, 64, 3, 1, 1, (0x800041, 0x800041, 0x800041)),
+    (32, 20, 20, 256, 80, 1, 1, 0, (0x400815, 0x800061, 0x400815)),
+    (32, 20, 20, 256, 80, 3, 1, 1, (0x800051, 0x800051, 0x800051)),
+    (32, 20, 20, 256, 128, 1, 1, 0, (0x400818, 0x800041, 0x400818)),
+    (32, 20, 20, 256, 256, 1, 1, 0, (0x400818, 0x800041, 0x400818)),
+    (32, 20, 20, 256, 256, 3, 1, 1, (0x800041, 0x800041, 0x800041)),
+    (32, 20, 20, 256, 512, 3, 1, 1, (0x4000082, 0x4000082, 0x4000082)),
+    (32, 20, 20, 384, 256, 1, 1, 0, (0x400818, 0x800041, 0x400818)),
+    (32, 20, 20, 512, 64, 3, 1, 1, (0x800041, 0x800041, 0x800041)),
+    (32, 20, 20, 512, 128, 3, 1, 1, (0x800041, 0x800041, 0x800041)),
+    (32, 20, 20, 512, 256, 1, 1, 0, (0x400818, 0x800041, 0x400818)),
+    (32, 20, 20, 512, 256, 3, 1, 1, (0x800041, 0x800041, 0x800041)),
+    (32, 20, 20, 512, 512, 1, 1, 0, (0x400818, 0x800081, 0x400818)),
+    (32, 20, 20, 512, 1024, 3, 1, 1, (0x800082, 0x800082, 0x800082)),
+    (32, 20, 20, 768, 512, 1, 1, 0, (0x800081, 0x800081, 0x800081)),
+    (32, 20, 20, 1024, 256, 1, 1, 0, (0x800041, 0x800041, 0x800041)),
+    (32, 20, 20, 1024, 512, 1, 1, 0, (0x800081, 0x800081, 0x800081)),
+    (32, 40, 40, 64, 64, 1, 1, 0, (0x400824, 0x800041, 0x400824)),
+    (32, 40, 40, 64, 64, 3, 1, 1, (0x1000044, 0x800041, 0x1000044)),
+    (32, 40, 40, 80, 80, 1, 1, 0, (0x400825, 0x800061, 0x400825)),
+    (32, 40, 40, 80, 80, 3, 1, 1, (0x800051, 0x800051, 0x800051)),
+    (32, 40, 40, 128, 64, 1, 1, 0, (0x400824, 0x800041, 0x400824)),
+    (32, 40, 40, 128, 64, 3, 1, 1, (0x800041, 0x800041, 0x800041)),
+    (32, 40, 40, 128, 80, 1, 1, 0, (0x400825, 0x800061, 0x400825)),
+    (32, 40, 40, 128, 80, 3, 1, 1, (0x800051, 0x800051, 0x800051)),
+    (32, 40, 40, 128, 128, 1, 1, 0, (0x400828, 0x800081, 0x400828)),
+    (32, 40, 40, 128, 128, 3, 1, 1, (0x800081, 0x800081, 0x800081)),
+    (32, 40, 40, 128, 128, 3, 2, 1, (0x800041, 0x800041, 0x800041)),
+    (32, 40, 40, 128, 256, 3, 1, 1, (0x800082, 0x800082, 0x800082)),
+    (32, 40, 40, 128, 256, 3, 2, 1, (0x800041, 0x800041, 0x800041)),
+    (32, 40, 40, 192, 128, 1, 1, 0, (0x400828, 0x800081, 0x400828)),
+    (32, 40, 40, 256, 64, 1, 1, 0, (0x400824, 0x800041, 0x400824)),
+    (32, 40, 40, 256, 64, 3, 1, 1, (0x800041, 0x800041, 0x800041)),
+    (32, 40, 40, 256, 80, 1, 1, 0, (0x400825, 0x800061, 0x400825)),
+    (32, 40, 40, 256, 128, 1, 1, 0, (0x400828, 0x800081, 0x400828)),
+    (32, 40, 40, 256, 128, 3, 1, 1, (0x4000082, 0x4000082, 0x4000082)),
+    (32, 40, 40, 256, 256, 1, 1, 0, (0x400828, 0x800082, 0x400828)),
+    (32, 40, 40, 256, 256, 3, 1, 1, (0x800082, 0x800082, 0x800082)),
+    (32, 40, 40, 256, 256, 3, 2, 1, (0x800041, 0x800041, 0x800041)),
+    (32, 40, 40, 256, 512, 3, 2, 1, (0x800081, 0x800081, 0x800081)),
+    (32, 40, 40, 384, 128, 1, 1, 0, (0x400828, 0x800081, 0x400828)),
+    (32, 40, 40, 384, 256, 1, 1, 0, (0x400828, 0x800082, 0x400828)),
+    (32, 40, 40, 384, 256, 3, 1, 1, (0x800082, 0x800082, 0x800082)),
+    (32, 40, 40, 512, 256, 1, 1, 0, (0x400818, 0x800082, 0x400818)),
+    (32, 40, 40, 768, 256, 1, 1, 0, (0x800082, 0x800082, 0x800082)),
+    (32, 80, 80, 32, 32, 1, 1, 0, (0x400842, 0x400842, 0x400842)),
+    (32, 80, 80, 32, 32, 3, 1, 1, (0x200002, 0x200002, 0x200002)),
+    (32, 80, 80, 64, 32, 1, 1, 0, (0x400842, 0x400842, 0x400842)),
+    (32, 80, 80, 64, 64, 1, 1, 0, (0x400844, 0x800042, 0x400844)),
+    (32, 80, 80, 64, 64, 3, 1, 1, (0x1000044, 0x800042, 0x1000044)),
+    (32, 80, 80, 64, 64, 3, 2, 1, (0x22242, 0x800041, 0x22242)),
+    (32, 80, 80, 64, 80, 3, 1, 1, (0x800052, 0x800052, 0x800052)),
+    (32, 80, 80, 64, 128, 3, 1, 1, (0x800082, 0x800082, 0x800082)),
+    (32, 80, 80, 64, 128, 3, 2, 1, (0x800081, 0x800081, 0x800081)),
+    (32, 80, 80, 80, 80, 1, 1, 0, (0x400845, 0x800062, 0x400845)),
+    (32, 80, 80, 80, 80, 3, 1, 1, (0x800052, 0x800052, 0x800052)),
+    (32, 80, 80, 96, 64, 1, 1, 0, (0x400844, 0x800042, 0x400844)),
+    (32, 80, 80, 128, 32, 1, 1, 0, (0x400842, 0x400842, 0x400842)),
+    (32, 80, 80, 128, 64, 1, 1, 0, (0x400844, 0x800042, 0x400844)),
+    (32, 80, 80, 128, 64, 3, 1, 1, (0x800042, 0x800042, 0x800042)),
+    (32, 80, 80, 128, 80, 1, 1, 0, (0x400845, 0x800062, 0x400845)),
+    (32, 80, 80, 128, 128, 1, 1, 0, (0x400848, 0x800082, 0x400848)),
+    (32, 80, 80, 128, 128, 3, 1, 1, (0x800082, 0x800082, 0x800082)),
+    (32, 80, 80, 128, 128, 3, 2, 1, (0x800081, 0x800081, 0x800081)),
+    (32, 80, 80, 128, 256, 3, 2, 1, (0x800082, 0x800082, 0x800082)),
+    (32, 80, 80, 192, 64, 1, 1, 0, (0x400844, 0x800042, 0x400844)),
+    (32, 80, 80, 192, 128, 1, 1, 0, (0x400848, 0x800082, 0x400848)),
+    (32, 80, 80, 256, 128, 1, 1, 0, (0x400828, 0x800082, 0x400828)),
+    (32, 80, 80, 384, 128, 1, 1, 0, (0x400828, 0x800082, 0x400828)),
+    (32, 160, 160, 16, 16, 1, 1, 0, (0x400841, 0x400841, 0x400841)),
+    (32, 160, 160, 16, 16, 3, 1, 1, (0x200101, 0x200101, 0x200101)),
+    (32, 160, 160, 32, 16, 1, 1, 0, (0x400841, 0x400841, 0x400841)),
+    (32, 160, 160, 32, 32, 1, 1, 0, (0x400842, 0x400842, 0x400842)),
+    (32, 160, 160, 32, 32, 3, 1, 1, (0x200002, 0x200002, 0x200002)),
+    (32, 160, 160, 32, 64, 3, 1, 1, (0x200004, 0x800042, 0x200004)),
+    (32, 160, 160, 32, 64, 3, 2, 1, (0x12242, 0x800042, 0x12242)),
+    (32, 160, 160, 48, 32, 1, 1, 0, (0x400842, 0x400842, 0x400842)),
+    (32, 160, 160, 64, 64, 1, 1, 0, (0x400844, 0x800042, 0x400844)),
+    (32, 160, 160, 64, 128, 3, 2, 1, (0x800082, 0x800082, 0x800082)),
+    (32, 160, 160, 96, 64, 1, 1, 0, (0x400844, 0x800042, 0x400844)),
+    (32, 320, 320, 16, 32, 3, 1, 1, (0x200102, 0x200102, 0x200102)),
+    (32, 320, 320, 16, 32, 3, 2, 1, (0x14122, 0x14122, 0x14122)),
+    (32, 320, 320, 32, 64, 3, 2, 1, (0x12242, 0x800042, 0x12242)),
+    (32, 80, 80, 64, 144, 3, 1, 1, (0x800092, 0x800092, 0x800092)),
+]
+
+
+def test_conv_dispatch_matches_the_recorded_table():
+    """Every bench workload's conv shape picks the same kernel family and instantiation (the variant bits bench.py / tools decode) under the
+    three option sets callers use."""
+    import ctypes as C
+    from ultralytics_pro_amd import _lib as L
+    lib = L.lib()
+    optsets = [None, L.Opts(c2f=4, conv_ws3=1, c2f_stream_rows=-1, detect_stream=2, conv_big=2),
+               L.Opts(pipe_min_tiles=1, pipe_all=1, pair=2, c2f64_max_px=-1)]
+    bad = []
+    for *shape, expected in CONV_VARIANTS:
+        got = tuple(lib.upa_conv_variant(*shape, L.UPA_BF16, None if o is None else C.pointer(o)) for o in optsets)
+        if got != expected:
+            bad.append((shape, [hex(v) for v in expected], [hex(v) for v in got]))
+    assert not bad, bad
 
 
 def test_product_builds_on_cpu_but_refuses_to_run_there():

@@ -1683,40 +1683,14 @@ def test_c3_stacked_cv1_cv2_equals_separate_launches(cls, args, xshape, dtype):
         assert (y1 - ref).abs().max().item() <= tol and (y1 - y0).abs().max().item() <= tol
 
 
-MM_CASES = [
-    # c1, c2, H, W, N, act, residual  (4-wave 32x32x16-MFMA kernel, csrc/conv_mm.hip: Cin % 64 == 0, Cout % 128 == 0, 3x3 stride 1)
-    (128, 128, 80, 80, 1, True, False),    # 16 x 16 tiles, two chunks
-    (256, 512, 40, 40, 2, True, False),    # 40 x 6 tiles (7 per image, the last ragged), four workgroup columns, four chunks
-    (512, 256, 20, 20, 2, True, True),     # 20 x 10 tiles (200 of 256 pixel slots), the Bottleneck shortcut
+P8_CASES = [
+    # c1, c2, H, W, N, act, residual  (csrc/conv_p8.hip: Cin % 64 == 0, Cout % 128 == 0, 3x3 stride 1)
+    (128, 128, 80, 80, 1, True, False),    # two chunks
+    (256, 512, 40, 40, 2, True, False),    # four workgroup columns, four chunks
+    (512, 256, 20, 20, 2, True, True),     # the Bottleneck shortcut
     (64, 128, 33, 47, 1, False, False),    # one chunk, ragged right / bottom tiles, no activation
-    (128, 256, 9, 11, 3, True, True),      # a map smaller than a tile (99 of 256 slots), shortcut
-    (192, 128, 24, 56, 1, True, False),    # three chunks, 56-pixel-wide tiles
-]
-
-
-@pytest.mark.parametrize("case", MM_CASES, ids=[f"c{c[0]}-{c[1]}_{c[2]}x{c[3]}n{c[4]}{'' if c[5] else '_lin'}{'_res' if c[6] else ''}" for c in MM_CASES])
-def test_conv_mm_kernel(case):
-    """bf16 3x3 convs forced through conv_mm_kernel (upa_opts.conv_mm = 2) vs the oracle Conv (conv.py:188-197, + the Bottleneck add
-    block.py:668) on BN-folded bf16 weights: every tile shape the host picks (16 x 16, 40 x 6, 20 x 10, ragged and undersized maps),
-    1 - 4 chunks, 1 - 4 workgroup columns, the shortcut read, the lane remap of the 32 x 32 x 16 fragments and the permlane32 epilogue."""
-    from tests.hip_utils import assert_bf16_close, bf16_round, bf16_weight_oracle, to_cpu_nchw, to_dev_nhwc
-    from ultralytics_pro_amd import _lib as L
-    from ultralytics_pro_amd.engine import runtime as R
-    pm, _ = _mods()
-    c1, c2, H, W, N, act, res = case
-    with R.use_opts(conv_mm=2):
-        var = L.lib().upa_conv_variant(N, H, W, c1, c2, 3, 1, 1, 1, R.opts_ptr())
-        assert (var >> 25) & 1, "case is not dispatched to conv_mm"
-        o, m = _pair(om.Conv, pm.Conv, (c1, c2, 3, 1, None, 1, 1, act), "conv_mm")
-        x = bf16_round(P.uniform(f"mm{case}", (N, c1, H, W), -1, 1))
-        rsd = bf16_round(P.uniform(f"mmres{case}", (N, c2, H, W), -1, 1)) if res else None
-        with torch.no_grad():
-            ref = bf16_weight_oracle(o)(x) + (rsd if res else 0)
-            y = to_cpu_nchw(m(to_dev_nhwc(x, torch.bfloat16), residual=to_dev_nhwc(rsd, torch.bfloat16) if res else None))
-    assert_bf16_close(y, ref, f"conv_mm{case}")
-
-
-P8_CASES = MM_CASES + [
+    (128, 256, 9, 11, 3, True, True),      # a map smaller than a tile, shortcut
+    (192, 128, 24, 56, 1, True, False),    # three chunks
     (1024, 128, 20, 20, 1, True, False),   # sixteen chunks: the halo double buffer and the weight ring wrap many times
     (64, 256, 16, 16, 2, True, True),      # ONE chunk: the prefetch of a chunk that does not exist (zero pieces), shortcut
 ]

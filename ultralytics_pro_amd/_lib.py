@@ -29,7 +29,7 @@ class Opts(C.Structure):
     parity tests / sweep tools wrap calls in `runtime.use_opts(Opts(...))`.  `Opts.from_env()` maps the UPA_* variable names
     of rounds 1-2 onto fields for the command-line tools (tools/bench_conv.py, tools/experiments)."""
 
-    _fields_ = [("size", C.c_uint32), ("conv_big", _i), ("conv_big_bm", _i), ("conv_force", _i * 4), ("conv_ckt", _i),
+    _fields_ = [("size", C.c_uint32), ("conv_big", _i), ("conv_big_bm", _i), ("conv_ckt", _i),
                 ("no_ws", _i), ("no_pipe", _i), ("no_1x1", _i), ("no_c16", _i), ("no_upcat", _i),
                 ("pipe_all", _i), ("pipe_min_tiles", _i), ("pipe_wgs", _i), ("c16_wgs", _i),
                 ("c1_mt", _i), ("c1_waves", _i), ("c1_wgs", _i),
@@ -37,16 +37,13 @@ class Opts(C.Structure):
                 ("c2f", _i), ("c2f16_waves", _i), ("c2f32_th", _i),
                 ("no_branch_tail", _i), ("branch_tail_bm", _i),
                 ("stem_wgs", _i), ("stemf_wgs", _i), ("stemf_waves", _i), ("stem_no_mfma", _i),
-                ("ablate_conv", _i), ("ablate_pipe", _i), ("ablate_c1", _i), ("ablate_stem", _i), ("c2f64_max_px", _i), ("conv_ws3", _i), ("no_group", _i), ("no_c2f32_up", _i), ("conv_mm", _i), ("no_xcd", _i), ("keys_only", _i), ("conv_p8", _i), ("c2f_stream", _i), ("c2f_stream_rows", _i), ("no_stack_first", _i), ("no_epi_stats", _i), ("nms_stages", _i), ("nms_first_prefix", _i), ("detect_stream", _i), ("detect_stream_rows", _i), ("no_sppf_front", _i), ("no_c2f16_down", _i)]
+                ("ablate_conv", _i), ("ablate_pipe", _i), ("ablate_c1", _i), ("ablate_stem", _i), ("c2f64_max_px", _i), ("conv_ws3", _i), ("no_group", _i), ("no_c2f32_up", _i), ("no_xcd", _i), ("keys_only", _i), ("conv_p8", _i), ("c2f_stream", _i), ("c2f_stream_rows", _i), ("no_stack_first", _i), ("no_epi_stats", _i), ("nms_stages", _i), ("nms_first_prefix", _i), ("detect_stream", _i), ("detect_stream_rows", _i), ("no_sppf_front", _i), ("no_c2f16_down", _i)]
 
     def __init__(self, **kw):
         super().__init__()
         self.size = C.sizeof(Opts)
         for k, v in kw.items():
-            if k == "conv_force":
-                for j, x in enumerate(v):
-                    self.conv_force[j] = int(x)
-            elif k in dict(self._fields_):
+            if k in dict(self._fields_):
                 setattr(self, k, int(v))
             else:
                 raise AttributeError(f"upa_opts has no field '{k}'")
@@ -55,11 +52,7 @@ class Opts(C.Structure):
         o = Opts()
         C.memmove(C.byref(o), C.byref(self), C.sizeof(Opts))
         for k, v in kw.items():
-            if k == "conv_force":
-                for j, x in enumerate(v):
-                    o.conv_force[j] = int(x)
-            else:
-                setattr(o, k, int(v))
+            setattr(o, k, int(v))
         return o
 
     # name of the round-1/2 environment switch -> (field, value transform)
@@ -84,9 +77,6 @@ class Opts(C.Structure):
         for name, (field, conv) in cls._ENV.items():
             if name in env:
                 setattr(o, field, conv(env[name]))
-        if "UPA_CONV_FORCE" in env:
-            for j, x in enumerate(env["UPA_CONV_FORCE"].split(",")[:4]):
-                o.conv_force[j] = int(x)
         return o
 
 

@@ -666,15 +666,14 @@ struct TileCfg {
   int TH, TW;
 };
 
-thread_local int g_query_only = 0;   // upa_conv_variant: run the dispatch logic without launching
-thread_local int g_last_variant = 0;
-
+// The launchers below take query_only (1 = resolve the instantiation, launch nothing) and variant (if non-null: receives the
+// instantiation in upa_conv_variant's bit layout) as the other kernel families' launchers do.
 template <typename T, int WM, int WN, int MTW, int NTW, int CKT>
-int launch_conv_ckt(ConvParams& p, hipStream_t stream) {
+int launch_conv_ckt(ConvParams& p, hipStream_t stream, int query_only, int* variant) {
   constexpr int BM = WM * MTW * 16;
   constexpr int BN = WN * NTW * 16;
-  g_last_variant = (CKT << 16) | (WM << 12) | (WN << 8) | (MTW << 4) | NTW;
-  if (g_query_only) return UPA_OK;
+  if (variant) *variant = (CKT << 16) | (WM << 12) | (WN << 8) | (MTW << 4) | NTW;
+  if (query_only) return UPA_OK;
   // tile shape: BM pixels as TH x TW
   int TW, TH;
   if (p.KS == 1 && p.stride == 1 && p.pad == 0) {
@@ -716,16 +715,16 @@ int launch_conv_ckt(ConvParams& p, hipStream_t stream) {
 }
 
 template <typename T, int WM, int WN, int MTW, int NTW>
-int launch_conv(ConvParams& p, hipStream_t stream) {
-  if (p.CKT == 4) return launch_conv_ckt<T, WM, WN, MTW, NTW, 4>(p, stream);
-  if (p.CKT == 2) return launch_conv_ckt<T, WM, WN, MTW, NTW, 2>(p, stream);
-  return launch_conv_ckt<T, WM, WN, MTW, NTW, 1>(p, stream);
+int launch_conv(ConvParams& p, hipStream_t stream, int query_only, int* variant) {
+  if (p.CKT == 4) return launch_conv_ckt<T, WM, WN, MTW, NTW, 4>(p, stream, query_only, variant);
+  if (p.CKT == 2) return launch_conv_ckt<T, WM, WN, MTW, NTW, 2>(p, stream, query_only, variant);
+  return launch_conv_ckt<T, WM, WN, MTW, NTW, 1>(p, stream, query_only, variant);
 }
 
 
 // ---- weights-stationary launcher: returns UPA_EUNSUPPORTED when the problem does not qualify (caller falls back)
 template <typename T, int WM, int WN, int MTW, int NTW, int KTT>
-int launch_ws(ConvParams& p, hipStream_t stream) {
+int launch_ws(ConvParams& p, hipStream_t stream, int query_only, int* variant) {
   constexpr int BM = WM * MTW * 16;
   constexpr int NTB = WN * NTW;
   const int taps = p.KS * p.KS;
@@ -770,8 +769,8 @@ int launch_ws(ConvParams& p, hipStream_t stream) {
   int gx = numCU * perCU / gridY;
   if (gx < 1) gx = 1;
   if (gx > p.numTiles) gx = p.numTiles;
-  g_last_variant = (1 << 20) | (KTT << 16) | (WM << 12) | (WN << 8) | (MTW << 4) | NTW;
-  if (g_query_only) return UPA_OK;
+  if (variant) *variant = (1 << 20) | (KTT << 16) | (WM << 12) | (WN << 8) | (MTW << 4) | NTW;
+  if (query_only) return UPA_OK;
   auto kern = conv_ws_kernel<T, WM, WN, MTW, NTW, KTT>;
   if (hipError_t e = upa_full_lds<conv_ws_kernel<T, WM, WN, MTW, NTW, KTT>>(); e != hipSuccess) {
     upa_set_error("conv ws: cannot raise LDS limit: %s", hipGetErrorString(e));
@@ -783,187 +782,185 @@ int launch_ws(ConvParams& p, hipStream_t stream) {
 }
 
 template <typename T, int KTT>
-int dispatch_ws_ktt(ConvParams p, hipStream_t stream) {  // p by value: launch_ws mutates it
+int dispatch_ws_ktt(ConvParams p, hipStream_t stream, int query_only, int* variant) {  // p by value: launch_ws mutates it
   const int ntn = p.NTn;
   const long M = (long)p.N * p.OH * p.OW;
   if (M < 64 * 1024) return UPA_EUNSUPPORTED;              // few tiles: the one-tile-per-workgroup kernel parallelises better
-  if (ntn == 1) return launch_ws<T, 4, 1, 4, 1, KTT>(p, stream);   // 256 px x 16 ch
-  if (ntn == 2) return launch_ws<T, 4, 1, 4, 2, KTT>(p, stream);   // 256 px x 32 ch
+  if (ntn == 1) return launch_ws<T, 4, 1, 4, 1, KTT>(p, stream, query_only, variant);                 // 256 px x 16 ch
+  if (ntn == 2) return launch_ws<T, 4, 1, 4, 2, KTT>(p, stream, query_only, variant);                 // 256 px x 32 ch
   if (ntn == 4) {
     ConvParams q = p;
-    int rc = launch_ws<T, 4, 1, 4, 4, KTT>(q, stream);             // 256 px x 64 ch
+    int rc = launch_ws<T, 4, 1, 4, 4, KTT>(q, stream, query_only, variant);                           // 256 px x 64 ch
     if (rc != UPA_EUNSUPPORTED) return rc;
-    return launch_ws<T, 2, 2, 4, 2, KTT>(p, stream);               // 128 px x 64 ch
+    return launch_ws<T, 2, 2, 4, 2, KTT>(p, stream, query_only, variant);                             // 128 px x 64 ch
   }
   return UPA_EUNSUPPORTED;
 }
 
 template <typename T>
-int dispatch_ws(const ConvParams& p, hipStream_t stream) {
+int dispatch_ws(const ConvParams& p, hipStream_t stream, int query_only, int* variant) {
   if (UPA_OPT(p.opts, no_ws)) return UPA_EUNSUPPORTED;
   if (p.KS != 3 || p.stride != 1) return UPA_EUNSUPPORTED;  // 1x1 and stride-2 layers measured faster on the igemm kernel
-  if (p.KTT == 1) return dispatch_ws_ktt<T, 1>(p, stream);
-  if (p.KTT == 2) return dispatch_ws_ktt<T, 2>(p, stream);
-  if (p.KTT == 4) return dispatch_ws_ktt<T, 4>(p, stream);
-  return UPA_EUNSUPPORTED;
-}
-
-// Tuning hook (development): upa_opts.conv_force = {WM, WN, MTW, NTW} forces one of the extra bf16 instantiations below for
-// every conv whose Cout fits it; used by tools/bench_conv.py sweeps, never set in production.
-template <typename T>
-int dispatch_forced(ConvParams& p, hipStream_t stream) {
-  if constexpr (sizeof(T) == 2) {
-    const upa_opts* o = p.opts;
-    if (!o || o->size < offsetof(upa_opts, conv_force) + sizeof(o->conv_force) || o->conv_force[0] == 0) return UPA_EUNSUPPORTED;
-    const int wm = o->conv_force[0], wn = o->conv_force[1], mt = o->conv_force[2], nt = o->conv_force[3];
-    if (wn <= 0 || nt <= 0) return UPA_EUNSUPPORTED;
-    if (p.NTn % (wn * nt) != 0 && p.NTn > wn * nt) return UPA_EUNSUPPORTED;
-    if (p.NTn < wn * nt) return UPA_EUNSUPPORTED;
-#define UPA_TRY(A, B, C, D) if (wm == A && wn == B && mt == C && nt == D) return launch_conv<T, A, B, C, D>(p, stream);
-    UPA_TRY(4, 1, 4, 2) UPA_TRY(4, 1, 2, 4) UPA_TRY(2, 2, 8, 2) UPA_TRY(4, 2, 2, 2) UPA_TRY(4, 1, 4, 4) UPA_TRY(2, 4, 4, 1)
-    UPA_TRY(4, 2, 4, 1) UPA_TRY(8, 1, 2, 2) UPA_TRY(4, 1, 4, 1) UPA_TRY(8, 1, 2, 1) UPA_TRY(4, 2, 4, 2)
-#undef UPA_TRY
-  }
+  if (p.KTT == 1) return dispatch_ws_ktt<T, 1>(p, stream, query_only, variant);
+  if (p.KTT == 2) return dispatch_ws_ktt<T, 2>(p, stream, query_only, variant);
+  if (p.KTT == 4) return dispatch_ws_ktt<T, 4>(p, stream, query_only, variant);
   return UPA_EUNSUPPORTED;
 }
 
 template <typename T>
-int dispatch_conv(ConvParams& p, hipStream_t stream) {
-  {
-    const int rcf = dispatch_forced<T>(p, stream);
-    if (rcf != UPA_EUNSUPPORTED) return rcf;
-    const int rc = dispatch_ws<T>(p, stream);
-    if (rc != UPA_EUNSUPPORTED) return rc;
-  }
+int dispatch_conv(ConvParams& p, hipStream_t stream, int query_only, int* variant) {
+  if (const int rc = dispatch_ws<T>(p, stream, query_only, variant); rc != UPA_EUNSUPPORTED) return rc;
   const int ntn = p.NTn;
   const long M = (long)p.N * p.OH * p.OW;
   // n-tiling: prefer covering all output channels in one workgroup (input tile read once)
   // candidates (WM, WN, MTW, NTW): BM = WM*MTW*16, BN = WN*NTW*16
-  if (ntn == 1) return launch_conv<T, 4, 1, 2, 1>(p, stream);                     // BN=16,  BM=128
-  if (ntn == 2) return launch_conv<T, 4, 1, 2, 2>(p, stream);                     // BN=32,  BM=128
-  if (ntn == 3) return launch_conv<T, 4, 1, 2, 3>(p, stream);                     // BN=48
+  if (ntn == 1) return launch_conv<T, 4, 1, 2, 1>(p, stream, query_only, variant);                    // BN=16,  BM=128
+  if (ntn == 2) return launch_conv<T, 4, 1, 2, 2>(p, stream, query_only, variant);                    // BN=32,  BM=128
+  if (ntn == 3) return launch_conv<T, 4, 1, 2, 3>(p, stream, query_only, variant);                    // BN=48
   if (ntn == 5) {  // Cout = 80 (Detect class branch): run as 96 = 2 x 3 n-tiles, the 6th tile is zero-filled
-    if (M >= 128 * 1024) return launch_conv<T, 2, 2, 4, 3>(p, stream);            // BN=96, BM=128
-    return launch_conv<T, 2, 2, 2, 3>(p, stream);                                 // BN=96, BM=64
+    if (M >= 128 * 1024) return launch_conv<T, 2, 2, 4, 3>(p, stream, query_only, variant);           // BN=96, BM=128
+    return launch_conv<T, 2, 2, 2, 3>(p, stream, query_only, variant);                                // BN=96, BM=64
   }
   if (ntn % 4 == 0) {
-    if (M >= 128 * 1024 || ntn == 4) return launch_conv<T, 2, 2, 4, 2>(p, stream);  // BN=64, BM=128
-    return launch_conv<T, 2, 2, 2, 2>(p, stream);                                 // BN=64, BM=64 (small maps)
+    if (M >= 128 * 1024 || ntn == 4) return launch_conv<T, 2, 2, 4, 2>(p, stream, query_only, variant);  // BN=64, BM=128
+    return launch_conv<T, 2, 2, 2, 2>(p, stream, query_only, variant);                                // BN=64, BM=64 (small maps)
   }
-  if (ntn % 2 == 0) return launch_conv<T, 4, 1, 2, 2>(p, stream);
-  return launch_conv<T, 4, 1, 2, 1>(p, stream);
+  if (ntn % 2 == 0) return launch_conv<T, 4, 1, 2, 2>(p, stream, query_only, variant);
+  return launch_conv<T, 4, 1, 2, 1>(p, stream, query_only, variant);
+}
+
+// The kernel family a convolution runs on, in the order of preference.  ConvEntry = the entry point asking: upa_conv2d_bias_act,
+// upa_conv2d_bn_stats, or a member of upa_conv2d_bias_act_group.
+enum class ConvPath { WS3, P8, BIG, PIPE, C1X1, GENERIC };
+enum class ConvEntry { PLAIN, STATS, GROUP };
+
+// The first family from `from` on whose rule takes shape s (a family whose launcher then finds the problem outside its tiles
+// returns UPA_EUNSUPPORTED, and upa_conv2d_bias_act asks again from the next one).
+ConvPath conv_path(const ConvShape& s, const upa_opts* opts, ConvEntry entry, ConvPath from = ConvPath::WS3) {
+  if (from <= ConvPath::WS3 && upa_conv_ws3_eligible(s, opts)) return ConvPath::WS3;
+  // STATS: conv_p8 has no statistics epilogue (nor has conv_pipe: the caller reduces z in a pass of its own there);
+  // GROUP: a member keeps to conv_big so that its neighbours can share its grid
+  if (from <= ConvPath::P8 && entry == ConvEntry::PLAIN && upa_conv_p8_eligible(s, opts)) return ConvPath::P8;
+  if (from <= ConvPath::BIG && upa_conv_big_eligible(s, opts)) return ConvPath::BIG;
+  if (from <= ConvPath::PIPE && upa_conv_pipe_eligible(s, opts)) return ConvPath::PIPE;
+  if (from <= ConvPath::C1X1 && upa_conv1x1_eligible(s, opts)) return ConvPath::C1X1;
+  return ConvPath::GENERIC;
+}
+
+// Kernel arguments of shape s for conv_ws3 / conv_p8 / conv_big (their launchers fill in the tiling)
+BigParams big_params(const ConvShape& s, const void* x, const void* w_packed, const float* bias, void* y, const void* residual) {
+  BigParams q;
+  memset(&q, 0, sizeof(q));
+  q.x = (const char*)x; q.y = (char*)y; q.res = (const char*)residual; q.w = (const char*)w_packed; q.bias = bias;
+  q.N = s.n; q.H = s.h; q.W = s.w; q.Cin = s.cin; q.ldx = s.ldx; q.Cout = s.cout; q.ldy = s.ldy; q.ldr = s.ldr;
+  q.OH = (s.h + 2 * s.pad - s.k) / s.stride + 1;
+  q.OW = (s.w + 2 * s.pad - s.k) / s.stride + 1;
+  q.KS = s.k; q.stride = s.stride; q.pad = s.pad; q.act = s.act;
+  return q;
+}
+
+PipeParams pipe_params(const ConvShape& s, const void* x, const void* w_packed, const float* bias, void* y, const void* residual) {
+  PipeParams q;
+  memset(&q, 0, sizeof(q));
+  q.x = (const char*)x; q.y = (char*)y; q.res = (const char*)residual; q.w = (const char*)w_packed; q.bias = bias;
+  q.N = s.n; q.H = s.h; q.W = s.w; q.Cin = s.cin; q.ldx = s.ldx; q.Cout = s.cout; q.ldy = s.ldy; q.ldr = s.ldr; q.act = s.act;
+  return q;
+}
+
+C1Params c1_params(const ConvShape& s, const void* x, const void* w_packed, const float* bias, void* y) {
+  C1Params q;
+  memset(&q, 0, sizeof(q));
+  q.x = (const char*)x; q.y = (char*)y; q.w = (const char*)w_packed; q.bias = bias;
+  q.Cin = s.cin; q.ldx = s.ldx; q.Cout = s.cout; q.ldy = s.ldy; q.act = s.act;
+  return q;
+}
+
+// The argument rules of upa_conv2d_bias_act that do not look at pointers (upa_conv_variant applies them too)
+int conv_check(const ConvShape& s) {
+  UPA_CHECK_ARG(s.n > 0 && s.h > 0 && s.w > 0 && s.cin > 0 && s.cout > 0, "conv2d: bad shape");
+  UPA_CHECK_ARG(s.k >= 1 && s.k <= 7 && s.stride >= 1 && s.stride <= 2 && s.pad >= 0 && s.pad < s.k, "conv2d: unsupported k/s/p");
+  UPA_CHECK_ARG(s.dtype == UPA_F32 || s.dtype == UPA_BF16, "conv2d: bad dtype");
+  const int E = 16 / upa_elem_size(s.dtype);
+  UPA_CHECK_ARG(s.cin % E == 0 && s.ldx % E == 0, "conv2d: cin/ldx must be multiples of %d elements", E);
+  UPA_CHECK_ARG(s.cout % E == 0 && s.ldy % E == 0 && s.ldr % E == 0,
+                "conv2d: cout/ldy/ldr must be multiples of %d elements (16-byte row stores)", E);
+  return UPA_OK;
+}
+
+// The tile-per-workgroup implicit GEMM (conv_igemm_kernel) or its weights-stationary form (conv_ws_kernel): every shape and dtype
+int conv_generic(const ConvShape& s, const void* x, const void* w_packed, const float* bias, void* y, const void* residual,
+                 const upa_opts* opts, void* stream, int query_only, int* variant) {
+  ConvParams p;
+  memset(&p, 0, sizeof(p));
+  p.x = (const char*)x; p.y = (char*)y; p.res = (const char*)residual; p.w = (const char*)w_packed; p.bias = bias;
+  p.N = s.n; p.H = s.h; p.W = s.w; p.Cin = s.cin; p.ldx = s.ldx;
+  p.OH = (s.h + 2 * s.pad - s.k) / s.stride + 1;
+  p.OW = (s.w + 2 * s.pad - s.k) / s.stride + 1;
+  p.Cout = s.cout; p.ldy = s.ldy; p.ldr = s.ldr;
+  p.KS = s.k; p.stride = s.stride; p.pad = s.pad; p.act = s.act;
+  p.opts = opts;
+#ifdef UPA_ABLATE
+  p.ablate = UPA_OPT(opts, ablate_conv);
+#endif
+  const int ktch = 64 / upa_elem_size(s.dtype);
+  p.KTT = cdiv(s.cin, ktch);
+  p.NTn = cdiv(s.cout, 16);
+  // chunk = CKT k-tiles; CKT must divide KTT (every chunk full). Up to 4 (256 B of channels per pixel) for stride 1,
+  // 2 for stride 2 (bigger halo tile) and for wide-N variants (register budget of the per-tap weight buffers).
+  int ckt = (p.KTT % 4 == 0) ? 4 : ((p.KTT % 2 == 0) ? 2 : 1);
+  if ((s.stride == 2 || p.NTn == 5 || p.NTn == 3) && ckt > 2) ckt = 2;
+  if (s.k > 3 && ckt > 1) ckt = 1;
+  if (const int v = UPA_OPT(opts, conv_ckt); (v == 1 || v == 2 || v == 4) && p.KTT % v == 0 && v <= ckt) ckt = v;  // tuning override
+  p.CKT = ckt;
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = s.dtype == UPA_BF16 ? dispatch_conv<bf16_t>(p, st, query_only, variant) : dispatch_conv<float>(p, st, query_only, variant);
+  if (rc == UPA_EUNSUPPORTED) upa_set_error("conv2d: tile does not fit LDS (k=%d s=%d cin=%d)", s.k, s.stride, s.cin);
+  return rc;
+}
+
+// upa_conv2d_bias_act after its argument checks; query_only / variant as the launchers take them
+int conv_run(const ConvShape& s, const void* x, const void* w_packed, const float* bias, void* y, const void* residual,
+             const upa_opts* opts, void* stream, int query_only, int* variant) {
+  for (ConvPath path = conv_path(s, opts, ConvEntry::PLAIN);; path = conv_path(s, opts, ConvEntry::PLAIN, ConvPath((int)path + 1))) {
+    int rc = UPA_EUNSUPPORTED;
+    switch (path) {
+      case ConvPath::WS3: rc = upa_conv_ws3_launch(big_params(s, x, w_packed, bias, y, residual), query_only, variant, stream, opts); break;
+      case ConvPath::P8: rc = upa_conv_p8_launch(big_params(s, x, w_packed, bias, y, residual), query_only, variant, stream, opts); break;
+      case ConvPath::BIG: rc = upa_conv_big_launch(big_params(s, x, w_packed, bias, y, residual), query_only, variant, stream, opts); break;
+      case ConvPath::PIPE:
+        return upa_conv_pipe_launch(pipe_params(s, x, w_packed, bias, y, residual), query_only, variant, stream, opts);
+      case ConvPath::C1X1:
+        return upa_conv1x1_launch(c1_params(s, x, w_packed, bias, y), s.n * s.h * s.w, query_only, variant, stream, opts);
+      case ConvPath::GENERIC: return conv_generic(s, x, w_packed, bias, y, residual, opts, stream, query_only, variant);
+    }
+    if (rc != UPA_EUNSUPPORTED) return rc;
+  }
 }
 
 }  // namespace
-
-extern "C" int upa_conv2d_bias_act(const void*, int, int, int, int, int, const void*, const float*, void*, int, int,
-                                   const void*, int, int, int, int, int, int, const upa_opts*, void*);
 
 // Which template instantiation (WM<<12 | WN<<8 | MTW<<4 | NTW) upa_conv2d_bias_act would launch for this problem;
 // lets bench.py attribute algorithmic FLOPs to the kernel names rocprofv3 reports.
 extern "C" int upa_conv_variant(int n, int h, int w, int cin, int cout, int k, int stride, int pad, int dtype,
                                 const upa_opts* opts) {
-  static char dummy[64];
-  g_query_only = 1;
-  g_last_variant = 0;
   const int E = 16 / upa_elem_size(dtype);
-  int rc = upa_conv2d_bias_act(dummy, n, h, w, cin, (cin + E - 1) / E * E, dummy, nullptr, dummy, cout, cout, nullptr, 0, k,
-                               stride, pad, 0, dtype, opts, nullptr);
-  g_query_only = 0;
-  return rc == UPA_OK ? g_last_variant : rc;
+  const ConvShape s{n, h, w, cin, (cin + E - 1) / E * E, cout, cout, 0, k, stride, pad, UPA_ACT_NONE, dtype};
+  if (const int rc = conv_check(s); rc != UPA_OK) return rc;
+  int variant = 0;
+  const int rc = conv_run(s, nullptr, nullptr, nullptr, nullptr, nullptr, opts, nullptr, 1, &variant);
+  return rc == UPA_OK ? variant : rc;
 }
 
 extern "C" int upa_conv2d_bias_act(const void* x, int n, int h, int w, int cin, int ldx, const void* w_packed,
                                    const float* bias, void* y, int cout, int ldy, const void* residual, int ldr, int k,
                                    int stride, int pad, int act, int dtype, const upa_opts* opts, void* stream) {
   UPA_CHECK_ARG(x && w_packed && y, "conv2d: null pointer");
-  UPA_CHECK_ARG(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0, "conv2d: bad shape");
-  UPA_CHECK_ARG(k >= 1 && k <= 7 && stride >= 1 && stride <= 2 && pad >= 0 && pad < k, "conv2d: unsupported k/s/p");
-  UPA_CHECK_ARG(dtype == UPA_F32 || dtype == UPA_BF16, "conv2d: bad dtype");
-  const int es = upa_elem_size(dtype);
-  const int E = 16 / es;
-  UPA_CHECK_ARG(cin % E == 0 && ldx % E == 0, "conv2d: cin/ldx must be multiples of %d elements", E);
-  UPA_CHECK_ARG(cout % E == 0 && ldy % E == 0 && (!residual || ldr % E == 0),
-                "conv2d: cout/ldy/ldr must be multiples of %d elements (16-byte row stores)", E);
-  UPA_CHECK_ARG(g_query_only || (((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) &&
-                                 (!residual || (uintptr_t)residual % 16 == 0)), "conv2d: misaligned view");
-  if (upa_conv_ws3_eligible(n, h, w, cin, ldx, cout, ldy, residual != nullptr, k, stride, pad, act, dtype, opts)) {
-    BigParams q;
-    memset(&q, 0, sizeof(q));
-    q.x = (const char*)x; q.y = (char*)y; q.res = (const char*)residual; q.w = (const char*)w_packed; q.bias = bias;
-    q.N = n; q.H = h; q.W = w; q.Cin = cin; q.ldx = ldx; q.Cout = cout; q.ldy = ldy; q.ldr = ldr; q.OH = h; q.OW = w;
-    q.KS = 3; q.stride = 1; q.pad = 1; q.act = act;
-    const int rc = upa_conv_ws3_launch(q, g_query_only, &g_last_variant, stream, opts);
-    if (rc != UPA_EUNSUPPORTED) return rc;
-  }
-  if (upa_conv_p8_eligible(n, h, w, cin, ldx, cout, ldy, residual ? ldr : 0, k, stride, pad, act, dtype, opts)) {
-    BigParams q;
-    memset(&q, 0, sizeof(q));
-    q.x = (const char*)x; q.y = (char*)y; q.res = (const char*)residual; q.w = (const char*)w_packed; q.bias = bias;
-    q.N = n; q.H = h; q.W = w; q.Cin = cin; q.ldx = ldx; q.Cout = cout; q.ldy = ldy; q.ldr = ldr; q.act = act;
-    const int rc = upa_conv_p8_launch(q, g_query_only, &g_last_variant, stream, opts);
-    if (rc != UPA_EUNSUPPORTED) return rc;
-  }
-  if (upa_conv_mm_eligible(n, h, w, cin, ldx, cout, ldy, residual ? ldr : 0, k, stride, pad, act, dtype, opts)) {
-    BigParams q;
-    memset(&q, 0, sizeof(q));
-    q.x = (const char*)x; q.y = (char*)y; q.res = (const char*)residual; q.w = (const char*)w_packed; q.bias = bias;
-    q.N = n; q.H = h; q.W = w; q.Cin = cin; q.ldx = ldx; q.Cout = cout; q.ldy = ldy; q.ldr = ldr; q.act = act;
-    const int rc = upa_conv_mm_launch(q, g_query_only, &g_last_variant, stream, opts);
-    if (rc != UPA_EUNSUPPORTED) return rc;
-  }
-  if (upa_conv_big_eligible(n, h, w, cin, ldx, cout, ldy, residual ? ldr : 0, k, stride, pad, act, dtype, opts)) {
-    BigParams q;
-    memset(&q, 0, sizeof(q));
-    q.x = (const char*)x; q.y = (char*)y; q.res = (const char*)residual; q.w = (const char*)w_packed; q.bias = bias;
-    q.N = n; q.H = h; q.W = w; q.Cin = cin; q.ldx = ldx; q.Cout = cout; q.ldy = ldy; q.ldr = ldr;
-    q.OH = (h + 2 * pad - k) / stride + 1;
-    q.OW = (w + 2 * pad - k) / stride + 1;
-    q.KS = k; q.stride = stride; q.pad = pad; q.act = act;
-    const int rc = upa_conv_big_launch(q, g_query_only, &g_last_variant, stream, opts);
-    if (rc != UPA_EUNSUPPORTED) return rc;
-  }
-  if (upa_conv_pipe_eligible(n, h, w, cin, ldx, cout, ldy, residual ? ldr : 0, k, stride, pad, act, dtype, opts)) {
-    PipeParams q;
-    memset(&q, 0, sizeof(q));
-    q.x = (const char*)x; q.y = (char*)y; q.res = (const char*)residual; q.w = (const char*)w_packed; q.bias = bias;
-    q.N = n; q.H = h; q.W = w; q.Cin = cin; q.ldx = ldx; q.Cout = cout; q.ldy = ldy; q.ldr = ldr; q.act = act;
-    return upa_conv_pipe_launch(q, g_query_only, &g_last_variant, stream, opts);
-  }
-  if (upa_conv1x1_eligible(n, h, w, cin, ldx, cout, ldy, residual != nullptr, k, stride, pad, act, dtype, opts)) {
-    C1Params q;
-    memset(&q, 0, sizeof(q));
-    q.x = (const char*)x; q.y = (char*)y; q.w = (const char*)w_packed; q.bias = bias;
-    q.Cin = cin; q.ldx = ldx; q.Cout = cout; q.ldy = ldy; q.act = act;
-    return upa_conv1x1_launch(q, n * h * w, g_query_only, &g_last_variant, stream, opts);
-  }
-  ConvParams p;
-  memset(&p, 0, sizeof(p));
-  p.x = (const char*)x; p.y = (char*)y; p.res = (const char*)residual; p.w = (const char*)w_packed; p.bias = bias;
-  p.N = n; p.H = h; p.W = w; p.Cin = cin; p.ldx = ldx;
-  p.OH = (h + 2 * pad - k) / stride + 1;
-  p.OW = (w + 2 * pad - k) / stride + 1;
-  p.Cout = cout; p.ldy = ldy; p.ldr = ldr;
-  p.KS = k; p.stride = stride; p.pad = pad; p.act = act;
-  p.opts = opts;
-#ifdef UPA_ABLATE
-  p.ablate = UPA_OPT(opts, ablate_conv);
-#endif
-  const int ktch = 64 / es;
-  p.KTT = cdiv(cin, ktch);
-  p.NTn = cdiv(cout, 16);
-  // chunk: up to 4 k-tiles (256 B of channels per pixel) for stride 1, 2 for stride 2 (bigger halo)
-  // chunk = CKT k-tiles; CKT must divide KTT (every chunk full). Up to 4 (256 B of channels per pixel) for stride 1,
-  // 2 for stride 2 (bigger halo tile) and for wide-N variants (register budget of the per-tap weight buffers).
-  int ckt = (p.KTT % 4 == 0) ? 4 : ((p.KTT % 2 == 0) ? 2 : 1);
-  if ((stride == 2 || p.NTn == 5 || p.NTn == 3) && ckt > 2) ckt = 2;
-  if (k > 3 && ckt > 1) ckt = 1;
-  if (const int v = UPA_OPT(opts, conv_ckt); (v == 1 || v == 2 || v == 4) && p.KTT % v == 0 && v <= ckt) ckt = v;  // tuning override
-  p.CKT = ckt;
-  hipStream_t s = (hipStream_t)stream;
-  int rc = dtype == UPA_BF16 ? dispatch_conv<bf16_t>(p, s) : dispatch_conv<float>(p, s);
-  if (rc == UPA_EUNSUPPORTED) upa_set_error("conv2d: tile does not fit LDS (k=%d s=%d cin=%d)", k, stride, cin);
-  return rc;
+  UPA_CHECK_ARG(!residual || ldr > 0, "conv2d: residual without a pixel stride");
+  const ConvShape s{n, h, w, cin, ldx, cout, ldy, residual ? ldr : 0, k, stride, pad, act, dtype};
+  if (const int rc = conv_check(s); rc != UPA_OK) return rc;
+  UPA_CHECK_ARG(((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) && (!residual || (uintptr_t)residual % 16 == 0),
+                "conv2d: misaligned view");
+  return conv_run(s, x, w_packed, bias, y, residual, opts, stream, 0, nullptr);
 }
 
 // Training forward of Conv (conv.py:177-186 in train mode): z = conv2d(x) (no bias, no activation) AND nn.BatchNorm2d's batch statistics
@@ -988,32 +985,28 @@ extern "C" int upa_conv2d_bn_stats(const void* x, int n, int h, int w, int cin, 
   if (!mode && dtype == UPA_BF16 && cout % 16 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)z % 16) == 0) {
     float* rows = reinterpret_cast<float*>(ws);
     const long max_rows = (long)(upa_channel_reduce_workspace_bytes(cout) / ((size_t)2 * cout * sizeof(float)));
+    const ConvShape s{n, h, w, cin, ldx, cout, ldz, 0, k, stride, pad, UPA_ACT_NONE, dtype};
     int nrows = 0, rc = UPA_EUNSUPPORTED;
-    if (upa_conv_ws3_eligible(n, h, w, cin, ldx, cout, ldz, false, k, stride, pad, UPA_ACT_NONE, dtype, opts)) {
-      BigParams q;
-      memset(&q, 0, sizeof(q));
-      q.x = (const char*)x; q.y = (char*)z; q.w = (const char*)w_packed;
-      q.N = n; q.H = h; q.W = w; q.Cin = cin; q.ldx = ldx; q.Cout = cout; q.ldy = ldz; q.OH = h; q.OW = w;
-      q.KS = 3; q.stride = 1; q.pad = 1; q.act = UPA_ACT_NONE;
-      q.stats = rows;
-      rc = upa_conv_ws3_launch_stats(q, &nrows, max_rows, stream, opts);
-    } else if (upa_conv_big_eligible(n, h, w, cin, ldx, cout, ldz, 0, k, stride, pad, UPA_ACT_NONE, dtype, opts)) {
-      BigParams q;
-      memset(&q, 0, sizeof(q));
-      q.x = (const char*)x; q.y = (char*)z; q.w = (const char*)w_packed;
-      q.N = n; q.H = h; q.W = w; q.Cin = cin; q.ldx = ldx; q.Cout = cout; q.ldy = ldz; q.OH = oh; q.OW = ow;
-      q.KS = k; q.stride = stride; q.pad = pad; q.act = UPA_ACT_NONE;
-      q.stats = rows;
-      rc = upa_conv_big_launch_stats(q, &nrows, max_rows, stream, opts);
-    } else if (!upa_conv_ws3_eligible(n, h, w, cin, ldx, cout, ldz, false, k, stride, pad, UPA_ACT_NONE, dtype, opts) &&
-               !upa_conv_pipe_eligible(n, h, w, cin, ldx, cout, ldz, 0, k, stride, pad, UPA_ACT_NONE, dtype, opts) &&
-               upa_conv1x1_eligible(n, h, w, cin, ldx, cout, ldz, false, k, stride, pad, UPA_ACT_NONE, dtype, opts)) {
-      C1Params q;
-      memset(&q, 0, sizeof(q));
-      q.x = (const char*)x; q.y = (char*)z; q.w = (const char*)w_packed;
-      q.Cin = cin; q.ldx = ldx; q.Cout = cout; q.ldy = ldz; q.act = UPA_ACT_NONE;
-      q.stats = rows;
-      rc = upa_conv1x1_launch_stats(q, n * h * w, &nrows, max_rows, stream, opts);
+    switch (conv_path(s, opts, ConvEntry::STATS)) {
+      case ConvPath::WS3: {
+        BigParams q = big_params(s, x, w_packed, nullptr, z, nullptr);
+        q.stats = rows;
+        rc = upa_conv_ws3_launch_stats(q, &nrows, max_rows, stream, opts);
+        break;
+      }
+      case ConvPath::BIG: {
+        BigParams q = big_params(s, x, w_packed, nullptr, z, nullptr);
+        q.stats = rows;
+        rc = upa_conv_big_launch_stats(q, &nrows, max_rows, stream, opts);
+        break;
+      }
+      case ConvPath::C1X1: {
+        C1Params q = c1_params(s, x, w_packed, nullptr, z);
+        q.stats = rows;
+        rc = upa_conv1x1_launch_stats(q, n * h * w, &nrows, max_rows, stream, opts);
+        break;
+      }
+      default: break;  // no statistics epilogue on that path
     }
     if (rc == UPA_OK) return upa_bn_finalize_rows(rows, nrows, cout, npix, cout, momentum, mean, var, running_mean, running_var, stream);
     if (rc != UPA_EUNSUPPORTED) return rc;
@@ -1032,14 +1025,13 @@ extern "C" int upa_conv2d_bn_stats(const void* x, int n, int h, int w, int cin, 
 extern "C" int upa_conv2d_dgrad_s2(const void* dz, int n, int oh, int ow, int cout, int lddz, const void* phase_w_packed, void* dx, int h,
                                    int w, int cin, int lddx, int accumulate, int dtype, const upa_opts* opts, void* stream) {
   UPA_CHECK_ARG(dz && phase_w_packed && dx, "conv2d_dgrad_s2: null pointer");
+  // the phase convolution: dz -> 4 cin channels at (oh + 1, ow + 1)
+  const ConvShape s{n, oh, ow, cout, lddz, 4 * cin, 4 * cin, 0, 2, 1, 1, UPA_ACT_NONE, dtype};
   if (dtype != UPA_BF16 || cin % 8 != 0 || lddx % 8 != 0 || lddz % 8 != 0 || ((uintptr_t)dz % 16) != 0 || ((uintptr_t)dx % 16) != 0 ||
-      !upa_conv_big_eligible(n, oh, ow, cout, lddz, 4 * cin, 4 * cin, 0, 2, 1, 1, UPA_ACT_NONE, dtype, opts))
+      conv_path(s, opts, ConvEntry::PLAIN) != ConvPath::BIG)
     return UPA_EUNSUPPORTED;
-  BigParams q;
-  memset(&q, 0, sizeof(q));
-  q.x = (const char*)dz; q.y = (char*)dx; q.w = (const char*)phase_w_packed; q.res = accumulate ? (const char*)dx : nullptr;
-  q.N = n; q.H = oh; q.W = ow; q.Cin = cout; q.ldx = lddz; q.Cout = 4 * cin; q.ldy = lddx; q.ldr = lddx; q.OH = oh + 1; q.OW = ow + 1;
-  q.KS = 2; q.stride = 1; q.pad = 1; q.act = UPA_ACT_NONE;
+  BigParams q = big_params(s, dz, phase_w_packed, nullptr, dx, accumulate ? dx : nullptr);
+  q.ldy = lddx; q.ldr = lddx;  // the epilogue writes (and accumulates onto) dx's interleaved pixels
   q.il_h = h; q.il_w = w; q.il_c = cin;
   return upa_conv_big_launch_interleave(q, stream, opts);
 }
@@ -1077,10 +1069,8 @@ extern "C" int upa_conv2d_pool2(const void* x, int n, int h, int w, int cin, int
     upa_set_error("conv2d_pool2: outside the fused form (bf16, k 3 s 1 p 1, SiLU, h %% 8 == 0, w %% 16 == 0, cin <= 128, cout %% 32 == 0)");
     return UPA_EUNSUPPORTED;
   }
-  PipeParams q;
-  memset(&q, 0, sizeof(q));
-  q.x = (const char*)x; q.y = (char*)y; q.w = (const char*)w_packed; q.bias = bias;
-  q.N = n; q.H = h; q.W = w; q.Cin = cin; q.ldx = ldx; q.Cout = cout; q.ldy = ldy; q.act = act; q.pool = 1;
+  PipeParams q = pipe_params({n, h, w, cin, ldx, cout, ldy, 0, k, stride, pad, act, dtype}, x, w_packed, bias, y, nullptr);
+  q.pool = 1;
   return upa_conv_pipe_launch(q, 0, nullptr, stream, opts);
 }
 
@@ -1090,19 +1080,15 @@ extern "C" int upa_conv2d_pool2(const void* x, int n, int h, int w, int cin, int
 extern "C" int upa_conv2d_bias_act_group(const upa_conv_problem* probs, int count, int k, int stride, int pad, int act, int dtype,
                                          const upa_opts* opts, void* stream) {
   UPA_CHECK_ARG(probs && count >= 1 && count <= 8, "conv2d_group: 1..8 problems");
+  auto shape = [&](const upa_conv_problem& q) {  // (a problem with a residual never joins a grid)
+    return ConvShape{q.n, q.h, q.w, q.cin, q.ldx, q.cout, q.ldy, 0, k, stride, pad, act, dtype};
+  };
   auto big_ok = [&](const upa_conv_problem& q) {
     return q.x && q.y && q.w_packed && ((uintptr_t)q.x % 16) == 0 && ((uintptr_t)q.y % 16) == 0 && !q.residual &&
-           !upa_conv_ws3_eligible(q.n, q.h, q.w, q.cin, q.ldx, q.cout, q.ldy, false, k, stride, pad, act, dtype, opts) &&
-           upa_conv_big_eligible(q.n, q.h, q.w, q.cin, q.ldx, q.cout, q.ldy, 0, k, stride, pad, act, dtype, opts);
+           conv_path(shape(q), opts, ConvEntry::GROUP) == ConvPath::BIG;
   };
   auto fill = [&](const upa_conv_problem& q) {
-    BigParams b;
-    memset(&b, 0, sizeof(b));
-    b.x = (const char*)q.x; b.y = (char*)q.y; b.w = (const char*)q.w_packed; b.bias = q.bias;
-    b.N = q.n; b.H = q.h; b.W = q.w; b.Cin = q.cin; b.ldx = q.ldx; b.Cout = q.cout; b.ldy = q.ldy;
-    b.OH = (q.h + 2 * pad - k) / stride + 1;
-    b.OW = (q.w + 2 * pad - k) / stride + 1;
-    b.KS = k; b.stride = stride; b.pad = pad; b.act = act;
+    BigParams b = big_params(shape(q), q.x, q.w_packed, q.bias, q.y, nullptr);
     b.no_xcd = UPA_OPT(opts, no_xcd);
     return b;
   };

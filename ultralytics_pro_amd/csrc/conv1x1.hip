@@ -351,16 +351,15 @@ int launch_c1_ntw(const C1Params& p, int mt, int waves, dim3 grid, size_t lds, h
 
 }  // namespace
 
-bool upa_conv1x1_eligible(int n, int h, int w, int cin, int ldx, int cout, int ldy, bool residual, int k, int stride,
-                          int pad, int act, int dtype, const upa_opts* opts) {
+bool upa_conv1x1_eligible(const ConvShape& s, const upa_opts* opts) {
   if (UPA_OPT(opts, no_1x1)) return false;
-  if (dtype != UPA_BF16 || k != 1 || stride != 1 || pad != 0 || residual) return false;
-  if (act != UPA_ACT_SILU && act != UPA_ACT_NONE) return false;
-  if (cin % 8 != 0 || cout % 8 != 0 || ldx % 8 != 0 || ldy % 8 != 0) return false;
-  const long px = (long)n * h * w;
-  if (px * ldx * 2 >= (1L << 31) - 4096 || px * ldy * 2 >= (1L << 31) - 4096) return false;  // 32-bit byte offsets
-  const int ktt = (cin + 31) / 32;
-  const int ntw = cout > 128 ? 8 : (cout + 15) / 16;
+  if (s.dtype != UPA_BF16 || s.k != 1 || s.stride != 1 || s.pad != 0 || s.ldr != 0) return false;
+  if (s.act != UPA_ACT_SILU && s.act != UPA_ACT_NONE) return false;
+  if (s.cin % 8 != 0 || s.cout % 8 != 0 || s.ldx % 8 != 0 || s.ldy % 8 != 0) return false;
+  const long px = (long)s.n * s.h * s.w;
+  if (px * s.ldx * 2 >= (1L << 31) - 4096 || px * s.ldy * 2 >= (1L << 31) - 4096) return false;  // 32-bit byte offsets
+  const int ktt = (s.cin + 31) / 32;
+  const int ntw = s.cout > 128 ? 8 : (s.cout + 15) / 16;
   if ((size_t)ktt * ntw * 1024 + 4 * ring_of(1) * 1024 + 512 > 160 * 1024) return false;  // weight slice + the smallest ring
   return true;
 }
@@ -479,7 +478,7 @@ extern "C" int upa_detect_tail(const void* x, int n, int h, int w, int cin, int 
   // (the flat pixel -> (image, anchor) split of detect_epi.h must be exact up to the last pixel)
   if (dtype != UPA_BF16 || h * w < 2 || w < 2 || (kind == 1 && cout != 64) || (kind == 2 && (cout < nc || cout > 128)) ||
       !upa_magic_exact((long)n * h * w - 1, h * w) || !upa_magic_exact((long)h * w - 1, w) ||
-      !upa_conv1x1_eligible(n, h, w, cin, ldx, cout, raw ? ldraw : cout, false, 1, 1, 0, UPA_ACT_NONE, dtype, opts)) {
+      !upa_conv1x1_eligible({n, h, w, cin, ldx, cout, raw ? ldraw : cout, 0, 1, 1, 0, UPA_ACT_NONE, dtype}, opts)) {
     upa_set_error("detect_tail: shape / dtype outside the fused form (bf16, reg_max 16, nc <= 128)");
     return UPA_EUNSUPPORTED;  // the caller runs the conv and upa_detect_decode separately
   }
@@ -508,7 +507,7 @@ extern "C" int upa_conv1x1_upcat(const void* x, int n, int h, int w, int cin, in
   if (UPA_OPT(opts, no_upcat) || (h & 1) || (w & 1) || up_c <= 0 || up_c % 32 != 0 || up_c >= cin || up_ld % 8 != 0 || ((uintptr_t)up % 16) != 0 ||
       (long)n * (h / 2) * (w / 2) * up_ld * 2 >= (1L << 31) - 4096 || !upa_magic_exact((long)n * h * w - 1, w) ||
       !upa_magic_exact((long)n * h - 1, h) ||
-      !upa_conv1x1_eligible(n, h, w, cin, ldx, cout, ldy, false, 1, 1, 0, act, dtype, opts)) {
+      !upa_conv1x1_eligible({n, h, w, cin, ldx, cout, ldy, 0, 1, 1, 0, act, dtype}, opts)) {
     upa_set_error("conv1x1_upcat: outside the fused form (bf16 streaming 1x1, even h / w, up_c %% 32 == 0)");
     return UPA_EUNSUPPORTED;
   }

@@ -886,18 +886,18 @@ extern "C" int upa_detect_head_tails(const upa_branch_level* box, const upa_bran
 
 bool upa_conv_big_pick_tile(BigParams& p, int bm, int ntb, size_t lds_cap) { return big_pick_tile(p, bm, ntb, lds_cap); }
 
-bool upa_conv_big_eligible(int n, int h, int w, int cin, int ldx, int cout, int ldy, int ldr, int k, int stride, int pad,
-                           int act, int dtype, const upa_opts* opts) {
+bool upa_conv_big_eligible(const ConvShape& s, const upa_opts* opts) {
   // upa_opts.conv_big: 0 = by the size rule below (default), 1 = never, 2 = every shape the kernel can run (parity tests,
   // tools/bench_conv.py)
   const int mode = UPA_OPT(opts, conv_big);
   if (mode == 1) return false;
-  if (dtype != UPA_BF16 || !((k == 1 && stride == 1) || (k == 2 && stride == 1) || (k == 3 && (stride == 1 || stride == 2))) || pad != k / 2) return false;
-  if (cin % 8 != 0 || ldx % 8 != 0 || cout % 8 != 0 || ldy % 8 != 0 || ldr % 8 != 0) return false;
-  if (act != UPA_ACT_SILU && act != UPA_ACT_NONE && act != UPA_ACT_RELU) return false;
+  const int k = s.k, stride = s.stride, cin = s.cin, cout = s.cout;
+  if (s.dtype != UPA_BF16 || !((k == 1 && stride == 1) || (k == 2 && stride == 1) || (k == 3 && (stride == 1 || stride == 2))) || s.pad != k / 2) return false;
+  if (cin % 8 != 0 || s.ldx % 8 != 0 || cout % 8 != 0 || s.ldy % 8 != 0 || s.ldr % 8 != 0) return false;
+  if (s.act != UPA_ACT_SILU && s.act != UPA_ACT_NONE && s.act != UPA_ACT_RELU) return false;
   if (mode == 2) return cout >= 64;
-  const int oh = (h + 2 * pad - k) / stride + 1, ow = (w + 2 * pad - k) / stride + 1;
-  const long px = (long)n * oh * ow;
+  const int oh = (s.h + 2 * s.pad - k) / stride + 1, ow = (s.w + 2 * s.pad - k) / stride + 1;
+  const long px = (long)s.n * oh * ow;
   if (k == 1) {
     // pointwise layers stream faster through conv1x1.hip while their weight slice fits LDS; past that (512+ channels in)
     // the weights have to be shared per tap-chunk anyway
@@ -905,7 +905,7 @@ bool upa_conv_big_eligible(int n, int h, int w, int cin, int ldx, int cout, int 
     // 134400 x 1536 x 256), where the streaming kernel would re-read its input once per 128-column row of workgroups
     if (cout % 128 != 0 || px < 2048) return false;
     if (cout >= 1024 && cin >= 128 && px >= 32 * 1024) return true;
-    return cin >= 512 && !upa_conv1x1_eligible(n, h, w, cin, ldx, cout, ldy, ldr != 0, k, stride, pad, act, dtype, opts);
+    return cin >= 512 && !upa_conv1x1_eligible(s, opts);
   }
   // measured on MI355X (tools/bench_conv.py, yolov3-rtdetr bs 16 / yolov8n bs 32, round 2): 3x3 layers with whole 128-channel
   // output columns run at 800-1000 TFLOP/s here against 430-615 on the per-wave-weights kernel; the 80-channel class

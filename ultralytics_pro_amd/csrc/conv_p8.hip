@@ -281,14 +281,13 @@ bool p8_geometry(BigParams& p) {
 }
 }  // namespace
 
-bool upa_conv_p8_eligible(int n, int h, int w, int cin, int ldx, int cout, int ldy, int ldr, int k, int stride, int pad, int act,
-                          int dtype, const upa_opts* opts) {
+bool upa_conv_p8_eligible(const ConvShape& s, const upa_opts* opts) {
   const int mode = UPA_OPT(opts, conv_p8);  // 0 = by the size rule, 1 = never, 2 = every shape the kernel can run
   if (mode == 1) return false;
-  if (dtype != UPA_BF16 || k != 3 || stride != 1 || pad != 1) return false;
-  if (cin % 64 != 0 || cout % 128 != 0 || ldx % 8 != 0 || ldy % 8 != 0 || ldr % 8 != 0) return false;
-  if (act != UPA_ACT_SILU && act != UPA_ACT_NONE && act != UPA_ACT_RELU) return false;
-  if (h < 4 || w < 4) return false;
+  if (s.dtype != UPA_BF16 || s.k != 3 || s.stride != 1 || s.pad != 1) return false;
+  if (s.cin % 64 != 0 || s.cout % 128 != 0 || s.ldx % 8 != 0 || s.ldy % 8 != 0 || s.ldr % 8 != 0) return false;
+  if (s.act != UPA_ACT_SILU && s.act != UPA_ACT_NONE && s.act != UPA_ACT_RELU) return false;
+  if (s.h < 4 || s.w < 4) return false;
   if (mode == 2) return true;
   // Measured on MI355X (round 4, yolov3-rtdetr bs 16, tools/bench_conv.py --opts conv_p8=2 | 1): one workgroup per CU wins where the
   // whole layer is ONE round of 256-pixel x 128-channel tiles and the K loop is long enough to amortise the un-overlapped prologue and
@@ -298,12 +297,12 @@ bool upa_conv_p8_eligible(int n, int h, int w, int cin, int ldx, int cout, int l
   // @20x20 87.3 -> 98.0) half the chip idles.  One-round layers with K = 2304 win less but still win (yolov3-tiny bs 32 256->512 @20x20,
   // 256 tiles: 45.1 -> 40.6 us; yolov8s 256->128 @40x40, 200 tiles: 40.4 -> 35.9); at K = 1152 (128->128 @40x40: 26.0 -> 24.4, with
   // the shortcut 26.1 -> 26.0) the prologue and epilogue are half the tile and the rule stops.
-  if (cin < 256) return false;
+  if (s.cin < 256) return false;
   BigParams q;
   memset(&q, 0, sizeof(q));
-  q.N = n; q.H = h; q.W = w; q.Cin = cin; q.Cout = cout;
+  q.N = s.n; q.H = s.h; q.W = s.w; q.Cin = s.cin; q.Cout = s.cout;
   if (!p8_geometry(q)) return false;
-  const long tiles = (long)q.tilesX * q.tilesY * n * cdiv(q.NTn, P8_NTB);
+  const long tiles = (long)q.tilesX * q.tilesY * s.n * cdiv(q.NTn, P8_NTB);
   return tiles >= 176 && tiles <= 256;
 }
 

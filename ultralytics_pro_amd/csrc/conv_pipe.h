@@ -1,5 +1,10 @@
 // Internal interface between conv.hip (dispatch) and conv_pipe.hip (software-pipelined 3x3 stride-1 kernel).
 #pragma once
+// One convolution as the dispatch rules (upa_conv_*_eligible) see it: NHWC views with pixel strides ldx / ldy / ldr (elements);
+// ldr != 0 = a residual is added
+struct ConvShape {
+  int n, h, w, cin, ldx, cout, ldy, ldr, k, stride, pad, act, dtype;
+};
 struct PipeParams {
   const char* x;
   char* y;
@@ -15,8 +20,7 @@ struct PipeParams {
   int ablate;  // debug build only (upa_opts.ablate_pipe): 1 no halo DMA, 2 no weight loads, 4 no stores, 8 no MFMA, 16 no epilogue
 #endif
 };
-bool upa_conv_pipe_eligible(int n, int h, int w, int cin, int ldx, int cout, int ldy, int ldr, int k, int stride, int pad,
-                            int act, int dtype, const upa_opts* opts);
+bool upa_conv_pipe_eligible(const ConvShape& s, const upa_opts* opts);
 // variant (if non-null) receives (1 << 21) | NTW of the first launch; query_only = 1 skips the launches
 int upa_conv_pipe_launch(PipeParams p, int query_only, int* variant, void* stream, const upa_opts* opts);
 
@@ -45,8 +49,7 @@ struct C1Params {
   int upKT, up_ld, upH, upW;       // k-tiles taken from `up`, its pixel stride (elements), FULL-resolution H and W
   unsigned upMagicW, upMagicH;
 };
-bool upa_conv1x1_eligible(int n, int h, int w, int cin, int ldx, int cout, int ldy, bool residual, int k, int stride,
-                          int pad, int act, int dtype, const upa_opts* opts);
+bool upa_conv1x1_eligible(const ConvShape& s, const upa_opts* opts);
 // variant (if non-null) receives (1 << 22) | waves << 8 | MT << 4 | NTW; query_only = 1 skips the launch
 int upa_conv1x1_launch(C1Params p, int n_pixels, int query_only, int* variant, void* stream, const upa_opts* opts);
 // p.stats != nullptr (act none, no bias): the convolution + the first stage of the batch statistics; *rows = rows written (one per
@@ -78,8 +81,7 @@ struct BigParams {
   int stats_ld;
   int il_h, il_w, il_c;  // interleaving epilogue (conv_big TAIL 4): dx's height, width, channels
 };
-bool upa_conv_big_eligible(int n, int h, int w, int cin, int ldx, int cout, int ldy, int ldr, int k, int stride, int pad,
-                           int act, int dtype, const upa_opts* opts);
+bool upa_conv_big_eligible(const ConvShape& s, const upa_opts* opts);
 // variant (if non-null) receives (1 << 23) | n-tiles per workgroup << 4 | pixels per workgroup / 128; query_only = 1 skips the launch
 int upa_conv_big_launch(BigParams p, int query_only, int* variant, void* stream, const upa_opts* opts);
 // p.stats != nullptr: the convolution + the first stage of the batch statistics (see BigParams::stats); *rows = rows written
@@ -94,20 +96,12 @@ int upa_conv_big_launch_group(const BigParams* probs, int count, int* consumed, 
 bool upa_conv_big_pick_tile(BigParams& p, int bm, int ntb, size_t lds_cap);
 
 // ---- conv_p8.hip: 8-wave two-group phased kernel for the MFMA-bound 3x3 stride-1 layers (bf16, Cin % 64 == 0, Cout % 128 == 0); BigParams as conv_big
-bool upa_conv_p8_eligible(int n, int h, int w, int cin, int ldx, int cout, int ldy, int ldr, int k, int stride, int pad, int act,
-                          int dtype, const upa_opts* opts);
+bool upa_conv_p8_eligible(const ConvShape& s, const upa_opts* opts);
 // variant (if non-null) receives (1 << 26) | 8 << 4 | 2; query_only = 1 skips the launch
 int upa_conv_p8_launch(BigParams p, int query_only, int* variant, void* stream, const upa_opts* opts);
 
-// ---- conv_mm.hip: 4-wave 32x32x16-MFMA kernel for the MFMA-bound 3x3 stride-1 layers (bf16, Cin % 64 == 0, Cout % 128 == 0); BigParams as conv_big
-bool upa_conv_mm_eligible(int n, int h, int w, int cin, int ldx, int cout, int ldy, int ldr, int k, int stride, int pad, int act,
-                          int dtype, const upa_opts* opts);
-// variant (if non-null) receives (1 << 25) | 8 << 4 | 2; query_only = 1 skips the launch
-int upa_conv_mm_launch(BigParams p, int query_only, int* variant, void* stream, const upa_opts* opts);
-
 // ---- conv_ws3.hip: persistent weights-stationary 3x3 (bf16, stride 1, pad 1, Cin <= 64, Cout = 64); BigParams as conv_big
-bool upa_conv_ws3_eligible(int n, int h, int w, int cin, int ldx, int cout, int ldy, bool residual, int k, int stride, int pad,
-                           int act, int dtype, const upa_opts* opts);
+bool upa_conv_ws3_eligible(const ConvShape& s, const upa_opts* opts);
 // variant (if non-null) receives (1 << 24) | NT << 4 | MT; query_only = 1 skips the launch
 int upa_conv_ws3_launch(BigParams p, int query_only, int* variant, void* stream, const upa_opts* opts);
 int upa_conv_ws3_launch_stats(BigParams p, int* rows, long max_rows, void* stream, const upa_opts* opts);  // as upa_conv_big_launch_stats

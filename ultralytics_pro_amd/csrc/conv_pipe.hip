@@ -564,12 +564,12 @@ static int launch_pipe(const PipeParams& p, int grid, hipStream_t s) {
   return UPA_OK;
 }
 
-bool upa_conv_pipe_eligible(int n, int h, int w, int cin, int ldx, int cout, int ldy, int ldr, int k, int stride, int pad,
-                            int act, int dtype, const upa_opts* opts) {
+bool upa_conv_pipe_eligible(const ConvShape& s, const upa_opts* opts) {
   if (UPA_OPT(opts, no_pipe)) return false;
-  if (dtype != UPA_BF16 || k != 3 || stride != 1 || pad != 1) return false;
-  if (act != UPA_ACT_SILU && act != UPA_ACT_NONE) return false;
-  if (h % TH != 0 || w % TW != 0 || cin % 8 != 0 || cout % 16 != 0) return false;
+  if (s.dtype != UPA_BF16 || s.k != 3 || s.stride != 1 || s.pad != 1) return false;
+  if (s.act != UPA_ACT_SILU && s.act != UPA_ACT_NONE) return false;
+  const int cin = s.cin, cout = s.cout;
+  if (s.h % TH != 0 || s.w % TW != 0 || cin % 8 != 0 || cout % 16 != 0) return false;
   if (cin > 128) return false;
   // measured on MI355X (bs 32): the pipelined kernel wins for 32 / 64 output channels per launch (14.2 vs 15.4 us,
   // 28.9 vs 29.4) and for 80->80 (59.1 vs 64.8); 16-channel launches (16->16, the +16 tail of 64->80) re-read the
@@ -579,8 +579,8 @@ bool upa_conv_pipe_eligible(int n, int h, int w, int cin, int ldx, int cout, int
   const bool no_c16 = UPA_OPT(opts, no_c16) != 0;
   const bool c16_shape = cin == 16 && cout == 16 && !no_c16;  // conv3x3_c16_kernel
   if (!all_shapes && !c16_shape && (ntn & 1) && !(ntn >= 5 && cin >= 80)) return false;
-  const long px = (long)n * h * w;
-  if (px * ldx * 2 >= (1L << 31) || px * ldy * 2 >= (1L << 31) || px * ldr * 2 >= (1L << 31)) return false;
+  const long px = (long)s.n * s.h * s.w;
+  if (px * s.ldx * 2 >= (1L << 31) || px * s.ldy * 2 >= (1L << 31) || px * s.ldr * 2 >= (1L << 31)) return false;
   // enough wave tiles to fill the chip; low-resolution layers stay on the tile-per-workgroup kernel
   const int min_tiles = UPA_OPT(opts, pipe_min_tiles) > 0 ? UPA_OPT(opts, pipe_min_tiles) : 1024;
   if (px / (TH * TW) < min_tiles) return false;

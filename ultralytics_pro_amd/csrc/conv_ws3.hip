@@ -269,17 +269,15 @@ int ws3_num_cu() {
 }  // namespace
 
 // Dispatch rule (upa_opts.conv_ws3: 0 = by size, 1 = never, 2 = every shape the kernel can run).
-bool upa_conv_ws3_eligible(int n, int h, int w, int cin, int ldx, int cout, int ldy, bool residual, int k, int stride, int pad,
-                           int act, int dtype, const upa_opts* opts) {
+bool upa_conv_ws3_eligible(const ConvShape& s, const upa_opts* opts) {
   const int mode = UPA_OPT(opts, conv_ws3);
   if (mode == 1) return false;
-  if (dtype != UPA_BF16 || k != 3 || stride != 1 || pad != 1) return false;
-  if (cin > 64 || cin % 8 != 0 || ldx % 8 != 0 || ldy % 8 != 0 || cout != 64) return false;
-  if (act != UPA_ACT_SILU && act != UPA_ACT_NONE && act != UPA_ACT_RELU) return false;
+  if (s.dtype != UPA_BF16 || s.k != 3 || s.stride != 1 || s.pad != 1) return false;
+  if (s.cin > 64 || s.cin % 8 != 0 || s.ldx % 8 != 0 || s.ldy % 8 != 0 || s.cout != 64) return false;
+  if (s.act != UPA_ACT_SILU && s.act != UPA_ACT_NONE && s.act != UPA_ACT_RELU) return false;
   if (mode == 2) return true;
-  if (mode == 3) return cin == 64 && (long)n * h * w >= 8192 && (long)n * h * w < 100000;  // one tile per workgroup at most: no resident walk
   // measured against conv_big at batch 32 (tools/bench_conv.py): 64 -> 64 @80x80 23.6 vs 27.0 us, @40x40 11.0 vs 12.0, @20x20 8.4 vs 9.0
-  return cin == 64 && (long)n * h * w >= 8192;
+  return s.cin == 64 && (long)s.n * s.h * s.w >= 8192;
 }
 
 static int ws3_launch(BigParams p, int query_only, int* variant, int* rows, void* stream);

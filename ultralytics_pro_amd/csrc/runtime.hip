@@ -20,7 +20,7 @@ __global__ void upa_zero_words_kernel(unsigned* p, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) p[i] = 0u;
 }
-extern "C" int upa_version(void) { return 2; }  // 2: upa_opts argument on the dispatching entry points (round 3)
+extern "C" int upa_version(void) { return 3; }  // 2: upa_opts argument on the dispatching entry points; 3: conv_force / conv_mm left upa_opts
 extern "C" size_t upa_opts_size(void) { return sizeof(upa_opts); }
 
 // Device -> pinned host copy as a KERNEL (the device writes the host-mapped allocation through its unified address): a step
