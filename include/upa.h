@@ -352,6 +352,19 @@ int upa_nms_batched(const float* pred, int b, int nc, int a, float conf_thres, f
 int upa_mhsa(const void* q, const void* k, const void* v, int ldqkv, int n, int hw, int heads, int d, float scale,
              const void* residual, int ldr, void* y, int ldy, int dtype, void* stream);
 
+/* ---- YOLO11 (C2PSA, non-legacy Detect) -----------------------------------------------------------------------------
+ * Depthwise k x k conv (DWConv, groups = C; nn/modules/conv.py:411-425): y = act(dwconv(x) + bias) on NHWC views (any C, channel
+ * slices allowed; the output must not overlap the input).  weight: (k*k, C) f32 tap-major (BN folded by the caller), bias (C) f32.
+ * Supported: k 3, pad 1, stride 1 | 2, act NONE | SILU, f32 | bf16 (f32 accumulate); anything else -> UPA_EUNSUPPORTED. */
+int upa_dwconv2d(const void* x, int n, int h, int w, int c, int ldx, const float* weight, const float* bias, void* y, int ldy, int k,
+                 int stride, int pad, int act, int dtype, void* stream);
+/* v10_Attention core (block.py:1701-1722): qkv = the qkv conv's NHWC output, heads * (2 key_dim + head_dim) channels in the per-head
+ * order [q | k | v]; y[:, head*head_dim + j] = softmax(scale * q^T k) applied to v  +  pe(v), pe = depthwise 3x3 on v (channel
+ * head*head_dim + j; pe_weight (9, heads*head_dim) f32 tap-major, BN folded, no act).  Any H*W (keys are streamed); key_dim 32 /
+ * head_dim 64 (every YOLO11 scale), otherwise UPA_EUNSUPPORTED.  y must not overlap qkv. */
+int upa_psa_attention(const void* qkv, int ldqkv, int n, int h, int w, int heads, int key_dim, int head_dim, float scale,
+                      const float* pe_weight, const float* pe_bias, void* y, int ldy, int dtype, void* stream);
+
 /* ---- RT-DETR decoder head pieces (f32 token rows) -------------------------------------------------------------------
  * nn.Linear: y[m,n] = act(x[m,k] . W[n,k]^T + bias[n]) (+ residual); W packed by upa_pack_conv_weight(k=1, UPA_F32).
  *                                                                     transformer.py:348-399, head.py:1993-2003 */

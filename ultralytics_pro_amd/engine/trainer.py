@@ -471,6 +471,11 @@ class DetectionTrainer:
 
     def __init__(self, model, dtype=torch.bfloat16, hyp=None, device=None, world_size=1, ema=True, wgrad_streams: int = 1,
                  amp_scaler: bool = False):
+        # YOLO11 blocks subclass / reuse C2f and Detect but have no backward here: the graph below would take a C3k2 for a C2f
+        # and the DWConv class branch for the legacy one
+        for m in model.modules():
+            if isinstance(m, (B.C3k2, B.C2PSA)) or (isinstance(m, H.Detect) and not m.legacy_cls):
+                raise L.UpaError(f"{type(m).__name__} (YOLO11) has no training path on HIP yet")
         self.model = model
         self.hyp = dict(HYP, **(hyp or {}))
         self.device = torch.device(device or "cuda:0")

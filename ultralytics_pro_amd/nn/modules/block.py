@@ -13,7 +13,8 @@ from ... import _lib as L
 from ...engine import runtime as R
 from .conv import Conv, PackedConv, _HipConvMixin, fold_bn, hip_conv2d, version_key
 
-__all__ = ("DFL", "SPPF", "C2f", "C3", "Bottleneck", "MHSA", "BottleneckTransformer", "BoT3")
+__all__ = ("DFL", "SPPF", "C2f", "C3", "Bottleneck", "MHSA", "BottleneckTransformer", "BoT3", "C3k", "C3k2", "v10_Attention", "PSABlock",
+           "C2PSA")
 
 
 class DFL(nn.Module):
@@ -437,3 +438,116 @@ class BoT3(nn.Module):
         for i, m in enumerate(self.m):
             y = m(y, out=cat[:, :c_] if i == len(self.m) - 1 else None)
         return self.cv3(cat, out=out)
+
+
+# ---- YOLO11 ----------------------------------------------------------------------------------------------------------------------------
+
+
+class C3k(C3):
+    """C3 whose Bottlenecks have k x k convolutions (block.py:1510-1530): YOLO11's C3k2(c3k=True) inner block."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5, k=3):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*(Bottleneck(c_, c_, shortcut, g, k=(k, k), e=1.0) for _ in range(n)))
+
+
+class C3k2(C2f):
+    """C2f whose inner blocks are Bottleneck(c, c, e=0.5) or C3k(c, c, 2) (block.py:1485-1507).
+
+    The C2f whole-block kernels (`_fused`, `forward_down`, `_pair_cv2`) hard-code Bottleneck(c, c, e=1.0): a C3k2 with the same outer
+    shapes (yolov11n layers 6, 13, 16, 19) would pass their predicates and compute another function, so they are off here - cv1, the
+    inner blocks (each with its own kernels: conv pair, stacked C3 1x1s) and cv2 run as separate launches into the concat buffer."""
+
+    fuse_block = False
+    fuse_pair_cv2 = False
+
+    def __init__(self, c1, c2, n=1, c3k=False, e=0.5, g=1, shortcut=True):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = nn.ModuleList(C3k(self.c, self.c, 2, shortcut, g) if c3k else Bottleneck(self.c, self.c, shortcut, g) for _ in range(n))
+
+    def _fused(self, x, out, up=None):
+        return None
+
+    def forward_down(self, x, down, out=None):
+        return None
+
+    def _pair_cv2(self, cat, out):
+        return None
+
+
+class v10_Attention(nn.Module):  # noqa: N801 (the reference's class name: state_dict / YAML contract)
+    """Multi-head self-attention over all H*W pixels (block.py:1668-1722): qkv 1x1 conv, per head softmax(scale q^T k) v with
+    [q (key_dim) | k (key_dim) | v (head_dim)] channel slices, + pe (depthwise 3x3 of v), proj 1x1 conv.  The attention and pe are ONE
+    launch (`upa_psa_attention`, csrc/psa.hip); qkv and proj are HIP convs, proj takes the caller's residual in its epilogue."""
+
+    def __init__(self, dim, num_heads=8, attn_ratio=0.5):
+        super().__init__()
+        self.num_heads = num_heads
+        self.head_dim = dim // num_heads
+        self.key_dim = int(self.head_dim * attn_ratio)
+        self.scale = self.key_dim ** -0.5
+        nh_kd = self.key_dim * num_heads
+        h = dim + nh_kd * 2
+        self.qkv = Conv(dim, h, 1, act=False)
+        self.proj = Conv(dim, dim, 1, act=False)
+        self.pe = Conv(dim, dim, 3, 1, g=dim, act=False)
+
+    def forward(self, x, out=None, residual=None):
+        """proj(attn(x) + pe(v)) (+ residual); `out` must not overlap x (the attention reads x's qkv while proj writes)."""
+        x = R.to_nhwc(x, x.dtype)
+        n, c, h, w = x.shape
+        if self.head_dim * self.num_heads != c:
+            raise L.UpaError(f"v10_Attention: {self.num_heads} heads x {self.head_dim} != {c} channels")
+        if not isinstance(self.pe.act, nn.Identity):
+            raise L.UpaError(f"v10_Attention: pe must have no activation (the fused epilogue adds pe linearly), got {self.pe.act}")
+        qkv = self.qkv(x)
+        t = R.alloc_nhwc(n, c, h, w, x.dtype, x.device, key=(id(self), "t"))
+        pw, pb = self.pe._dw_packed(self.pe.conv, getattr(self.pe, "bn", None), x.device)
+        vq, vt = R.view_of(qkv), R.view_of(t)
+        L.check(L.lib().upa_psa_attention(vq.ptr, vq.ld, n, h, w, self.num_heads, self.key_dim, self.head_dim, float(self.scale),
+                                          pw.data_ptr(), pb.data_ptr(), vt.ptr, vt.ld, vq.dtype, L.current_stream(x.device)),
+                "psa_attention")
+        return self.proj(t, out=out, residual=residual)
+
+
+class PSABlock(nn.Module):
+    """x + attn(x), then + ffn(x) (block.py:1724-1766); both residual adds run in the epilogue of the branch's last 1x1 conv."""
+
+    def __init__(self, c, attn_ratio=0.5, num_heads=4, shortcut=True):
+        super().__init__()
+        self.attn = v10_Attention(c, attn_ratio=attn_ratio, num_heads=num_heads)
+        self.ffn = nn.Sequential(Conv(c, c * 2, 1), Conv(c * 2, c, 1, act=False))
+        self.add = shortcut
+
+    def forward(self, x, out=None):
+        """`out` may be x itself: x is last read by attn's proj (residual), before the ffn writes `out`."""
+        x = R.to_nhwc(x, x.dtype)
+        n, c, h, w = x.shape
+        u = R.alloc_nhwc(n, c, h, w, x.dtype, x.device, key=(id(self), "u"))
+        self.attn(x, out=u, residual=x if self.add else None)
+        return self.ffn[1](self.ffn[0](u), out=out, residual=u if self.add else None)
+
+
+class C2PSA(nn.Module):
+    """cv1 -> [a | b], b through n PSABlocks, cv2(cat(a, b)) (block.py:1829-1881).  One 2c-channel buffer: cv1 writes it whole, the
+    last PSABlock writes its result back into the b half (b is no longer read by then) and cv2 reads the buffer - no concat copy."""
+
+    def __init__(self, c1, c2, n=1, e=0.5):
+        super().__init__()
+        assert c1 == c2
+        self.c = int(c1 * e)
+        self.cv1 = Conv(c1, 2 * self.c, 1, 1)
+        self.cv2 = Conv(2 * self.c, c1, 1)
+        self.m = nn.Sequential(*(PSABlock(self.c, attn_ratio=0.5, num_heads=self.c // 64) for _ in range(n)))
+
+    def forward(self, x, out=None):
+        x = R.to_nhwc(x, x.dtype)
+        n, _, h, w = x.shape
+        c = self.c
+        buf = R.alloc_nhwc(n, 2 * c, h, w, x.dtype, x.device, key=(id(self), "cat"))
+        self.cv1(x, out=buf)
+        b = buf[:, c:]
+        for i, m in enumerate(self.m):
+            b = m(b, out=buf[:, c:] if i == len(self.m) - 1 else None)
+        return self.cv2(buf, out=out)

@@ -9,6 +9,7 @@ folds BN (utils/torch_utils.py:236-266), packs the weights once per dtype into M
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 import torch.nn as nn
@@ -16,7 +17,7 @@ import torch.nn as nn
 from ... import _lib as L
 from ...engine import runtime as R
 
-__all__ = ("autopad", "Conv", "Concat", "hip_conv2d", "PackedConv", "version_key", "bump_weights_generation")
+__all__ = ("autopad", "Conv", "DWConv", "Concat", "hip_conv2d", "hip_dwconv2d", "PackedConv", "version_key", "bump_weights_generation")
 
 
 def autopad(k, p=None, d=1):
@@ -142,6 +143,21 @@ def hip_conv2d(x: torch.Tensor, pk: PackedConv, stride: int, pad: int, act: int,
     return y
 
 
+def hip_dwconv2d(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, k: int, stride: int, pad: int, act: int,
+                 out: torch.Tensor | None = None, key=None) -> torch.Tensor:
+    """y = act(depthwise conv(x) + b) on the HIP path (`upa_dwconv2d`). x: NHWC view; w: (k*k, C) f32 tap-major, b: (C,) f32 (device)."""
+    L.require_gpu(x, "dwconv2d")
+    vx = R.view_of(x)
+    oh, ow = (vx.h + 2 * pad - k) // stride + 1, (vx.w + 2 * pad - k) // stride + 1
+    y = out if out is not None else R.alloc_nhwc(vx.n, vx.c, oh, ow, x.dtype, x.device, key)
+    vy = R.view_of(y)
+    if vy.dtype != vx.dtype or (vy.n, vy.h, vy.w, vy.c) != (vx.n, oh, ow, vx.c):
+        raise L.UpaError(f"dwconv2d: bad output view {tuple(y.shape)} for input {tuple(x.shape)}")
+    L.check(L.lib().upa_dwconv2d(vx.ptr, vx.n, vx.h, vx.w, vx.c, vx.ld, w.data_ptr(), b.data_ptr(), vy.ptr, vy.ld, k, stride, pad, act,
+                                 vx.dtype, L.current_stream(x.device)), "dwconv2d")
+    return y
+
+
 _WEIGHTS_GEN = [0]
 
 
@@ -213,6 +229,26 @@ class _HipConvMixin:
         cache[key] = (ver, pk)
         return pk
 
+    def _dw_packed(self, conv: nn.Conv2d, bn, device):
+        """BN-folded depthwise filters as ((k*k, C) f32 tap-major, (C,) f32) on `device` for `upa_dwconv2d` / `upa_psa_attention` (the
+        same f32 weights in both modes: the kernels are bound by activation bytes, not by the 9 MACs per element)."""
+        cache = self.__dict__.setdefault("_pk_cache", {})
+        key = (id(conv), str(device), "dw")
+        ver = version_key(conv.weight, conv.bias, *(() if bn is None else (bn.weight, bn.bias, bn.running_mean,
+                                                                           bn.running_var))) + ((bn.eps,) if bn is not None else ())
+        hit = cache.get(key)
+        if hit is not None and hit[0] == ver:
+            return hit[1]
+        c, k = conv.out_channels, conv.kernel_size[0]
+        if not (conv.groups == conv.in_channels == c and conv.kernel_size[0] == conv.kernel_size[1] and conv.dilation == (1, 1)
+                and conv.stride[0] == conv.stride[1] and conv.padding[0] == conv.padding[1]):
+            raise L.UpaError(f"HIP depthwise conv needs groups = in = out channels, square kernel, dilation 1, got {conv}")
+        w, b = fold_bn(conv, bn)  # (C, 1, k, k): fold_bn scales per output channel = per channel here
+        wt = w.reshape(c, k * k).t().contiguous().to(device)
+        pk = (wt, b.contiguous().to(device))
+        cache[key] = (ver, pk)
+        return pk
+
     def invalidate_packed(self):
         self.__dict__.pop("_pk_cache", None)
 
@@ -249,6 +285,8 @@ class Conv(nn.Module, _HipConvMixin):
         """act(bn(conv(x))) with BN folded into the HIP conv epilogue (conv.py:177-197 compute the same function)."""
         if self.training:
             raise L.UpaError("training-mode Conv (batch-statistics BN) is not on the HIP path yet (SURVEY §8f rank 2)")
+        if self.conv.groups != 1:
+            return self._forward_dw(x, out=out, residual=residual, up=up)
         stem = _is_model_input(x, self.conv.in_channels)
         # raw uint8 frames with no compute dtype chosen: float32 activations (the reference's `im.float()`, predictor.py:169)
         dt = (self.compute_dtype or (torch.float32 if x.dtype == torch.uint8 else x.dtype)) if stem else x.dtype
@@ -258,6 +296,19 @@ class Conv(nn.Module, _HipConvMixin):
             up = None
         return hip_conv2d(x, pk, self.conv.stride[0], self.conv.padding[0], self._act_code(), out=out, residual=residual,
                           out_dtype=dt, key=(id(self), "y"), up=up)
+
+    def _forward_dw(self, x, out=None, residual=None, up=None):
+        """Depthwise form (groups = in = out channels: DWConv, v10_Attention.pe): `upa_dwconv2d`.  Other grouped convs raise."""
+        cv = self.conv
+        if not (cv.groups == cv.in_channels == cv.out_channels):
+            raise L.UpaError(f"HIP conv supports groups = 1 or depthwise (groups = in = out channels), got {cv}")
+        if residual is not None:
+            raise L.UpaError("depthwise conv has no residual epilogue")
+        if up is not None:
+            up.materialize()
+        x = R.to_nhwc(x, x.dtype if x.dtype in (torch.float32, torch.bfloat16) else torch.float32)
+        w, b = self._dw_packed(cv, getattr(self, "bn", None), x.device)
+        return hip_dwconv2d(x, w, b, cv.kernel_size[0], cv.stride[0], cv.padding[0], self._act_code(), out=out, key=(id(self), "y"))
 
     forward_fuse = forward  # BN is always folded on the HIP path (tasks.py:1134 rebinding is a no-op here)
 
@@ -314,6 +365,13 @@ class Conv(nn.Module, _HipConvMixin):
     def _load_from_state_dict(self, *a, **k):
         self.invalidate_packed()
         return super()._load_from_state_dict(*a, **k)
+
+
+class DWConv(Conv):
+    """Depth-wise convolution (conv.py:411-425): Conv with groups = gcd(c1, c2), run by `upa_dwconv2d` when that is c1 = c2."""
+
+    def __init__(self, c1, c2, k=1, s=1, d=1, act=True):
+        super().__init__(c1, c2, k, s, g=math.gcd(c1, c2), d=d, act=act)
 
 
 class Concat(nn.Module):

@@ -10,7 +10,7 @@ import torch.nn as nn
 from ... import _lib as L
 from ...engine import runtime as R
 from .block import DFL
-from .conv import Conv, _HipConvMixin, hip_conv2d, version_key
+from .conv import Conv, DWConv, _HipConvMixin, hip_conv2d, version_key
 
 __all__ = ("Detect",)
 
@@ -54,9 +54,17 @@ class Detect(nn.Module, _HipConvMixin):
         c2, c3 = max((16, ch[0] // 4, self.reg_max * 4)), max(ch[0], min(self.nc, 100))
         self.cv2 = nn.ModuleList(
             nn.Sequential(Conv(x, c2, 3), Conv(c2, c2, 3), nn.Conv2d(c2, 4 * self.reg_max, 1)) for x in ch)
-        if not self.legacy:
-            raise L.UpaError("Detect(legacy=False) (DWConv class branch, v11+) is outside the hot-path scope (SURVEY §2)")
-        self.cv3 = nn.ModuleList(nn.Sequential(Conv(x, c3, 3), Conv(c3, c3, 3), nn.Conv2d(c3, self.nc, 1)) for x in ch)
+        # legacy v3/v5/v8 class branch: Conv3x3 -> Conv3x3 -> 1x1; v11+ (legacy = False, head.py:101-110): DW3x3 -> 1x1 -> DW3x3 -> 1x1 -> 1x1.
+        # Recorded per instance (parse_model sets the CLASS attribute for the model being built).  The fused class-branch forms below
+        # (branch tail, level stream, grouped levels) assume the legacy branch: the DWConv branch runs its convs and `upa_detect_tail`.
+        self.legacy_cls = bool(self.legacy)
+        if self.legacy_cls:
+            self.cv3 = nn.ModuleList(nn.Sequential(Conv(x, c3, 3), Conv(c3, c3, 3), nn.Conv2d(c3, self.nc, 1)) for x in ch)
+        else:
+            self.cv3 = nn.ModuleList(
+                nn.Sequential(nn.Sequential(DWConv(x, x, 3), Conv(x, c3, 1)), nn.Sequential(DWConv(c3, c3, 3), Conv(c3, c3, 1)),
+                              nn.Conv2d(c3, self.nc, 1))
+                for x in ch)
         self.dfl = DFL(self.reg_max) if self.reg_max > 1 else nn.Identity()
 
     # ---- decode fused into the last 1x1 conv of each branch (bf16 perf mode) ----------------------------------------------
@@ -116,6 +124,8 @@ class Detect(nn.Module, _HipConvMixin):
 
     def _branch_tail_args(self, t: torch.Tensor, mid, conv: nn.Conv2d, kind: int):
         """(view of t, packed 3x3, packed 1x1 tail, its bias) for `upa_detect_branch_tail`, or None outside the fused form."""
+        if kind == 2 and not self.legacy_cls:
+            return None
         c = mid.conv.in_channels
         cp = 64 if kind == 1 else (80 if c == 80 else 96)  # padded channel count of the fused form (upa_detect_branch_tail)
         if not (isinstance(mid, Conv) and isinstance(mid.act, nn.SiLU) and mid.conv.kernel_size == (3, 3) and mid.conv.stride == (1, 1)
@@ -171,7 +181,8 @@ class Detect(nn.Module, _HipConvMixin):
     def _level_stream(self, i: int, x: torch.Tensor, plan) -> bool:
         """Level i through `upa_detect_level_stream`; False (nothing launched) outside its form."""
         o_ = R.current_opts()
-        if not self.level_stream or o_ is None or o_.detect_stream != 2 or x.dtype != torch.bfloat16 or self.reg_max != 16:
+        if not self.level_stream or o_ is None or o_.detect_stream != 2 or x.dtype != torch.bfloat16 or self.reg_max != 16 \
+                or not self.legacy_cls:
             return False
         b, c = self.cv2[i], self.cv3[i]
         ok3 = lambda m, ci, co: (isinstance(m, Conv) and not m.training and isinstance(m.act, nn.SiLU) and hasattr(m, "bn")  # noqa: E731
@@ -217,6 +228,8 @@ class Detect(nn.Module, _HipConvMixin):
         """Both branches of the levels `idx` (inputs `xs`, NHWC) through the group entry points; False (nothing launched) when a
         level is outside the fused forms."""
         import ctypes as C
+        if not self.legacy_cls:
+            return False
         lib = L.lib()
         dev = xs[0].device
         stream = L.current_stream(dev)

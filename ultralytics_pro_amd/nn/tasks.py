@@ -19,7 +19,7 @@ import yaml
 
 from .. import _lib as L
 from ..engine import runtime as R
-from .modules import (C2f, C3, SPPF, BoT3, Bottleneck, Concat, Conv, Detect)
+from .modules import (C2f, C2PSA, C3, C3k2, SPPF, BoT3, Bottleneck, Concat, Conv, Detect)
 from .modules.conv import VirtualUpsample
 from .modules.resample import MaxPool2d, Upsample, ZeroPad2d
 
@@ -29,7 +29,7 @@ _NN_STANDINS = {"Upsample": Upsample, "MaxPool2d": MaxPool2d, "ZeroPad2d": ZeroP
 
 
 def _registry():
-    reg = {m.__name__: m for m in (Conv, C2f, C3, SPPF, BoT3, Bottleneck, Concat, Detect)}
+    reg = {m.__name__: m for m in (Conv, C2f, C3, SPPF, BoT3, Bottleneck, Concat, Detect, C3k2, C2PSA)}
     try:
         from .modules.rtdetr import RTDETRDecoder
         reg["RTDETRDecoder"] = RTDETRDecoder
@@ -38,8 +38,8 @@ def _registry():
     return reg
 
 
-BASE_MODULES = {"Conv", "C2f", "C3", "SPPF", "BoT3", "Bottleneck"}  # subset of base_modules, tasks.py:2446-2710
-REPEAT_MODULES = {"C2f", "C3"}  # subset of repeat_modules (BoT3 is not one: SURVEY §8a row 15)
+BASE_MODULES = {"Conv", "C2f", "C3", "SPPF", "BoT3", "Bottleneck", "C3k2", "C2PSA"}  # subset of base_modules, tasks.py:2446-2710
+REPEAT_MODULES = {"C2f", "C3", "C3k2", "C2PSA"}  # subset of repeat_modules (BoT3 is not one: SURVEY §8a row 15)
 
 
 def make_divisible(x, divisor):
@@ -101,6 +101,10 @@ def parse_model(d, ch, verbose=False):
             if mname in REPEAT_MODULES:
                 args.insert(2, n)
                 n = 1
+            if mname == "C3k2":  # YOLO11: the DWConv Detect class branch, C3k inner blocks for M/L/X (tasks.py:2859-2863)
+                legacy = False
+                if scale in "mlx":
+                    args[3] = True
         elif mname == "Concat":
             c2 = sum(ch[x] for x in f)
         elif mname == "Detect":
@@ -146,7 +150,7 @@ def _out_channels(m, ch):
     last = m[-1] if isinstance(m, HipSequential) else m
     if isinstance(last, Conv):
         return last.conv.out_channels
-    if isinstance(last, (C2f, SPPF)):
+    if isinstance(last, (C2f, SPPF, C2PSA)):
         return last.cv2.conv.out_channels
     if isinstance(last, (C3, BoT3)):
         return last.cv3.conv.out_channels
