@@ -566,6 +566,53 @@ int upa_detection_loss_scaled(const float* const* feats, float* const* grads, co
                               int max_gt, float gain_box, float gain_cls, float gain_dfl, float grad_scale,
                               const float* grad_scale_dev, float* loss_items, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- instance segmentation (Segment head, Proto, masks) --------------------------------------------------------------------
+ * nn.ConvTranspose2d(c_, c_, 2, 2, 0, bias = True), Proto's upsample (nn/modules/block.py:257-276): y[n, 2y+i, 2x+j, co] =
+ * b[co] + sum_ci x[n, y, x, ci] W[ci, co, i, j], one GEMM (pixels x cin) . (cin x 4 cout) with a pixel-shuffle store.  bf16 on the
+ * bf16 MFMAs, f32 on exact-f32 MFMA; f32 accumulation.  x: NHWC (n, h, w, cin) view, y: NHWC (n, 2h, 2w, cout) view; w_packed from
+ * upa_pack_conv_transpose2x2_weight (W as the (cin, cout, 2, 2) f32 torch weight).  cin, cout, ldx, ldy: multiples of 16 bytes. */
+size_t upa_conv_transpose2x2_packed_weight_bytes(int cin, int cout, int dtype);
+int upa_pack_conv_transpose2x2_weight(const float* w, int cin, int cout, int dtype, void* out);
+int upa_conv_transpose2x2(const void* x, int n, int h, int w, int cin, int ldx, const void* w_packed, const float* bias, void* y,
+                          int cout, int ldy, int dtype, void* stream);
+/* Segment's mask coefficients (nn/modules/head.py:827): out[b, c0 + ch, a0 + y * w + x] = x[b, y, x, ch] as f32, out = (n, c_total,
+ * a_total) f32 - the `.view(bs, nm, -1)` + `torch.cat(.., 2)` of one level (or its rows of a concatenated (4+nc+nm, A) output). */
+int upa_mask_coef_rows(const void* x, int n, int h, int w, int c, int ldx, int dtype, float* out, int c_total, int c0, int a_total,
+                       int a0, void* stream);
+/* The extra columns of NMS's kept rows (utils/nms.py:74-122 carries columns 4+nc.. through as `mask`): for j < counts[b],
+ * out[b, j, off + k] = extra[b, k, keep[b, j]] (extra = (b, ne, a) f32, keep / counts from upa_nms_batched*), off = 6 when `det`
+ * ((b, max_det, 6) NMS rows) is given - its row is then copied to columns 0..5 - else 0.  Rows j >= counts[b] are zero.  Counts are
+ * read on the device (graph-capturable).  out: (b, max_det) rows of ldo floats. */
+int upa_nms_gather_extra(const float* extra, int b, int ne, int a, const int32_t* keep, const int32_t* counts, int max_det,
+                         const float* det, float* out, int ldo, void* stream);
+/* Binary instance masks (utils/ops.py:489-583): mask = coef . protos (nm-deep dot, k ascending) at proto resolution, then
+ *   mode 0 (process_mask): crop_mask with boxes x (crop_sx, crop_sy) at proto resolution, bilinear to (out_h, out_w);
+ *            upsample = False is out = (mh, mw);
+ *   mode 1 (process_mask_native): bilinear of the proto window [top:bottom, left:right] (scale_masks) to (out_h, out_w), then
+ *            crop_mask with the boxes in output coordinates;
+ * then > 0.  crop_mask's float-comparison form (the GPU branch, ops.py:510-513); bilinear = torch's upsample_bilinear2d with
+ * align_corners = False.  protos: NHWC (b, mh, mw, nm) view (pixel stride ldp); coef: (b, max_det) rows of coef_ld floats; det:
+ * (b, max_det) rows of det_ld floats, xyxy box in the first 4; counts (b,) int32 on the device.
+ * Ragged output: the mask of (image i, detection j) is row base[i] + j of `masks` (out_h * out_w bytes each), base = exclusive prefix
+ * sum of counts (computed on the device); rows >= capacity are not written; nonempty[row] (int32) = 1 iff the mask has a pixel set
+ * (the predictor's keep filter, models/yolo/segment/predict.py:106-109); *total = sum(counts), so the caller can detect overflow.
+ * Limits: nm <= 128, b <= 1024; UPA_EUNSUPPORTED outside them. */
+int upa_process_mask(const void* protos, int b, int mh, int mw, int nm, int ldp, int dtype, const float* coef, int coef_ld,
+                     const float* det, int det_ld, int max_det, const int32_t* counts, int out_h, int out_w, int mode,
+                     float crop_sx, float crop_sy, int top, int left, int bottom, int right, unsigned char* masks,
+                     int32_t* nonempty, int capacity, int32_t* total, void* stream);
+
+/* crop_mask's comparison form (utils/ops.py:489-513, the branch a GPU takes): out[k, y, x] = masks[k, y, x] * (x >= x1 & x < x2 &
+ * y >= y1 & y < y2) for the xyxy box in the first 4 of row k of `boxes` (row stride box_ld floats).  masks / out: (n, h, w) f32. */
+int upa_crop_mask(const float* masks, int n, int h, int w, const float* boxes, int box_ld, float* out, void* stream);
+/* scale_masks' resample (utils/ops.py:562-583): y = F.interpolate(x[..., top:bottom, left:right], (out_h, out_w), "bilinear") with
+ * align_corners = False, per plane.  x: (planes, h, w) f32, y: (planes, out_h, out_w) f32. */
+int upa_resize_bilinear(const float* x, int planes, int h, int w, int top, int left, int bottom, int right, float* y, int out_h,
+                        int out_w, void* stream);
+/* dst[r, 0:cols] = src[r, 0:cols] for r < rows (f32 rows of strides lds / ldd: Segment's concatenated output when its rows are not
+ * 16-byte multiples, where upa_copy_view does not apply). */
+int upa_copy_rows(const float* src, long rows, int cols, long lds, float* dst, long ldd, void* stream);
+
 /* ---- HIP graph helpers (capture a launch sequence once, replay per batch) -------------------------------------
  * upa_graph_begin / _end bracket a stream capture of upa_* launches; upa_graph_launch replays the instantiated graph.
  * Two rules for graphs that run concurrently with other graphs (several steps in flight on separate streams), both found

@@ -203,6 +203,16 @@ PROTOTYPES = {
     "upa_detection_loss_scaled": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _f, _f, _f, _f, _vp, _vp, _vp, _sz, _vp]),
     "upa_sgd_nesterov_ema_scaled": (_i, [_vp, _vp, _vp, _vp, C.c_long, _vp, _f, _f, _f, _f, _i, _f, _vp, _i, _vp, _vp]),
     "upa_grad_scaler_update": (_i, [_vp, _vp, _f, _f, _i, _vp]),
+    "upa_conv_transpose2x2_packed_weight_bytes": (_sz, [_i, _i, _i]),
+    "upa_pack_conv_transpose2x2_weight": (_i, [_vp, _i, _i, _i, _vp]),
+    "upa_conv_transpose2x2": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "upa_mask_coef_rows": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    "upa_nms_gather_extra": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "upa_process_mask": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _f, _f, _i, _i, _i, _i, _vp, _vp, _i,
+                              _vp, _vp]),
+    "upa_crop_mask": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "upa_resize_bilinear": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "upa_copy_rows": (_i, [_vp, C.c_long, _i, C.c_long, _vp, C.c_long, _vp]),
     "upa_graph_begin": (_i, [_vp]),
     "upa_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "upa_graph_launch": (_i, [_vp, _vp]),

@@ -473,6 +473,8 @@ class DetectionTrainer:
                  amp_scaler: bool = False):
         # YOLO11 blocks subclass / reuse C2f and Detect but have no backward here: the graph below would take a C3k2 for a C2f
         # and the DWConv class branch for the legacy one
+        if any(isinstance(m, H.Segment) for m in model.modules()):
+            raise L.UpaError("segmentation models (Segment head) have no training path on HIP: v8SegmentationLoss is out of scope")
         for m in model.modules():
             if isinstance(m, (B.C3k2, B.C2PSA)) or (isinstance(m, H.Detect) and not m.legacy_cls):
                 raise L.UpaError(f"{type(m).__name__} (YOLO11) has no training path on HIP yet")

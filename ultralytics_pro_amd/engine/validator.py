@@ -21,6 +21,8 @@ from ..utils.nms import nms_raw
 
 class DetectionValidator:
     def __init__(self, model=None, conf: float = 0.001, iou: float = 0.7, max_det: int = 300, max_gt: int = 64):
+        if model is not None and any(type(m).__name__ == "Segment" for m in model.modules()):
+            raise L.UpaError("segmentation models (Segment head) cannot be validated here: mask mAP is out of scope")
         self.model, self.conf, self.iou, self.max_det, self.max_gt = model, conf, iou, max_det, max_gt
         self.reset()
 

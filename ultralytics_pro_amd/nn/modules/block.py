@@ -14,7 +14,7 @@ from ...engine import runtime as R
 from .conv import Conv, PackedConv, _HipConvMixin, fold_bn, hip_conv2d, version_key
 
 __all__ = ("DFL", "SPPF", "C2f", "C3", "Bottleneck", "MHSA", "BottleneckTransformer", "BoT3", "C3k", "C3k2", "v10_Attention", "PSABlock",
-           "C2PSA")
+           "C2PSA", "Proto", "hip_conv_transpose2x2")
 
 
 class DFL(nn.Module):
@@ -551,3 +551,57 @@ class C2PSA(nn.Module):
         for i, m in enumerate(self.m):
             b = m(b, out=buf[:, c:] if i == len(self.m) - 1 else None)
         return self.cv2(buf, out=out)
+
+
+def hip_conv_transpose2x2(x: torch.Tensor, owner, conv: nn.ConvTranspose2d, out: torch.Tensor | None = None, key=None) -> torch.Tensor:
+    """nn.ConvTranspose2d(c1, c2, 2, 2, 0, bias=True) on `upa_conv_transpose2x2`.  x: NHWC view; the weights are packed once per
+    (device, dtype) and re-packed when the parameters change (`version_key`), like `Conv._packed`."""
+    if conv.kernel_size != (2, 2) or conv.stride != (2, 2) or conv.padding != (0, 0) or conv.output_padding != (0, 0) \
+            or conv.groups != 1 or conv.dilation != (1, 1):
+        raise L.UpaError(f"HIP transposed conv supports kernel 2, stride 2, padding 0 only, got {conv}")
+    L.require_gpu(x, "conv_transpose2x2")
+    vx = R.view_of(x)
+    cin, cout = conv.in_channels, conv.out_channels
+    cache = owner.__dict__.setdefault("_pk_cache", {})
+    ck = (id(conv), str(x.device), x.dtype, "convt")
+    ver = version_key(conv.weight, conv.bias)
+    hit = cache.get(ck)
+    if hit is None or hit[0] != ver:
+        w = conv.weight.detach().float().cpu().contiguous()
+        b = torch.zeros(cout) if conv.bias is None else conv.bias.detach().float().cpu()
+        host = torch.empty(L.lib().upa_conv_transpose2x2_packed_weight_bytes(cin, cout, vx.dtype), dtype=torch.uint8)
+        L.check(L.lib().upa_pack_conv_transpose2x2_weight(w.data_ptr(), cin, cout, vx.dtype, host.data_ptr()), "pack_conv_transpose2x2")
+        hit = (ver, (host.to(x.device), b.contiguous().to(x.device)))
+        cache[ck] = hit
+    wp, bias = hit[1]
+    y = out if out is not None else R.alloc_nhwc(vx.n, cout, 2 * vx.h, 2 * vx.w, x.dtype, x.device, key)
+    vy = R.view_of(y)
+    if vx.c != cin or (vy.n, vy.h, vy.w, vy.c, vy.dtype) != (vx.n, 2 * vx.h, 2 * vx.w, cout, vx.dtype):
+        raise L.UpaError(f"conv_transpose2x2: bad views in {tuple(x.shape)} out {tuple(y.shape)} for {conv}")
+    L.check(L.lib().upa_conv_transpose2x2(vx.ptr, vx.n, vx.h, vx.w, vx.c, vx.ld, wp.data_ptr(), bias.data_ptr(), vy.ptr, cout, vy.ld,
+                                          vx.dtype, L.current_stream(x.device)), "conv_transpose2x2")
+    return y
+
+
+class Proto(nn.Module):
+    """Mask prototypes: cv3(cv2(upsample(cv1(x)))) (block.py:257-276).  `upsample` is nn.ConvTranspose2d(c_, c_, 2, 2, 0) with bias and
+    no BN / activation: `upa_conv_transpose2x2`.  Returns the (B, c2, 2H, 2W) protos as an NHWC view (each pixel's c2 values are
+    contiguous: the layout `upa_process_mask` reads)."""
+
+    def __init__(self, c1: int, c_: int = 256, c2: int = 32):
+        super().__init__()
+        self.cv1 = Conv(c1, c_, k=3)
+        self.upsample = nn.ConvTranspose2d(c_, c_, 2, 2, 0, bias=True)
+        self.cv2 = Conv(c_, c_, k=3)
+        self.cv3 = Conv(c_, c2)
+
+    def forward(self, x, out=None):
+        if self.training:
+            raise L.UpaError("training-mode Proto is not on the HIP path (segmentation training is out of scope)")
+        x = R.to_nhwc(x, x.dtype)
+        t = hip_conv_transpose2x2(self.cv1(x), self, self.upsample, key=(id(self), "up"))
+        return self.cv3(self.cv2(t), out=out)
+
+    def train(self, mode: bool = True):
+        self.__dict__.pop("_pk_cache", None)
+        return super().train(mode)

@@ -9,10 +9,10 @@ import torch.nn as nn
 
 from ... import _lib as L
 from ...engine import runtime as R
-from .block import DFL
+from .block import DFL, Proto
 from .conv import Conv, DWConv, _HipConvMixin, hip_conv2d, version_key
 
-__all__ = ("Detect",)
+__all__ = ("Detect", "Segment")
 
 
 def _magic_exact(xmax: int, d: int) -> bool:
@@ -507,4 +507,109 @@ class Detect(nn.Module, _HipConvMixin):
 
     def train(self, mode: bool = True):
         self.invalidate_packed()
+        return super().train(mode)
+
+
+class Segment(Detect):
+    """YOLO Segment head (head.py:790-837): Detect + `proto = Proto(ch[0], npr, nm)` + per-level mask-coefficient branches
+    `cv4[l] = Conv3x3 -> Conv3x3 -> nn.Conv2d(c4, nm, 1)`, c4 = max(ch[0] // 4, nm).
+
+    Eval forward returns the reference's `(cat([y, mc], 1), (raw, mc, p))`: y = Detect's (B, 4+nc, A) output, untouched (every fused
+    Detect form and NMS kernel keeps its image stride), mc = (B, nm, A) f32 coefficients (`upa_mask_coef_rows` writes each level's
+    map into its anchor range), p = the (B, nm, 2H0, 2W0) protos as an NHWC view.  With `cat_out = False` the concatenated copy is
+    not made and the first element is y itself; `utils.ops.segment_postprocess_raw` reads y, mc and p either way.  The
+    concatenated tensor carries `_upa_parts = (y, mc)`, so `utils.nms` runs on y and gathers the coefficients of the kept rows.
+
+    Scheduling: a level's cv4 branch runs when `start_level` is called for it (the moment its feature map exists), and Proto with
+    level 0; levels the executor did not start (a direct call, or the levels `Detect.forward` groups) run in `forward`."""
+
+    cat_out = True
+
+    def __init__(self, nc: int = 80, nm: int = 32, npr: int = 256, ch: tuple = ()):
+        super().__init__(nc, ch)
+        self.nm = nm
+        self.npr = npr
+        self.proto = Proto(ch[0], self.npr, self.nm)
+        c4 = max(ch[0] // 4, self.nm)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.nm, 1)) for x in ch)
+
+    def _seg_plans(self):
+        return self.__dict__.setdefault("_seg", {})
+
+    def begin(self, n: int, level_hw, dtype, device) -> None:
+        super().begin(n, level_hw, dtype, device)
+        self._seg_begin(n, level_hw, device)
+
+    def _seg_begin(self, n, level_hw, device):
+        a0, tot = [], 0
+        for (h, w) in level_hw:
+            a0.append(tot)
+            tot += int(h) * int(w)
+        mc = R.alloc_plain((int(n), self.nm, tot), torch.float32, device, key=(id(self), "mc"))
+        self._seg_plans()[R.current_tag()] = dict(mc=mc, a0=a0, a_total=tot, n=int(n), hw=[(int(h), int(w)) for h, w in level_hw],
+                                                  done=set(), p=None)
+
+    def start_level(self, i: int, x: torch.Tensor, defer_ok: bool = True) -> None:
+        super().start_level(i, x, defer_ok)
+        plan = self._seg_plans().get(R.current_tag())
+        if plan is not None and i not in plan["done"] and self._seg_fits(plan, i, x):
+            self._seg_level(plan, i, x)
+
+    @staticmethod
+    def _seg_fits(plan, i, x) -> bool:
+        return plan["n"] == int(x.shape[0]) and plan["hw"][i] == (int(x.shape[2]), int(x.shape[3])) and plan["mc"].device == x.device
+
+    def _seg_level(self, plan, i: int, x: torch.Tensor) -> None:
+        """cv4[i] into mc[:, :, a0_i : a0_i + H_i W_i] (and Proto, for level 0)."""
+        x = R.to_nhwc(x, x.dtype)
+        seq = self.cv4[i]
+        t = seq[1](seq[0](x))
+        pk = self._packed(seq[2], None, x.device, x.dtype, False)
+        c = hip_conv2d(t, pk, 1, 0, L.ACT_NONE, key=(id(self), "mc_map", i))
+        vc = R.view_of(c)
+        L.check(L.lib().upa_mask_coef_rows(vc.ptr, vc.n, vc.h, vc.w, vc.c, vc.ld, vc.dtype, plan["mc"].data_ptr(), self.nm, 0,
+                                           plan["a_total"], plan["a0"][i], L.current_stream(x.device)), "mask_coef_rows")
+        plan["done"].add(i)
+        if i == 0:
+            plan["p"] = self.proto(x)
+
+    def forward(self, x):
+        if self.training:
+            raise L.UpaError("training-mode Segment is not on the HIP path (segmentation training is out of scope)")
+        det = super().forward(x)
+        y, raw = (det, None) if self.export else det
+        tag = R.current_tag()
+        plan = self._seg_plans().get(tag)
+        if plan is None or not all(self._seg_fits(plan, i, x[i]) for i in range(self.nl)):
+            self._seg_begin(x[0].shape[0], [(t.shape[2], t.shape[3]) for t in x], x[0].device)
+            plan = self._seg_plans()[tag]
+        for i in range(self.nl):
+            if i not in plan["done"]:
+                self._seg_level(plan, i, x[i])
+        self._seg_plans().pop(tag, None)
+        mc, p = plan["mc"], plan["p"]
+        if self.cat_out or self.export:
+            out = self._cat(y, mc)
+        else:
+            out = y
+        return (out, p) if self.export else (out, (raw, mc, p))
+
+    def _cat(self, y: torch.Tensor, mc: torch.Tensor) -> torch.Tensor:
+        """(B, 4+nc+nm, A) = cat([y, mc], 1) with two strided copies: `upa_copy_view` over one 'pixel' per image when every row is
+        a 16-byte multiple, else `upa_copy_rows` (any A)."""
+        n, cy, a = y.shape
+        ct = cy + self.nm
+        cat = R.alloc_plain((n, ct, a), torch.float32, y.device, key=(id(self), "cat"))
+        stream = L.current_stream(y.device)
+        lib = L.lib()
+        for src, c, dst in ((y, cy, cat), (mc, self.nm, cat[:, cy:])):
+            if (cy * a) % 4 == 0 and (self.nm * a) % 4 == 0:
+                L.check(lib.upa_copy_view(src.data_ptr(), n, 1, 1, c * a, c * a, dst.data_ptr(), ct * a, L.UPA_F32, stream), "copy_view")
+            else:
+                L.check(lib.upa_copy_rows(src.data_ptr(), n, c * a, c * a, dst.data_ptr(), ct * a, stream), "copy_rows")
+        cat._upa_parts = (y, mc)
+        return cat
+
+    def train(self, mode: bool = True):
+        self.__dict__.pop("_seg", None)
         return super().train(mode)

@@ -19,7 +19,7 @@ import yaml
 
 from .. import _lib as L
 from ..engine import runtime as R
-from .modules import (C2f, C2PSA, C3, C3k2, SPPF, BoT3, Bottleneck, Concat, Conv, Detect)
+from .modules import (C2f, C2PSA, C3, C3k2, SPPF, BoT3, Bottleneck, Concat, Conv, Detect, Segment)
 from .modules.conv import VirtualUpsample
 from .modules.resample import MaxPool2d, Upsample, ZeroPad2d
 
@@ -29,7 +29,7 @@ _NN_STANDINS = {"Upsample": Upsample, "MaxPool2d": MaxPool2d, "ZeroPad2d": ZeroP
 
 
 def _registry():
-    reg = {m.__name__: m for m in (Conv, C2f, C3, SPPF, BoT3, Bottleneck, Concat, Detect, C3k2, C2PSA)}
+    reg = {m.__name__: m for m in (Conv, C2f, C3, SPPF, BoT3, Bottleneck, Concat, Detect, Segment, C3k2, C2PSA)}
     try:
         from .modules.rtdetr import RTDETRDecoder
         reg["RTDETRDecoder"] = RTDETRDecoder
@@ -48,12 +48,16 @@ def make_divisible(x, divisor):
 
 
 def yaml_model_load(path):
-    """Load a model YAML; 'yolov8n.yaml' resolves to yolov8.yaml with scale 'n' (tasks.py:3147-3185)."""
+    """Load a model YAML; 'yolov8n.yaml' resolves to yolov8.yaml with scale 'n', 'yolov8n-seg.yaml' to yolov8-seg.yaml
+    (tasks.py:3147-3185)."""
     path = Path(path)
     stem, scale = path.stem, ""
     m = re.match(r"^(yolo(?:v)?\d+)([nslmx])$", stem)
+    seg = re.match(r"^(yolo(?:v)?\d+)([ntslmx])-seg$", stem)
     if m:
         stem, scale = m.group(1), m.group(2)
+    elif seg:
+        stem, scale = seg.group(1) + "-seg", seg.group(2)
     cands = [path] if path.is_file() else sorted(CFG_DIR.rglob(stem + ".yaml"))
     if not cands:
         raise FileNotFoundError(f"model YAML '{path}' not found under {CFG_DIR}")
@@ -107,8 +111,10 @@ def parse_model(d, ch, verbose=False):
                     args[3] = True
         elif mname == "Concat":
             c2 = sum(ch[x] for x in f)
-        elif mname == "Detect":
+        elif mname in ("Detect", "Segment"):
             args.append([ch[x] for x in f])
+            if mname == "Segment":  # npr (tasks.py:2990-2991)
+                args[2] = make_divisible(min(args[2], max_channels) * width, 8)
             m.legacy = legacy
         elif mname == "RTDETRDecoder":
             args.insert(1, [ch[x] for x in f])
@@ -520,6 +526,16 @@ class DetectionModel(BaseModel):
                     s /= 2
             scale.append(s)
         return [32.0]
+
+
+class SegmentationModel(DetectionModel):
+    """YOLO segmentation model (tasks.py:1343-1365): a DetectionModel whose head is `Segment`.  Inference only: training
+    (v8SegmentationLoss) and mask mAP are not on the HIP path."""
+
+    def __init__(self, cfg="yolov8n-seg.yaml", ch=3, nc=None, verbose=False):
+        super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
+        if not isinstance(self.model[-1], Segment):
+            raise L.UpaError(f"SegmentationModel needs a Segment head, {cfg} ends in {type(self.model[-1]).__name__}")
 
 
 RTDETRDetectionModel = DetectionModel  # eval path differs only in the head module (tasks.py:1608)

@@ -14,10 +14,26 @@ from ..engine import runtime as R
 
 def nms_raw(prediction: torch.Tensor, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False,
             max_det=300, nc=0, max_nms=30000, max_wh=7680, key=None):
-    """Device-side NMS. Returns (out (B,max_det,6) f32, counts (B,) int32, keep_idx (B,max_det) int32) without syncing."""
+    """Device-side NMS. Returns (out (B,max_det,6) f32, counts (B,) int32, keep_idx (B,max_det) int32) without syncing.
+
+    A prediction with extra channels after 4 + nc (a Segment head's `cat([y, mc], 1)`) returns (B, max_det, 6 + nm) rows instead:
+    the extra columns of each kept anchor are carried through (nms.py:74-122).  NMS itself runs on the (B, 4+nc, A) part -
+    Segment's own y when the tensor carries it (`_upa_parts`), else a contiguous copy of the first 4 + nc rows."""
     if isinstance(prediction, (list, tuple)):
         prediction = prediction[0]
     L.require_gpu(prediction, "non_max_suppression")
+    parts = getattr(prediction, "_upa_parts", None)
+    if parts is not None or (nc and prediction.dim() == 3 and prediction.shape[1] > 4 + nc):
+        if parts is not None:
+            y, extra = parts
+        else:
+            y, extra = prediction[:, :4 + nc].contiguous(), prediction[:, 4 + nc:].contiguous()
+        out, counts, keep = nms_raw(y, conf_thres, iou_thres, classes, agnostic, multi_label, max_det, nc, max_nms, max_wh, key)
+        b, ne, a = extra.shape
+        rows = R.alloc_plain((b, max_det, 6 + ne), torch.float32, y.device, key=(key, "nms_rows"))
+        L.check(L.lib().upa_nms_gather_extra(extra.data_ptr(), b, ne, a, keep.data_ptr(), counts.data_ptr(), int(max_det),
+                                             out.data_ptr(), rows.data_ptr(), 6 + ne, L.current_stream(y.device)), "nms_gather_extra")
+        return rows, counts, keep
     assert 0 <= conf_thres <= 1, f"Invalid Confidence threshold {conf_thres}, valid values are between 0.0 and 1.0"
     assert 0 <= iou_thres <= 1, f"Invalid IoU {iou_thres}, valid values are between 0.0 and 1.0"
     if prediction.dtype != torch.float32 or not prediction.is_contiguous():
@@ -25,7 +41,7 @@ def nms_raw(prediction: torch.Tensor, conf_thres=0.25, iou_thres=0.45, classes=N
     b, ch, a = prediction.shape
     nc = nc or (ch - 4)
     if ch != 4 + nc:
-        raise L.UpaError("extra mask channels (segmentation) are outside the hot-path scope")
+        raise L.UpaError(f"prediction has {ch} channels, fewer than 4 + nc = {4 + nc}")
     dev = prediction.device
     lib = L.lib()
     ws_bytes = lib.upa_nms_workspace_bytes(b, nc, a, int(bool(multi_label)), max_nms)
@@ -63,7 +79,8 @@ def non_max_suppression(prediction, conf_thres: float = 0.25, iou_thres: float =
                         agnostic: bool = False, multi_label: bool = False, labels=(), max_det: int = 300, nc: int = 0,
                         max_time_img: float = 0.05, max_nms: int = 30000, max_wh: int = 7680, rotated: bool = False,
                         end2end: bool = False, return_idxs: bool = False):
-    """Reference-compatible wrapper: list of (n, 6) tensors [x1, y1, x2, y2, conf, cls] per image (nms.py:13-166).
+    """Reference-compatible wrapper: list of (n, 6) tensors [x1, y1, x2, y2, conf, cls] per image (nms.py:13-166); (n, 6 + nm)
+    with the extra columns (mask coefficients) of a Segment output.
     `max_time_img` is accepted and ignored: the reference's wall-clock abort (nms.py:81,162-164) is not emulated."""
     if labels or rotated:
         raise L.UpaError("apriori labels / rotated boxes are outside the hot-path scope")

@@ -35,3 +35,196 @@ def scale_boxes(img1_shape, boxes: torch.Tensor, img0_shape, ratio_pad=None, pad
 def make_divisible(x, divisor):
     """Nearest multiple of divisor not below x (utils/ops.py:137-150)."""
     return math.ceil(x / divisor) * divisor
+
+
+# ---- instance masks (utils/ops.py:489-583, models/yolo/segment/predict.py:84-109) on `upa_process_mask` ----------------------------
+
+def _protos_nhwc(protos: torch.Tensor) -> torch.Tensor:
+    """(B, nm, mh, mw) protos as an NHWC view: Segment's own output already is one, anything else goes through the transpose kernel."""
+    from ..engine import runtime as R
+    if protos.dim() == 3:
+        protos = protos[None]
+    if R.is_nhwc_view(protos) and protos.dtype in (torch.float32, torch.bfloat16):
+        return protos
+    return R.to_nhwc(protos.float().contiguous(), torch.float32)
+
+
+def scale_masks_window(mh: int, mw: int, shape, padding: bool = True):
+    """(top, left, bottom, right) of the proto map that scale_masks resamples to `shape` (ops.py:562-583, same rounding)."""
+    gain = min(mh / shape[0], mw / shape[1])
+    pad_w = mw - shape[1] * gain
+    pad_h = mh - shape[0] * gain
+    if padding:
+        pad_w /= 2
+        pad_h /= 2
+    top, left = (round(pad_h - 0.1), round(pad_w - 0.1)) if padding else (0, 0)
+    bottom = mh - round(pad_h + 0.1)
+    right = mw - round(pad_w + 0.1)
+    return int(top), int(left), int(bottom), int(right)
+
+
+def crop_mask(masks: torch.Tensor, boxes: torch.Tensor) -> torch.Tensor:
+    """masks (N, H, W) zeroed outside the xyxy boxes (N, 4) (ops.py:489-513), on `upa_crop_mask`: the float-comparison form, the
+    branch the reference takes on a GPU.  Returns a new float32 tensor."""
+    L.require_gpu(masks, "crop_mask")
+    if boxes.device != masks.device:
+        boxes = boxes.to(masks.device)
+    m = masks.float().contiguous()
+    b = boxes.float().contiguous()
+    n, h, w = m.shape
+    out = torch.empty_like(m)
+    if out.numel() == 0:
+        return out
+    L.check(L.lib().upa_crop_mask(m.data_ptr(), n, h, w, b.data_ptr(), int(b.shape[-1]) if n else 4, out.data_ptr(),
+                                  L.current_stream(m.device)), "crop_mask")
+    return out
+
+
+def scale_masks(masks: torch.Tensor, shape, padding: bool = True) -> torch.Tensor:
+    """(N, C, H, W) masks resampled to `shape` (h, w) after removing the letterbox padding (ops.py:562-583), on `upa_resize_bilinear`
+    (bilinear, align_corners = False).  Returns float32."""
+    L.require_gpu(masks, "scale_masks")
+    m = masks.float().contiguous()
+    n, c, mh, mw = m.shape
+    oh, ow = int(shape[0]), int(shape[1])
+    top, left, bottom, right = scale_masks_window(int(mh), int(mw), (oh, ow), padding)
+    out = torch.empty((n, c, oh, ow), dtype=torch.float32, device=m.device)
+    if out.numel() == 0:
+        return out
+    L.check(L.lib().upa_resize_bilinear(m.data_ptr(), n * c, mh, mw, top, left, bottom, right, out.data_ptr(), oh, ow,
+                                        L.current_stream(m.device)), "scale_masks")
+    return out
+
+
+def _launch_process_mask(p, coef, coef_ld, det, det_ld, max_det, counts, out_hw, native, crop, window, masks, nonempty, capacity, total):
+    from ..engine import runtime as R
+    vp = R.view_of(p)
+    top, left, bottom, right = window
+    L.check(L.lib().upa_process_mask(vp.ptr, vp.n, vp.h, vp.w, vp.c, vp.ld, vp.dtype, coef.data_ptr(), int(coef_ld), det.data_ptr(),
+                                     int(det_ld), int(max_det), counts.data_ptr(), int(out_hw[0]), int(out_hw[1]), int(bool(native)),
+                                     float(crop[0]), float(crop[1]), int(top), int(left), int(bottom), int(right),
+                                     None if masks is None else masks.data_ptr(), None if nonempty is None else nonempty.data_ptr(),
+                                     int(capacity), total.data_ptr(), L.current_stream(p.device)), "process_mask")
+
+
+def _single_image_masks(protos, masks_in, bboxes, out_hw, native, crop, window):
+    L.require_gpu(masks_in, "process_mask")
+    p = _protos_nhwc(protos)
+    n = int(masks_in.shape[0])
+    dev = masks_in.device
+    masks = torch.empty((n, int(out_hw[0]), int(out_hw[1])), dtype=torch.uint8, device=dev)
+    if n == 0:
+        return masks
+    coef = masks_in.float().contiguous()
+    det = bboxes.float().contiguous()
+    counts = torch.tensor([n], dtype=torch.int32, device=dev)
+    nonempty = torch.empty((n,), dtype=torch.int32, device=dev)
+    total = torch.empty((1,), dtype=torch.int32, device=dev)
+    _launch_process_mask(p, coef, coef.shape[1], det, det.shape[1], n, counts, out_hw, native, crop, window, masks, nonempty, n, total)
+    return masks
+
+
+def process_mask(protos, masks_in, bboxes, shape, upsample: bool = False):
+    """(N, H, W) uint8 masks (ops.py:517-545): coefficients x protos, crop_mask at proto resolution with the boxes scaled by
+    (mw / W, mh / H), bilinear to `shape` when `upsample` (else the (mh, mw) proto grid), > 0.  protos: (nm, mh, mw) of one image."""
+    p = protos if protos.dim() == 3 else protos[0]
+    _, mh, mw = p.shape
+    out = tuple(int(s) for s in shape[:2]) if upsample else (int(mh), int(mw))
+    return _single_image_masks(p, masks_in, bboxes, out, False, (mw / shape[1], mh / shape[0]), (0, 0, int(mh), int(mw)))
+
+
+def process_mask_native(protos, masks_in, bboxes, shape):
+    """(N, H, W) uint8 masks (ops.py:548-560): coefficients x protos, scale_masks to `shape`, crop_mask with the boxes in `shape`
+    coordinates, > 0."""
+    p = protos if protos.dim() == 3 else protos[0]
+    _, mh, mw = p.shape
+    out = tuple(int(s) for s in shape[:2])
+    return _single_image_masks(p, masks_in, bboxes, out, True, (1.0, 1.0), scale_masks_window(int(mh), int(mw), out))
+
+
+def _seg_parts(preds, nc: int):
+    """(y (B, 4+nc, A), mc (B, nm, A), protos) from a Segment head's eval output `(y | cat([y, mc], 1), (raw, mc, p))`."""
+    first, second = preds[0], preds[1]
+    if not (isinstance(second, (list, tuple)) and len(second) == 3):
+        raise L.UpaError("segment postprocess expects a Segment head's eval output (y, (raw, mc, protos))")
+    _, mc, p = second
+    parts = getattr(first, "_upa_parts", None)
+    if parts is not None:
+        y = parts[0]
+    else:
+        y = first
+        nc = nc or (int(first.shape[1]) - 4 - int(mc.shape[1]))
+        if first.shape[1] != 4 + nc:  # a concatenated tensor without its parts: the detection rows as a contiguous copy
+            y = first[:, :4 + nc].contiguous()
+    return y, mc, p
+
+
+def segment_postprocess_raw(preds, conf_thres: float = 0.25, iou_thres: float = 0.7, classes=None, agnostic: bool = False,
+                            multi_label: bool = False, max_det: int = 300, nc: int = 0, imgsz=None, orig_shape=None,
+                            retina_masks: bool = False, capacity: int | None = None, key=None):
+    """Device-side segmentation postprocess with no host synchronisation (capturable in `DetectionModel.compile(post=...)` and
+    `PipelinedRunner`): NMS -> coefficient gather -> masks -> scale_boxes, as SegmentationPredictor.construct_result
+    (models/yolo/segment/predict.py:84-109) does image by image.
+
+    Returns a dict of device tensors: rows (B, max_det, 6 + nm) [box, conf, cls, coefficients] with the box scaled to `orig_shape`
+    when given, counts (B,), masks (capacity, H, W) uint8 - the mask of (image i, detection j) is row base[i] + j, base = exclusive
+    prefix sum of counts -, nonempty (capacity,) int32 (the predictor's keep filter), total (1,) int32 = sum(counts): rows past
+    `capacity` are not written (the caller compares total with capacity).  (H, W) = imgsz, the network input size (default: 4x the
+    proto map, which is what Proto produces from the stride-8 level), or orig_shape with `retina_masks` (process_mask_native).  One
+    `orig_shape` for the whole batch."""
+    from ..engine import runtime as R
+    from .nms import nms_raw
+    y, mc, p = _seg_parts(preds, nc)
+    nc = int(y.shape[1]) - 4
+    b, nm, a = mc.shape
+    dev = y.device
+    out, counts, keep = nms_raw(y, conf_thres, iou_thres, classes, agnostic, multi_label, max_det, nc, key=key)
+    rows = R.alloc_plain((b, max_det, 6 + nm), torch.float32, dev, key=(key, "seg_rows"))
+    L.check(L.lib().upa_nms_gather_extra(mc.data_ptr(), b, nm, a, keep.data_ptr(), counts.data_ptr(), int(max_det), out.data_ptr(),
+                                         rows.data_ptr(), 6 + nm, L.current_stream(dev)), "nms_gather_extra")
+    pv = _protos_nhwc(p)
+    mh, mw = int(pv.shape[2]), int(pv.shape[3])
+    ih, iw = (4 * mh, 4 * mw) if imgsz is None else (int(imgsz[0]), int(imgsz[1]))
+    out_hw = (int(orig_shape[0]), int(orig_shape[1])) if (retina_masks and orig_shape is not None) else (ih, iw)
+    if capacity is None:  # every row up to a 256 MB mask buffer
+        capacity = max(1, min(b * max_det, (256 << 20) // (out_hw[0] * out_hw[1])))
+    masks = R.alloc_plain((capacity, out_hw[0], out_hw[1]), torch.uint8, dev, key=(key, "seg_masks"))
+    nonempty = R.alloc_plain((capacity,), torch.int32, dev, key=(key, "seg_nonempty"))
+    total = R.alloc_plain((1,), torch.int32, dev, key=(key, "seg_total"))
+    if retina_masks and orig_shape is not None:
+        scale_boxes((ih, iw), rows, orig_shape)  # boxes to image space first, then masks in image coordinates
+        _launch_process_mask(pv, rows[..., 6:], 6 + nm, rows, 6 + nm, max_det, counts, out_hw, True, (1.0, 1.0),
+                             scale_masks_window(mh, mw, out_hw), masks, nonempty, capacity, total)
+    else:
+        _launch_process_mask(pv, rows[..., 6:], 6 + nm, rows, 6 + nm, max_det, counts, out_hw, False, (mw / iw, mh / ih),
+                             (0, 0, mh, mw), masks, nonempty, capacity, total)
+        if orig_shape is not None:
+            scale_boxes((ih, iw), rows, orig_shape)
+    return dict(rows=rows, counts=counts, masks=masks, nonempty=nonempty, total=total)
+
+
+def segment_postprocess(preds, conf_thres: float = 0.25, iou_thres: float = 0.7, classes=None, agnostic: bool = False,
+                        multi_label: bool = False, max_det: int = 300, nc: int = 0, imgsz=None, orig_shape=None,
+                        retina_masks: bool = False, capacity: int | None = None):
+    """Per image (boxes (n, 6) [x1, y1, x2, y2, conf, cls], masks (n, H, W) uint8 or None), mirroring
+    SegmentationPredictor.construct_result: rows whose mask is empty are dropped.  Raises if the masks overflow `capacity`."""
+    r = segment_postprocess_raw(preds, conf_thres, iou_thres, classes, agnostic, multi_label, max_det, nc, imgsz, orig_shape,
+                                retina_masks, capacity)
+    n = r["counts"].tolist()
+    total = int(r["total"].item())
+    cap = int(r["masks"].shape[0])
+    if total > cap:
+        raise L.UpaError(f"{total} masks overflow the mask buffer of {cap} rows: pass a larger capacity")
+    res, base = [], 0
+    for i, k in enumerate(n):
+        det = r["rows"][i, :k, :6]
+        if k == 0:
+            res.append((det, None))
+            continue
+        masks = r["masks"][base:base + k]
+        keep = r["nonempty"][base:base + k] > 0
+        if not bool(keep.all()):
+            det, masks = det[keep], masks[keep]
+        res.append((det, masks))
+        base += k
+    return res

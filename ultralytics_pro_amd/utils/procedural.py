@@ -102,7 +102,12 @@ ATTN_GAIN2 = 1.0  # MHSA q/k/v 1x1 convs (block.py:6020-6062): energy = q^T k is
 # gain^2 of the YOLO11 attention's qkv 1x1 conv (attn.qkv) per family: at CONV_GAIN2 the softmax over 400 tokens is flat (max probability
 # 0.003 ~ 1/400); 100 makes it neither flat nor one-hot (median max probability 0.017, ~7x uniform) while the f32 model stays
 # reproducible: larger gains make the head so sensitive that the f32 reference itself sits 8e-3 px from its float64 run
-PSA_QKV_GAIN2 = {"yolov11n": 100.0, "smooth:yolov11n": 100.0}
+PSA_QKV_GAIN2 = {"yolov11n": 100.0, "smooth:yolov11n": 100.0, "yolov11n-seg": 100.0, "smooth:yolov11n-seg": 100.0}
+# Mean bias of the Segment head's final coefficient 1x1 convs (cv4.l.2, head.py:790-837) per family, U(m - 0.1, m + 0.1).  The protos
+# leave their SiLU mostly positive, and with the default U(-0.1, 0.1) biases the yolov11n-seg coefficients of the kept anchors weight
+# them so that coefficients . protos is negative over almost every box: every stored instance mask came out empty.  A positive bias
+# adds a positive multiple of the proto mass; these values fill roughly 25-60 % of a kept box (none empty, none full).
+MASK_COEF_BIAS = {"yolov11n-seg": 10.0, "smooth:yolov11n-seg": 1.0}
 RES_GAIN2 = 0.3  # last conv of a residual branch (Bottleneck.cv2 with add=True): damped, else x + f(x) chains explode
 CLS_BIAS_SPREAD = 0.5
 # Detect-head recipe per model family: (final cls 1x1 weight gain, mean final cls bias, final box 1x1 weight gain).
@@ -116,6 +121,9 @@ HEAD_RECIPE = {
     "yolov5-BoT3": (0.8, -5.0, 0.25),
     # the DWConv class branch has no damping: small final gains; ~2 % of anchors above 0.25, f32 vs float64 within 5e-4 px / 3e-6
     "yolov11n": (0.1, -6.8, 0.1),
+    # segmentation: the detection graphs with a Segment head - the box / class branches are the detection ones, same gains
+    "yolov8n-seg": (5.0, -4.4, 5.0),
+    "yolov11n-seg": (0.1, -6.8, 0.1),
 }
 RTDETR_SCORE_BIAS = -6.5
 RTDETR_SCORE_GAIN = 1.5
@@ -148,6 +156,8 @@ SMOOTH_RECIPE = {
     "yolov3-tiny": (5.5, 4.0, -3.16, 1.5),
     "yolov5-BoT3": (6.5, 4.0, -3.75, 1.5),
     "yolov11n": (6.5, 0.1, -2.66, 0.05),
+    "yolov8n-seg": (6.5, 4.0, -4.09, 1.5),
+    "yolov11n-seg": (6.5, 0.1, -2.66, 0.05),
 }
 
 
@@ -208,6 +218,8 @@ def procedural_tensor(key: str, ref: torch.Tensor, kind: str, seed: int = 0, res
         if smooth and kind == "conv":  # weights a bf16 model stores exactly (round-to-nearest-even of the same draws)
             w = w.to(torch.bfloat16).to(torch.float32)
         return w
+    if len(parts) >= 5 and parts[-4] == "cv4" and parts[-2] == "2" and parts[-3].isdigit() and family in MASK_COEF_BIAS:
+        return uniform(key, shape, MASK_COEF_BIAS[family] - 0.1, MASK_COEF_BIAS[family] + 0.1, seed)
     if det_final and parts[-4] == "cv3":
         return uniform(key, shape, cls_bias_shift - CLS_BIAS_SPREAD, cls_bias_shift + CLS_BIAS_SPREAD, seed)
     if det_final and parts[-4] == "cv2":
@@ -243,7 +255,7 @@ def apply_procedural_weights(model: torch.nn.Module, seed: int = 0, family: str 
     for mname, m in model.named_modules():
         if isinstance(m, (torch.nn.BatchNorm2d, torch.nn.LayerNorm)):
             kind = "norm"
-        elif isinstance(m, torch.nn.Conv2d):
+        elif isinstance(m, (torch.nn.Conv2d, torch.nn.ConvTranspose2d)):  # ConvTranspose2d: Proto.upsample (segmentation only)
             kind = "conv"
         else:
             kind = "linear"
