@@ -472,7 +472,10 @@ __global__ __launch_bounds__(256) void msdeform_kernel(const VT* value, int ldv,
       const float gx = 2.f * lx - 1.f, gy = 2.f * ly - 1.f;
       const float ix = ((gx + 1.f) * (float)W - 1.f) / 2.f, iy = ((gy + 1.f) * (float)H - 1.f) / 2.f;
       const float x0f = floorf(ix), y0f = floorf(iy);
-      const int x0 = (int)x0f, y0 = (int)y0f;
+      // the integer corner only is clamped before the conversion (tx / ty keep the reference's arithmetic): an offset that puts the
+      // pixel coordinate past 2^31 converts to INT_MAX, `x0 + 1` wraps, and the compiler - entitled to assume it does not - tests
+      // `x0 > -2 && x0 + 1 < W`, true for the wrapped value: the corner counted as inside and the load went to a wild address
+      const int x0 = (int)fminf(fmaxf(x0f, -2.f), (float)W), y0 = (int)fminf(fmaxf(y0f, -2.f), (float)H);
       const float tx = ix - x0f, ty = iy - y0f;
       float s = 0.f;
       const bool xin0 = x0 >= 0 && x0 < W, xin1 = x0 + 1 >= 0 && x0 + 1 < W;
