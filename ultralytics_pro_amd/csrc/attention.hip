@@ -128,9 +128,6 @@ __global__ __launch_bounds__(64 * KP) void mhsa_kernel(const char* q, const char
 // exp via v_exp_f32 on log2(e)-scaled scores (the scale of nn.MultiheadAttention folds into the same multiply), P rounded to bf16
 // (the values being averaged are bf16 already); f32 accumulation, f32 residual add, one rounding of the output as before.
 // =====================================================================================================================
-typedef __attribute__((address_space(1))) const void* agptr_t;
-typedef __attribute__((address_space(3))) void* alptr_t;
-__device__ __attribute__((aligned(16))) unsigned g_mhsa_zero16[4] = {0u, 0u, 0u, 0u};
 
 __global__ __launch_bounds__(512) void mhsa_mfma_bf16_d32_kernel(const char* q, const char* k, const char* v, int ld, int L, int Lp, int VP,
                                                                  int heads, const char* res, int ldr, char* y, int ldy, float c_log2) {
@@ -145,8 +142,8 @@ __global__ __launch_bounds__(512) void mhsa_mfma_bf16_d32_kernel(const char* q, 
   // ---- K by LDS-DMA (slot i of the image = 16-byte group (i & 3) ^ swz of key i >> 2; zero page past L)
   for (int base = wave * 64; base < Lp * 4; base += NT) {
     const int i = base + lane, key = i >> 2, cg = (i & 3) ^ ((key >> 1) & 3);
-    const char* src = key < L ? k + ((pix0 + key) * (size_t)ld + h * 32 + cg * 8) * 2 : reinterpret_cast<const char*>(g_mhsa_zero16);
-    __builtin_amdgcn_global_load_lds((agptr_t)src, (alptr_t)(ks + base * 16), 16, 0, 0);
+    const char* src = key < L ? k + ((pix0 + key) * (size_t)ld + h * 32 + cg * 8) * 2 : reinterpret_cast<const char*>(g_zero16);
+    lds_dma16(src, ks + base * 16);
   }
   // ---- V transposed: item = (key, 8 dims) -> eight 2-byte stores
   for (int i = tid; i < Lp * 4; i += NT) {

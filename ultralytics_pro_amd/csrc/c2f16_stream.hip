@@ -20,12 +20,6 @@
 
 #include "common.h"
 
-typedef __attribute__((address_space(1))) const void* c16_gptr_t;
-typedef __attribute__((address_space(3))) void* c16_lptr_t;
-typedef __attribute__((ext_vector_type(4))) short c16_s16x4;
-
-__device__ __attribute__((aligned(64))) unsigned int g_c16_zero_page[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
 struct C16Params {
   const char* x; char* y;
   const char *w1, *wa, *wb, *w2;   // cv1 (1x1 32 -> 32), m.cv1 / m.cv2 (3x3 16 -> 16), cv2 (1x1 48 -> 32): upa_pack_conv_weight(bf16) layouts
@@ -85,17 +79,8 @@ struct Ctx {
   int oy0, ox0;   // DOWN: first stride-2 output row / column of this workgroup
 };
 
-__device__ __forceinline__ float silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-__device__ __forceinline__ f32x4 mfma32(const u32x4& a, const u32x4& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(&a), *reinterpret_cast<const bf16x8*>(&b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16(const u32x2& a, const u32x2& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(*reinterpret_cast<const c16_s16x4*>(&a), *reinterpret_cast<const c16_s16x4*>(&b), c, 0, 0, 0);
-}
-__device__ __forceinline__ u32x4 lds128(const char* sm, int off) { return *reinterpret_cast<const u32x4*>(sm + off); }
-__device__ __forceinline__ u32x2 lds64(const char* sm, int off) { return *reinterpret_cast<const u32x2*>(sm + off); }
 __device__ __forceinline__ u32x2 silu_pack(const f32x4& a, unsigned m) {
-  return u32x2{pack_bf16x2(silu(a[0]), silu(a[1])) & m, pack_bf16x2(silu(a[2]), silu(a[3])) & m};
+  return u32x2{pack_bf16x2(silu_rcp(a[0]), silu_rcp(a[1])) & m, pack_bf16x2(silu_rcp(a[2]), silu_rcp(a[3])) & m};
 }
 
 // ---- cv1 (1x1, 32 -> 32) on units [U0, U0 + NU) of the band that has landed; with DMA: also the input bands by LDS-DMA, PREF ahead.  Band b = x rows
@@ -143,11 +128,11 @@ struct Cv1 {
     if (2 * b >= x.LP) return 0;  // wave-uniform
     const int gy = x.ry0 + 2 * b + (x.lane >> 5);
     const bool ok = colok && gy >= 0 && gy < x.p->H;
-    const char* src = ok ? ximg + ((unsigned)gy * rowpitch + coloff) : reinterpret_cast<const char*>(g_c16_zero_page);
+    const char* src = ok ? ximg + ((unsigned)gy * rowpitch + coloff) : reinterpret_cast<const char*>(g_zero16);
     const int dst = G::XB + ((2 * b) & (G::XROWS - 1)) * G::XROWB;  // + lane * 16 by the hardware
 #pragma unroll
     for (int cg = 0; cg < 4; ++cg)
-      __builtin_amdgcn_global_load_lds((c16_gptr_t)(src + (ok ? cg * 16 : 0)), (c16_lptr_t)(x.sm + dst + cg * G::XPLANE), 16, 0, 0);
+      lds_dma16(src + (ok ? cg * 16 : 0), x.sm + dst + cg * G::XPLANE);
     return 4;
   }
   __device__ __forceinline__ void step(const Ctx& x, int s) {
@@ -242,8 +227,8 @@ struct Conv3 {
       } else {
         // the shortcut: y1 (y planes 2, 3) at the same pixel = y column col + 2; f32 add, then the bf16 rounding of the separate launches
         const u32x2 rs = lds64(sm, G::YB + (2 + (g >> 1)) * G::YPLANE + (row & (G::YROWS - 1)) * G::YROWB + (u_col[u] + 2) * 16 + (g & 1) * 8);
-        const float v0 = silu(acc[u][0]) + __uint_as_float(rs[0] << 16), v1 = silu(acc[u][1]) + __uint_as_float(rs[0] & 0xFFFF0000u);
-        const float v2 = silu(acc[u][2]) + __uint_as_float(rs[1] << 16), v3 = silu(acc[u][3]) + __uint_as_float(rs[1] & 0xFFFF0000u);
+        const float v0 = silu_rcp(acc[u][0]) + __uint_as_float(rs[0] << 16), v1 = silu_rcp(acc[u][1]) + __uint_as_float(rs[0] & 0xFFFF0000u);
+        const float v2 = silu_rcp(acc[u][2]) + __uint_as_float(rs[1] << 16), v3 = silu_rcp(acc[u][3]) + __uint_as_float(rs[1] & 0xFFFF0000u);
         o = u32x2{pack_bf16x2(v0, v1), pack_bf16x2(v2, v3)};
       }
       *reinterpret_cast<u32x2*>(sm + (ok ? oa : G::DUMMY + x.lane * 8)) = o;
@@ -309,10 +294,7 @@ struct Cv2 {
     for (int u = 0; u < NU; ++u)
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt) o[u][nt] = mfma32(w32[nt], by[u], bias[nt]);
-    // a 4-pass MFMA must not take the result of an 8-pass one as the NEXT instruction's srcC without wait states (c2f_stream.hip: f_role)
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 15" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
+    mfma_shape_fence();  // the 32-wide chain is finished; the 16-wide k-step continues on the same accumulators
 #pragma unroll
     for (int u = 0; u < NU; ++u)
 #pragma unroll
@@ -499,16 +481,6 @@ __global__ __launch_bounds__(768, 6) void c2f16_down_kernel(const C16Params p) {
   }
 }
 
-static int c16s_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
 // Called by upa_c2f_fused (c2f_fused.hip) for the C2f(32, 32, n = 1, shortcut) form: UPA_EUNSUPPORTED = the caller runs the tile form.
 int upa_c2f16_stream_launch(const void* x, int n, int h, int w, int ldx, const void* w1, const float* b1, const void* wa, const float* ba,
                             const void* wb, const float* bb, const void* w2, const float* b2, void* y, int ldy, const upa_opts* opts,
@@ -527,7 +499,7 @@ int upa_c2f16_stream_launch(const void* x, int n, int h, int w, int ldx, const v
   int L = (h + 1) & ~1;
   if (rows >= 4) L = (rows + 1) & ~1;
   else {  // (-1, "the whole height", is the in-flight choice for the 16-wave kernels of c2f_stream.hip: their workgroups own a CU.  Three of these share one, so the one-round grid is the right size in flight as well)
-    const long slots = 3L * c16s_cus();  // three workgroups fit a CU (49.5 KB of LDS, 8 waves each)
+    const long slots = 3L * upa_num_cus();  // three workgroups fit a CU (49.5 KB of LDS, 8 waves each)
     long best = -1;
     for (int parts = 1; parts <= cdiv(h, 8); ++parts) {
       const int l = cdiv(cdiv(h, parts), 2) * 2;
@@ -575,7 +547,7 @@ extern "C" int upa_c2f16_down_fused(const void* x, int n, int h, int w, int ldx,
   int L = oh;
   if (rows >= 4) L = rows / 2;
   else {
-    const long slots = 2L * c16s_cus();
+    const long slots = 2L * upa_num_cus();
     long best = -1;
     for (int parts = 1; parts <= cdiv(oh, 4); ++parts) {
       const int l = cdiv(oh, parts);

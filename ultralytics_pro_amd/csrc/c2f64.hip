@@ -26,11 +26,6 @@
 #include "common.h"
 UPA_STAMP_DEFINE(c2f64)
 
-typedef __attribute__((address_space(1))) const void* c6gptr_t;
-typedef __attribute__((address_space(3))) void* c6lptr_t;
-
-__device__ __attribute__((aligned(16))) unsigned g_c2f64_zero16[4] = {0u, 0u, 0u, 0u};
-
 struct C2f64Params {
   const char* x; char* y;
   const char* up;        // half-resolution tensor holding the first upC channels of every pixel at (y / 2, x / 2), or nullptr
@@ -42,10 +37,6 @@ struct C2f64Params {
 };
 
 namespace c2f64 {
-__device__ __forceinline__ float silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-__device__ __forceinline__ f32x4 mfma32(const u32x4& a, const u32x4& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(&a), *reinterpret_cast<const bf16x8*>(&b), c, 0, 0, 0);
-}
 // 128-byte pixel records, 16-byte group cg of pixel px at slot cg ^ (px & 7)
 __device__ __forceinline__ int rec_addr(int px, int cg) { return px * 128 + ((cg ^ (px & 7)) << 4); }
 // the 8 bytes holding channels 16 j + 4 g .. + 3 of pixel px
@@ -83,7 +74,7 @@ __device__ __forceinline__ void conv3x3_stage(const char* src, char* dst, const 
     const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
     float v[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = in ? silu(acc[e]) : 0.f;
+    for (int e = 0; e < 4; ++e) v[e] = in ? silu_rcp(acc[e]) : 0.f;
     if (res) {  // the shortcut tensor is zero outside the image already
       const u32x2 rr = *reinterpret_cast<const u32x2*>(res + quad_addr((yy + OFF) * SR + xx + OFF, j, g));
       v[0] += __uint_as_float(rr[0] << 16); v[1] += __uint_as_float(rr[0] & 0xFFFF0000u);
@@ -161,8 +152,8 @@ __global__ __launch_bounds__(512, 2) void c2f64_fused_kernel(const C2f64Params p
 #pragma unroll
     for (int it = 0; it < NPASS; ++it) {
       const char* src = xoff[it] != 0xffffffffu ? base + (size_t)(fromUp ? uoff[it] : xoff[it]) + c * 128
-                                                : reinterpret_cast<const char*>(g_c2f64_zero16);
-      __builtin_amdgcn_global_load_lds((c6gptr_t)src, (c6lptr_t)(buf + (it * 512 + wave * 64) * 16), 16, 0, 0);
+                                                : reinterpret_cast<const char*>(g_zero16);
+      lds_dma16(src, buf + (it * 512 + wave * 64) * 16);
     }
   };
   UPA_STAMP_AT(0);
@@ -235,7 +226,7 @@ __global__ __launch_bounds__(512, 2) void c2f64_fused_kernel(const C2f64Params p
     const bool in = q < XPX && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
     float v[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = in ? silu(acc1[i][e]) : 0.f;
+    for (int e = 0; e < 4; ++e) v[e] = in ? silu_rcp(acc1[i][e]) : 0.f;
     if (q < XPX) *reinterpret_cast<u32x2*>(y1s + quad_addr(hy * PY1 + hx, j, g)) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
   }
 #pragma unroll
@@ -244,7 +235,7 @@ __global__ __launch_bounds__(512, 2) void c2f64_fused_kernel(const C2f64Params p
     if (mt >= NMT0) continue;
     const int q = mt * 16 + r;
     *reinterpret_cast<u32x2*>(y0s + quad_addr(q, j, g)) =
-        u32x2{pack_bf16x2(silu(acc0[i][0]), silu(acc0[i][1])), pack_bf16x2(silu(acc0[i][2]), silu(acc0[i][3]))};
+        u32x2{pack_bf16x2(silu_rcp(acc0[i][0]), silu_rcp(acc0[i][1])), pack_bf16x2(silu_rcp(acc0[i][2]), silu_rcp(acc0[i][3]))};
   }
   load_w18(wB, p.wm[1], j, lane);  // every later stage's weights are fetched one stage ahead
   f32x4 bA = *reinterpret_cast<const f32x4*>(p.bm[0] + j * 16 + 4 * g);
@@ -312,8 +303,8 @@ __global__ __launch_bounds__(512, 2) void c2f64_fused_kernel(const C2f64Params p
     float v0[4], v1[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      v0[e] = silu(o0[e]);
-      v1[e] = silu(o1[e]);
+      v0[e] = silu_rcp(o0[e]);
+      v1[e] = silu_rcp(o1[e]);
     }
     auto lo = __builtin_amdgcn_permlane16_swap(pack_bf16x2(v0[0], v0[1]), pack_bf16x2(v1[0], v1[1]), false, false);
     auto hi = __builtin_amdgcn_permlane16_swap(pack_bf16x2(v0[2], v0[3]), pack_bf16x2(v1[2], v1[3]), false, false);

@@ -24,12 +24,6 @@
 #include "common.h"
 UPA_STAMP_DEFINE(c2f)
 
-typedef __attribute__((address_space(1))) const void* cgptr_t;
-typedef __attribute__((address_space(3))) void* clptr_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-__device__ __attribute__((aligned(16))) unsigned g_c2f_zero16[4] = {0u, 0u, 0u, 0u};
-
 struct C2fParams {
   const char* x; char* y;
   const char *w1, *wa, *wb, *w2;
@@ -53,14 +47,6 @@ constexpr int Y1_BYTES = XH * Y1P * 32;      // 16640
 constexpr int MT_B = (MPX + 15) / 16;        // 21 m-tiles of t
 constexpr int TS_BYTES = MT_B * 16 * 32;     // 10752
 constexpr int LDS = XS_BYTES + Y1_BYTES + TS_BYTES;
-
-__device__ __forceinline__ float silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-__device__ __forceinline__ f32x4 mfma32(const u32x4& a, const u32x4& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(&a), *reinterpret_cast<const bf16x8*>(&b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16(const u32x2& a, const u32x2& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(*reinterpret_cast<const s16x4*>(&a), *reinterpret_cast<const s16x4*>(&b), c, 0, 0, 0);
-}
 }  // namespace c2f
 
 // NW waves per workgroup: 4 (84 VGPRs, three workgroups per CU = three waves per SIMD; the default) or 8 (107 VGPRs, two
@@ -93,10 +79,10 @@ __global__ __launch_bounds__(NW * 64) void c2f16_fused_kernel(const C2fParams p)
     const int px = item >> 2, slot = item & 3;
     const int hy = px / XW, hx = px - hy * XW;
     const int iy = oy0 - 2 + hy, ix = ox0 - 2 + hx;
-    const char* src = reinterpret_cast<const char*>(g_c2f_zero16);
+    const char* src = reinterpret_cast<const char*>(g_zero16);
     if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W)
       src = p.x + (((size_t)n * p.H + iy) * p.W + ix) * (size_t)p.ldx * 2 + slot * 16;
-    __builtin_amdgcn_global_load_lds((cgptr_t)src, (clptr_t)(xs + (it * NTH + wave * 64) * 16), 16, 0, 0);
+    lds_dma16(src, xs + (it * NTH + wave * 64) * 16);
   }
 
   // ---- weights -> registers while the tile is in flight.  Packed layout: [tap][k-tile][n-tile][lane (g, r)][16 B], lane (g, r) =
@@ -152,7 +138,7 @@ __global__ __launch_bounds__(NW * 64) void c2f16_fused_kernel(const C2fParams p)
       }
       float v[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = in ? silu(acc[e]) : 0.f;
+      for (int e = 0; e < 4; ++e) v[e] = in ? silu_rcp(acc[e]) : 0.f;
       *reinterpret_cast<u32x2*>(y1s + (hy * Y1P + hx) * 32 + g * 8) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
     }
     __syncthreads();
@@ -173,7 +159,7 @@ __global__ __launch_bounds__(NW * 64) void c2f16_fused_kernel(const C2fParams p)
       }
       float v[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = in ? silu(acc[e]) : 0.f;
+      for (int e = 0; e < 4; ++e) v[e] = in ? silu_rcp(acc[e]) : 0.f;
       *reinterpret_cast<u32x2*>(ts + q * 32 + g * 8) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
     }
     __syncthreads();
@@ -191,13 +177,13 @@ __global__ __launch_bounds__(NW * 64) void c2f16_fused_kernel(const C2fParams p)
     for (int s = 0; s < 5; ++s) acc = mfma32(w_b[s], *reinterpret_cast<const u32x4*>(base + offC[s]), acc);
     const int cpx = (i + 2) * XW + r + 2;  // this pixel in the x halo tile
     const u32x2 y1c = *reinterpret_cast<const u32x2*>(y1s + ((i + 2) * Y1P + r + 2) * 32 + g * 8);
-    const float bv0 = silu(acc[0]) + __uint_as_float(y1c[0] << 16);
-    const float bv1 = silu(acc[1]) + __uint_as_float(y1c[0] & 0xFFFF0000u);
-    const float bv2 = silu(acc[2]) + __uint_as_float(y1c[1] << 16);
-    const float bv3 = silu(acc[3]) + __uint_as_float(y1c[1] & 0xFFFF0000u);
+    const float bv0 = silu_rcp(acc[0]) + __uint_as_float(y1c[0] << 16);
+    const float bv1 = silu_rcp(acc[1]) + __uint_as_float(y1c[0] & 0xFFFF0000u);
+    const float bv2 = silu_rcp(acc[2]) + __uint_as_float(y1c[1] << 16);
+    const float bv3 = silu_rcp(acc[3]) + __uint_as_float(y1c[1] & 0xFFFF0000u);
     const u32x2 bB = u32x2{pack_bf16x2(bv0, bv1), pack_bf16x2(bv2, bv3)};
     const f32x4 a0 = mfma32(w_y0, *reinterpret_cast<const u32x4*>(xs + cpx * 64 + g * 16), bias_y0);
-    const u32x2 y0B = u32x2{pack_bf16x2(silu(a0[0]), silu(a0[1])), pack_bf16x2(silu(a0[2]), silu(a0[3]))};
+    const u32x2 y0B = u32x2{pack_bf16x2(silu_rcp(a0[0]), silu_rcp(a0[1])), pack_bf16x2(silu_rcp(a0[2]), silu_rcp(a0[3]))};
     f32x4 o[2];
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
@@ -208,8 +194,8 @@ __global__ __launch_bounds__(NW * 64) void c2f16_fused_kernel(const C2fParams p)
     float v0[4], v1[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      v0[e] = silu(o[0][e]);
-      v1[e] = silu(o[1][e]);
+      v0[e] = silu_rcp(o[0][e]);
+      v1[e] = silu_rcp(o[1][e]);
     }
     auto lo = __builtin_amdgcn_permlane16_swap(pack_bf16x2(v0[0], v0[1]), pack_bf16x2(v1[0], v1[1]), false, false);
     auto hi = __builtin_amdgcn_permlane16_swap(pack_bf16x2(v0[2], v0[3]), pack_bf16x2(v1[2], v1[3]), false, false);
@@ -252,8 +238,6 @@ struct C2f32Params {
 };
 
 namespace c2f32 {
-using c2f::mfma32;
-using c2f::silu;
 constexpr int T = 16;
 constexpr int NW = 16;  // waves per workgroup
 __device__ __forceinline__ int swz64(int px) { return (px >> 1) & 3; }  // 64-byte pixel records: 4 groups of 16 B
@@ -296,7 +280,7 @@ __device__ __forceinline__ void conv3x3_stage(const char* src, char* dst, const 
     const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
     float v[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = in ? silu(acc[e]) : 0.f;
+    for (int e = 0; e < 4; ++e) v[e] = in ? silu_rcp(acc[e]) : 0.f;
     if (res) {  // the shortcut tensor is zero outside the image already
       const u32x2 rr = *reinterpret_cast<const u32x2*>(res + quad_addr((yy + OFF) * SR + xx + OFF, j, g));
       v[0] += __uint_as_float(rr[0] << 16); v[1] += __uint_as_float(rr[0] & 0xFFFF0000u);
@@ -360,9 +344,9 @@ __global__ __launch_bounds__(1024) void c2f32_fused_kernel(const C2f32Params p) 
         const int cg = slot ^ (px & 7);
         const int hy = px / SX, hx = px - hy * SX;
         const int iy = oy0 - R + hy, ix = ox0 - R + hx;
-        const char* src = reinterpret_cast<const char*>(g_c2f_zero16);
+        const char* src = reinterpret_cast<const char*>(g_zero16);
         if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) src = p.x + ((((size_t)n * p.H + iy) * p.W + ix) * (size_t)p.ldx + cg * 8) * 2;
-        __builtin_amdgcn_global_load_lds((cgptr_t)src, (clptr_t)(xs + (it * 1024 + wave * 64) * 16), 16, 0, 0);
+        lds_dma16(src, xs + (it * 1024 + wave * 64) * 16);
       }
     }
     // cv1 (64 -> 64: [2 k-tiles][4 n-tiles]): this wave's n-tiles j (y0) and 2 + j (y1); the first 3x3 conv's fragments
@@ -392,7 +376,7 @@ __global__ __launch_bounds__(1024) void c2f32_fused_kernel(const C2f32Params p) 
       const bool in = gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
       float v[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = in ? silu(a[e]) : 0.f;
+      for (int e = 0; e < 4; ++e) v[e] = in ? silu_rcp(a[e]) : 0.f;
       *reinterpret_cast<u32x2*>(y1s + quad_addr(q, j, g)) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
     }
     for (int i = wave >> 1; i < TH; i += NW / 2) {
@@ -401,7 +385,7 @@ __global__ __launch_bounds__(1024) void c2f32_fused_kernel(const C2f32Params p) 
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt)
         a = mfma32(w1f[kt][0], *reinterpret_cast<const u32x4*>(xs + q * 128 + (((kt * 4 + g) ^ (q & 7)) << 4)), a);
-      *reinterpret_cast<u32x2*>(y0s + quad_addr(i * T + r, j, g)) = u32x2{pack_bf16x2(silu(a[0]), silu(a[1])), pack_bf16x2(silu(a[2]), silu(a[3]))};
+      *reinterpret_cast<u32x2*>(y0s + quad_addr(i * T + r, j, g)) = u32x2{pack_bf16x2(silu_rcp(a[0]), silu_rcp(a[1])), pack_bf16x2(silu_rcp(a[2]), silu_rcp(a[3]))};
     }
   } else {
     // ---- cv1 over nch 64-channel chunks of the input (c1 = 64 nch; yolov8n model.15: 192 = upsampled 128 + skip 64).  Two chunk
@@ -429,8 +413,8 @@ __global__ __launch_bounds__(1024) void c2f32_fused_kernel(const C2f32Params p) 
       for (int it = 0; it < XIT; ++it) {
         if (it * 1024 + wave * 64 < XITEMS) {
           const char* src = xoff[it] != 0xffffffffu ? base + (size_t)(fromUp ? uoff[it] : xoff[it]) + c * 128
-                                                    : reinterpret_cast<const char*>(g_c2f_zero16);
-          __builtin_amdgcn_global_load_lds((cgptr_t)src, (clptr_t)(buf + (it * 1024 + wave * 64) * 16), 16, 0, 0);
+                                                    : reinterpret_cast<const char*>(g_zero16);
+          lds_dma16(src, buf + (it * 1024 + wave * 64) * 16);
         }
       }
     };
@@ -493,7 +477,7 @@ __global__ __launch_bounds__(1024) void c2f32_fused_kernel(const C2f32Params p) 
       const bool in = gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
       float v[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = in ? silu(acc1[k][e]) : 0.f;
+      for (int e = 0; e < 4; ++e) v[e] = in ? silu_rcp(acc1[k][e]) : 0.f;
       *reinterpret_cast<u32x2*>(y1s + quad_addr(q, j, g)) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
     }
 #pragma unroll
@@ -501,7 +485,7 @@ __global__ __launch_bounds__(1024) void c2f32_fused_kernel(const C2f32Params p) 
       const int i = (wave >> 1) + k * (NW / 2);
       if (i >= TH) break;  // uniform
       *reinterpret_cast<u32x2*>(y0s + quad_addr(i * T + r, j, g)) =
-          u32x2{pack_bf16x2(silu(acc0[k][0]), silu(acc0[k][1])), pack_bf16x2(silu(acc0[k][2]), silu(acc0[k][3]))};
+          u32x2{pack_bf16x2(silu_rcp(acc0[k][0]), silu_rcp(acc0[k][1])), pack_bf16x2(silu_rcp(acc0[k][2]), silu_rcp(acc0[k][3]))};
     }
   }
   load_w9(wB, p.wm[1], j, lane);  // every later stage's weights are fetched one stage ahead
@@ -568,8 +552,8 @@ __global__ __launch_bounds__(1024) void c2f32_fused_kernel(const C2f32Params p) 
     float v0[4], v1[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      v0[e] = silu(o0[e]);
-      v1[e] = silu(o1[e]);
+      v0[e] = silu_rcp(o0[e]);
+      v1[e] = silu_rcp(o1[e]);
     }
     auto lo = __builtin_amdgcn_permlane16_swap(pack_bf16x2(v0[0], v0[1]), pack_bf16x2(v1[0], v1[1]), false, false);
     auto hi = __builtin_amdgcn_permlane16_swap(pack_bf16x2(v0[2], v0[3]), pack_bf16x2(v1[2], v1[3]), false, false);

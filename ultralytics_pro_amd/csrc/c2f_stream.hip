@@ -22,10 +22,6 @@
 
 #include "common.h"
 
-typedef __attribute__((address_space(1))) const void* cgptr_t;
-typedef __attribute__((address_space(3))) void* clptr_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
 struct C2fsParams {
   const char* x; char* y;
   const char *w1, *w2;
@@ -88,31 +84,9 @@ struct Geo {
   static constexpr int LDS = BIAS + NST * 32 * 4;
 };
 
-#if defined(C2FS_EXP) && (C2FS_EXP == 11 || C2FS_EXP == 15)   // timing experiments only (tools/experiments/r05_c2fs_variants.sh): not SiLU
-__device__ __forceinline__ float silu(float v) { return v * 0.5f; }
-#elif defined(C2FS_EXP) && C2FS_EXP == 12
-__device__ __forceinline__ float silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + v * v); }
-#else
-__device__ __forceinline__ float silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-#endif
-__device__ __forceinline__ f32x4 mfma32(const u32x4& a, const u32x4& b, f32x4 c) {
-#if defined(C2FS_EXP) && (C2FS_EXP == 13 || C2FS_EXP == 15)  // timing experiment: no matrix instructions (operands still loaded)
-  asm volatile("" ::"v"(a), "v"(b));
-  return c;
-#endif
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(&a), *reinterpret_cast<const bf16x8*>(&b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16(const u32x2& a, const u32x2& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(*reinterpret_cast<const s16x4*>(&a), *reinterpret_cast<const s16x4*>(&b), c, 0, 0, 0);
-}
 __device__ __forceinline__ u32x2 silu_pack(const f32x4& a) {
-  return u32x2{pack_bf16x2(silu(a[0]), silu(a[1])), pack_bf16x2(silu(a[2]), silu(a[3]))};
+  return u32x2{pack_bf16x2(silu_rcp(a[0]), silu_rcp(a[1])), pack_bf16x2(silu_rcp(a[2]), silu_rcp(a[3]))};
 }
-#if defined(C2FS_EXP) && C2FS_EXP == 14  // timing experiment: no LDS reads of the 3x3 taps / cv2 operands
-__device__ __forceinline__ u32x4 lds128(const char* sm, int off) { return u32x4{(unsigned)off, 1u, 2u, 3u}; }
-#else
-__device__ __forceinline__ u32x4 lds128(const char* sm, int off) { return *reinterpret_cast<const u32x4*>(sm + off); }
-#endif
 
 // ---- a 3x3 stage K: the wave owns unit `unit` (and unit + 1 if TWO) of the stage's RS-row band for the life of the workgroup.
 // A unit = 16 consecutive pixels of the band (row-major over the stage's SD valid columns) x all 32 output channels.
@@ -194,7 +168,7 @@ __device__ __forceinline__ void stage_role(const C2fsParams& p, char* sm, int un
         const unsigned m = (gy >= 0 && gy < p.H) ? u_colm[u] : 0u;  // the tensor is ZERO outside the image (the next conv's padding)
         float v0[4], v1[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { v0[e] = silu(acc0[e]); v1[e] = silu(acc1[e]); }
+        for (int e = 0; e < 4; ++e) { v0[e] = silu_rcp(acc0[e]); v1[e] = silu_rcp(acc1[e]); }
         if (use_res) {
           v0[0] += __uint_as_float(rs0[0] << 16); v0[1] += __uint_as_float(rs0[0] & 0xFFFF0000u);
           v0[2] += __uint_as_float(rs0[1] << 16); v0[3] += __uint_as_float(rs0[1] & 0xFFFF0000u);
@@ -292,7 +266,8 @@ __device__ __forceinline__ void y_role(const C2fsParams& p, char* sm, int yi, in
     for (int i = 0; i < PCS; ++i) {
       if (!d_ok[i] || !(d_isf[i] ? fon : yon)) continue;  // wave-uniform
       const unsigned off = d_col[i] + (d_isf[i] ? (d_rr[i] ? fro[1] : fro[0]) : (d_rr[i] ? yro[1] : yro[0]));
-      __builtin_amdgcn_global_load_lds((cgptr_t)(ximg + off), (clptr_t)(sm + d_dst[i] + slot * (d_isf[i] ? G::FSLOT : G::XSLOT)), 16, 0, 0);
+      // (the builtin spelled out: through lds_dma16 hipcc schedules this kernel differently; kept instruction-identical)
+      __builtin_amdgcn_global_load_lds((gptr_t)(ximg + off), (lptr_t)(sm + d_dst[i] + slot * (d_isf[i] ? G::FSLOT : G::XSLOT)), 16, 0, 0);
       ++issued;
     }
     return issued;
@@ -419,12 +394,7 @@ __device__ __forceinline__ void f_role(const C2fsParams& p, char* sm, int fu, in
       o1 = mfma16(w2y0[0][1], y0B[0], o1);
       o0 = mfma16(w2y0[1][0], y0B[1], o0);
       o1 = mfma16(w2y0[1][1], y0B[1], o1);
-      // A 4-pass 16x16x16 MFMA whose result is the NEXT instruction's srcC of an 8-pass 16x16x32 MFMA came out wrong in rows 2, 3
-      // of each lane's four (measured, ROCm 7.2 / gfx950: hipcc inserts no wait states between the two shapes on one accumulator):
-      // finish the 16-wide chains first, then wait out the short pipeline before the 32-wide chains start.
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_nop 15" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
+      mfma_shape_fence();  // the 16-wide chains are finished; the 32-wide ones continue on the same accumulators
 #pragma unroll
       for (int k = 0; k < 1 + NB; ++k) {
         o0 = mfma32(w2f[k][0], opnd[k], o0);
@@ -626,7 +596,7 @@ __device__ __forceinline__ void dma_role(const C2fsParams& p, char* sm, int di, 
       for (int i = 0; i < G1::PPW; ++i) {
         if (!d_ok[i]) continue;  // wave-uniform
         const char* src = d_up[i] ? uimg + (d_col[i] + (d_rr[i] ? uro[1] : uro[0])) : ximg + (d_col[i] + (d_rr[i] ? xro[1] : xro[0]));
-        __builtin_amdgcn_global_load_lds((cgptr_t)src, (clptr_t)(sm + d_dst[i] + slot * G1::XSLOT1), 16, 0, 0);
+        lds_dma16(src, sm + d_dst[i] + slot * G1::XSLOT1);
         ++issued;
       }
     }
@@ -786,17 +756,6 @@ __global__ __launch_bounds__(1024) void c2f32_stream2_kernel(const C2fsParams p)
   }
 }
 
-// CUs of the current device (C++11 static initialisation: thread safe; 0 = the query failed)
-static int c2fs_cus() {
-  static const int cus = [] {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 0;
-    return pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
-  }();
-  return cus;
-}
-
 // rows per part for an (n, h, w) problem: one round of workgroups if possible, as few steps as possible
 static int c2fs_pick_rows(int n, int h, int w, int cus) {
   const int strips = cdiv(w, c2fs::WS);
@@ -818,8 +777,7 @@ int upa_c2f32_stream_launch(const void* x, int n, int h, int w, int ldx, int sho
                             const void* const* wm, const float* const* bm, const void* w2, const float* b2, void* y, int ldy,
                             const upa_opts* opts, hipStream_t s) {
   if ((long)n * h * w * (long)(ldx > ldy ? ldx : ldy) * 2 >= (1L << 31) || (long)w * ldx * 2 >= (1L << 24)) return UPA_EUNSUPPORTED;
-  const int cus = c2fs_cus();
-  if (!cus) return UPA_ELAUNCH;
+  const int cus = upa_num_cus();
   C2fsParams p;
   memset(&p, 0, sizeof(p));
   p.x = (const char*)x; p.y = (char*)y; p.w1 = (const char*)w1; p.w2 = (const char*)w2; p.b1 = b1; p.b2 = b2;
@@ -860,8 +818,7 @@ int upa_c2f32_stream1_launch(const void* x, int n, int h, int w, int c1, int ldx
   if (c1 % 64 != 0 || nch < 1 || nch > 3 || (up && (up_c % 64 != 0 || (h & 1) || (w & 1)))) return UPA_EUNSUPPORTED;
   const long ldm = ldx > ldy ? (ldx > up_ld ? ldx : up_ld) : (ldy > up_ld ? ldy : up_ld);
   if ((long)n * h * w * ldm * 2 >= (1L << 31) || (long)w * ldm * 2 >= (1L << 24)) return UPA_EUNSUPPORTED;
-  const int cus = c2fs_cus();
-  if (!cus) return UPA_ELAUNCH;
+  const int cus = upa_num_cus();
   C2fsParams p;
   memset(&p, 0, sizeof(p));
   p.x = (const char*)x; p.y = (char*)y; p.w1 = (const char*)w1; p.w2 = (const char*)w2; p.b1 = b1; p.b2 = b2;

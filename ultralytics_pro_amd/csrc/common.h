@@ -11,6 +11,8 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 typedef unsigned short bf16_t;  // raw bf16 bits
 
@@ -78,6 +80,53 @@ __device__ __forceinline__ float apply_act(float v, int act) {
   if (act == UPA_ACT_RELU) return fmaxf(v, 0.0f);
   return v;
 }
+
+// ---- gfx950 primitives shared by the kernel files: LDS-DMA, MFMA wrappers, LDS reads, the fast activations ----
+// Two SiLU forms exist on purpose.  silu_f / apply_act above divide (v / (1 + __expf(-v)), the IEEE divide sequence): dwconv.hip,
+// whose f32 and bf16 instantiations share one epilogue.  silu_rcp / act_rcp below multiply by v_rcp_f32 (1 ulp, one instruction):
+// every bf16 MFMA kernel - the conv*, c2f*, stem and Detect epilogues - whose results are rounded to bf16 anyway.  (The f32 parity
+// paths spell their own expf-and-divide.)  The two differ in the last bit, so a call site never switches form.
+__device__ __forceinline__ float silu_rcp(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
+template <int ACT>
+__device__ __forceinline__ float act_rcp(float v) {
+  if constexpr (ACT == UPA_ACT_SILU) return silu_rcp(v);
+  else if constexpr (ACT == UPA_ACT_RELU) return fmaxf(v, 0.0f);
+  else return v;
+}
+
+// LDS-DMA: every lane's 16 bytes at src go to dst + lane * 16 (dst is wave-uniform), without passing through registers
+typedef __attribute__((address_space(1))) const void* gptr_t;
+typedef __attribute__((address_space(3))) void* lptr_t;
+__device__ __forceinline__ void lds_dma16(const void* src, void* dst) { __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0); }
+// Zero bytes in device memory: the source of every out-of-image / padded-channel 16-byte group of an LDS-DMA (a lane cannot skip
+// its share of the instruction).  One aligned 64-byte line.  An inline variable: every code object that uses it carries its own
+// (weak) copy, addressed pc-relative exactly as a file-local global is.
+inline __device__ __attribute__((aligned(64))) unsigned g_zero16[16] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+
+__device__ __forceinline__ f32x4 mfma32(const u32x4& a, const u32x4& b, f32x4 c) {  // 16x16x32 bf16
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(&a), *reinterpret_cast<const bf16x8*>(&b), c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 mfma16(const u32x2& a, const u32x2& b, f32x4 c) {  // 16x16x16 bf16
+  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(*reinterpret_cast<const s16x4*>(&a), *reinterpret_cast<const s16x4*>(&b), c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 mfma32x32(const u32x4& a, const u32x4& b, f32x16 c) {  // 32x32x16 bf16
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&a), *reinterpret_cast<const bf16x8*>(&b), c, 0, 0, 0);
+}
+// Between MFMA shapes on ONE accumulator chain.  A 4-pass 16x16x16 MFMA whose result is the next instruction's srcC of an 8-pass
+// 16x16x32 MFMA (or the other way round) comes out wrong in half of each lane's four rows: hipcc inserts no wait states between the
+// two shapes (measured, ROCm 7.2 / gfx950; README.md, round 5; profiles/r05_valu_issue_rates.txt; tools/experiments/mfma_shape_hazard.hip).
+// Finish the chain of one shape, call this, then start the other: it waits out the short pipeline and keeps the scheduler from
+// moving an MFMA across.
+__device__ __forceinline__ void mfma_shape_fence() {
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_nop 15" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ u32x4 lds128(const char* sm, int off) { return *reinterpret_cast<const u32x4*>(sm + off); }
+__device__ __forceinline__ u32x2 lds64(const char* sm, int off) { return *reinterpret_cast<const u32x2*>(sm + off); }
+
+// CUs of the current device, queried once (runtime.hip); 256 - an MI355X - if the query fails.  Host side.
+int upa_num_cus();
 
 // Raise a kernel's dynamic-LDS limit to the whole 160 KB of a gfx950 CU (less its static __shared__), once per kernel instantiation (C++11 static
 // initialisation: thread safe, no API call on later launches, and no launch ever lowers a limit another launch - or a

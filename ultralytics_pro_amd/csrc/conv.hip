@@ -53,17 +53,12 @@ struct ConvParams {
   const upa_opts* opts;  // HOST side only (dispatch overrides of this call); never read by a kernel
 };
 
-// 16 zero bytes in device memory: source of every out-of-image / padded-channel 16-byte group of the halo DMA
-__device__ __attribute__((aligned(16))) unsigned g_zero16[4] = {0u, 0u, 0u, 0u};
-
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 template <bool PRECISE, int ACT>
 __device__ __forceinline__ float act_fn(float v) {
   if constexpr (ACT == UPA_ACT_SILU) {
     if constexpr (PRECISE) return v / (1.0f + expf(-v));  // ocml expf (<= 1 ulp) + IEEE divide: f32 parity mode
-    return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));  // bf16 perf mode: v_exp_f32 + v_rcp_f32 (1 ulp), no IEEE divide
+    return silu_rcp(v);  // bf16 perf mode: v_exp_f32 + v_rcp_f32 (1 ulp), no IEEE divide
   } else if constexpr (ACT == UPA_ACT_RELU) {
     return fmaxf(v, 0.0f);
   } else {
@@ -230,7 +225,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_igemm_kernel(const ConvParam
         const char* src = reinterpret_cast<const char*>(g_zero16);
         if (idx < haloItems && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W && ch < p.Cin && !UPA_ABL(p, 1))
           src = p.x + ((((size_t)n * p.H + iy) * p.W + ix) * (size_t)p.ldx + ch) * ES;
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + wbase * 16), 16, 0, 0);
+        lds_dma16(src, smem + wbase * 16);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -466,7 +461,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_ws_kernel(const ConvParams p
       const int nt = ntb0 + (within >> 6);
       const char* src = (nt < p.NTn) ? p.w + (((size_t)seg * p.NTn + ntb0) * 64 + within) * 16
                                      : reinterpret_cast<const char*>(g_zero16);
-      __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(wsm + base * 16), 16, 0, 0);
+      lds_dma16(src, wsm + base * 16);
     }
   }
   auto stage = [&](int tile, char* dst) {
@@ -487,7 +482,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_ws_kernel(const ConvParams p
       const char* src = reinterpret_cast<const char*>(g_zero16);
       if (idx < haloItems && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W && ch < p.Cin)
         src = p.x + ((((size_t)n * p.H + iy) * p.W + ix) * (size_t)p.ldx + ch) * ES;
-      __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(dst + base * 16), 16, 0, 0);
+      lds_dma16(src, dst + base * 16);
     }
   };
 
@@ -754,12 +749,7 @@ int launch_ws(ConvParams& p, hipStream_t stream, int query_only, int* variant) {
   p.numTiles = p.tilesX * p.tilesY * p.N;
   p.wsNTB = NTB;
   const int gridY = cdiv(p.NTn, NTB);
-  static int numCU = 0;
-  if (!numCU) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&numCU, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || numCU <= 0) numCU = 256;
-  }
+  const int numCU = upa_num_cus();
   int perCU = (int)((160 * 1024) / lds);  // co-resident workgroups per CU (LDS-limited), capped by the wave slots
   if (perCU > 4) perCU = 4;
   // measured on MI355X: with one workgroup per CU (4 waves, nothing to overlap the epilogue / LDS latency with) the

@@ -23,11 +23,6 @@
 #include "common.h"
 #include "conv_pipe.h"
 
-typedef __attribute__((address_space(1))) const void* c1gptr_t;
-typedef __attribute__((address_space(3))) void* c1lptr_t;
-
-__device__ __attribute__((aligned(16))) unsigned g_c1_zero16[4] = {0u, 0u, 0u, 0u};
-
 namespace {
 // stages of the wave-private input ring: two stages (of MT KiB) are in flight per wave while the third is multiplied.
 // Measured on MI355X (bs 32 yolov8n layers): 4 stages at MT 2 and 8 at MT 1 were slower wherever the bigger ring cost a
@@ -106,8 +101,8 @@ __global__ __launch_bounds__(WAVES * 64) void conv1x1_stream_kernel(const C1Para
 #pragma unroll
       for (int i = 0; i < MT; ++i) {
         const char* src = (chok && ioff[i] != 0xffffffffu && !UPA_ABL(p, 1)) ? xk + (fromUp ? uoff[i] : ioff[i])
-                                                                            : reinterpret_cast<const char*>(g_c1_zero16);
-        __builtin_amdgcn_global_load_lds((c1gptr_t)src, (c1lptr_t)(ring + (stage * MT + i) * 1024), 16, 0, 0);
+                                                                            : reinterpret_cast<const char*>(g_zero16);
+        lds_dma16(src, ring + (stage * MT + i) * 1024);
       }
       seq += MT;
       if (++ikt == p.KTT) {
@@ -140,7 +135,7 @@ __global__ __launch_bounds__(WAVES * 64) void conv1x1_stream_kernel(const C1Para
   auto epilogue = [&](int g, auto act_tag) __attribute__((always_inline)) {
     constexpr int ACT = decltype(act_tag)::value;
     auto act = [](float v) __attribute__((always_inline)) {
-      if constexpr (ACT == UPA_ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
+      if constexpr (ACT == UPA_ACT_SILU) return silu_rcp(v);
       else return v;
     };
     const int co0 = nt0 * 16;
@@ -271,9 +266,9 @@ __global__ __launch_bounds__(WAVES * 64) void conv1x1_stream_kernel(const C1Para
   // ---- weight slice -> LDS (once per workgroup); n-tiles past the packed weights read zeros
   for (int q = wave; q < p.KTT * NTW; q += WAVES) {
     const int kt = q / NTW, j = q - kt * NTW;
-    const char* src = reinterpret_cast<const char*>(g_c1_zero16);
+    const char* src = reinterpret_cast<const char*>(g_zero16);
     if (nt0 + j < p.NTn && !UPA_ABL(p, 2)) src = p.w + ((size_t)(kt * p.NTn + nt0 + j) * 1024 + lane * 16);
-    __builtin_amdgcn_global_load_lds((c1gptr_t)src, (c1lptr_t)(wl + q * 1024), 16, 0, 0);
+    lds_dma16(src, wl + q * 1024);
   }
   // bias slice -> LDS (read back per epilogue: keeps NTW*4 registers free for the accumulators)
   if (threadIdx.x < NTW * 16) {
@@ -384,12 +379,7 @@ static int c1_launch(C1Params p, int n_pixels, int query_only, int* variant, int
   const int gridY = (p.NTn + ntw - 1) / ntw;
   const size_t wbytes = (size_t)p.KTT * ntw * 1024;
   const int tiles = (p.P + 15) / 16;
-  static int numCU = 0;
-  if (!numCU) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&numCU, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || numCU <= 0) numCU = 256;
-  }
+  const int numCU = upa_num_cus();
   // pixel tiles per wave and step: enough groups that every SIMD of the chip has a few to pipeline
   const int f_mt = UPA_OPT(opts, c1_mt), f_waves = UPA_OPT(opts, c1_waves), f_wgs = UPA_OPT(opts, c1_wgs);  // tuning / tests
   int mt = tiles >= 8192 ? 4 : (tiles >= 2048 ? 2 : 1);

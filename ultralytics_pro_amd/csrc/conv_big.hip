@@ -37,20 +37,6 @@
 #include "conv_pipe.h"
 UPA_STAMP_DEFINE(conv_big)
 
-typedef __attribute__((address_space(1))) const void* bgptr_t;
-typedef __attribute__((address_space(3))) void* blptr_t;
-
-__device__ __attribute__((aligned(16))) unsigned g_big_zero16[4] = {0u, 0u, 0u, 0u};
-
-namespace {
-template <int ACT>
-__device__ __forceinline__ float big_act(float v) {
-  if constexpr (ACT == UPA_ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-  else if constexpr (ACT == UPA_ACT_RELU) return fmaxf(v, 0.0f);
-  else return v;
-}
-}  // namespace
-
 // TAIL != 0 (Detect branches, WN = 1 so that a wave holds every channel of its pixels): the SiLU'd result of this 3x3 conv is
 // not stored but fed, from the accumulators, into the branch's final 1x1 conv and that conv's half of the decode - see the
 // tail section below.  TAIL 1 = box branch (DFL + dist2bbox), 2 = class branch (sigmoid).
@@ -130,10 +116,10 @@ __device__ __forceinline__ void conv_big_body(const BigParams& p, const int bid0
       if constexpr (STRIDE == 2) px = qx < p.HALF ? 2 * qx : 2 * (qx - p.HALF) + 1;
       const int iy = iy0 + py, ix = ix0 + px;
       const int ch = c0 + cg * 8;
-      const char* src = reinterpret_cast<const char*>(g_big_zero16);
+      const char* src = reinterpret_cast<const char*>(g_zero16);
       if (idx < haloItems && px < p.IW && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W && ch < p.Cin)
         src = p.x + ((((size_t)n * p.H + iy) * p.W + ix) * (size_t)p.ldx + ch) * 2;
-      __builtin_amdgcn_global_load_lds((bgptr_t)src, (blptr_t)(hal + base * 16), 16, 0, 0);
+      lds_dma16(src, hal + base * 16);
     }
   };
   // weight slab of (tap, chunk c) -> buffer b: fragment f = kt * NTB + j (f < 2 * NTB); wave w brings fragments w, w + 8, ...
@@ -145,9 +131,9 @@ __device__ __forceinline__ void conv_big_body(const BigParams& p, const int bid0
         const int kt = f / NTB, j = f - kt * NTB;  // NTB is a compile-time constant
         const int ktg = c * 2 + kt;
         const int nt = ntb0 + j;
-        const char* src = reinterpret_cast<const char*>(g_big_zero16);
+        const char* src = reinterpret_cast<const char*>(g_zero16);
         if (ktg < p.KTT && nt < p.NTn) src = p.w + (((size_t)(tap * p.KTT + ktg) * p.NTn + nt) * 64 + lane) * 16;
-        __builtin_amdgcn_global_load_lds((bgptr_t)src, (blptr_t)(wbuf + b * WBUF + f * 1024), 16, 0, 0);
+        lds_dma16(src, wbuf + b * WBUF + f * 1024);
       }
     }
   };
@@ -252,8 +238,8 @@ __device__ __forceinline__ void conv_big_body(const BigParams& p, const int bid0
         float v0[4], v1[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          v0[q] = big_act<UPA_ACT_SILU>(acc[i][2 * s2][q] + bv[2 * s2][q]);
-          v1[q] = big_act<UPA_ACT_SILU>(acc[i][2 * s2 + 1][q] + bv[2 * s2 + 1][q]);
+          v0[q] = act_rcp<UPA_ACT_SILU>(acc[i][2 * s2][q] + bv[2 * s2][q]);
+          v1[q] = act_rcp<UPA_ACT_SILU>(acc[i][2 * s2 + 1][q] + bv[2 * s2 + 1][q]);
         }
         hb[i] = u32x4{pack_bf16x2(v0[0], v0[1]), pack_bf16x2(v0[2], v0[3]), pack_bf16x2(v1[0], v1[1]), pack_bf16x2(v1[2], v1[3])};
       }
@@ -277,7 +263,7 @@ __device__ __forceinline__ void conv_big_body(const BigParams& p, const int bid0
       for (int i = 0; i < MT; ++i) {
         float v0[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) v0[q] = big_act<UPA_ACT_SILU>(acc[i][j0][q] + bv[j0][q]);
+        for (int q = 0; q < 4; ++q) v0[q] = act_rcp<UPA_ACT_SILU>(acc[i][j0][q] + bv[j0][q]);
         hh[i] = u32x2{pack_bf16x2(v0[0], v0[1]), pack_bf16x2(v0[2], v0[3])};
       }
 #pragma unroll
@@ -417,8 +403,8 @@ __device__ __forceinline__ void conv_big_body(const BigParams& p, const int bid0
         float v0[4], v1[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          v0[q] = big_act<ACT>(acc[i][j][q] + bj0[q]);
-          v1[q] = big_act<ACT>(acc[i][j + 1][q] + bj1[q]);
+          v0[q] = act_rcp<ACT>(acc[i][j][q] + bj0[q]);
+          v1[q] = act_rcp<ACT>(acc[i][j + 1][q] + bj1[q]);
         }
         bool ok = pok && cw + cb < p.Cout;
         char* dst = yrow + cb * 2;
@@ -462,7 +448,7 @@ __device__ __forceinline__ void conv_big_body(const BigParams& p, const int bid0
         float v[4];
         const f32x4 bj = LAZY_BIAS ? bias_of(j) : biasv[LAZY_BIAS ? 0 : j];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = big_act<ACT>(acc[i][j][q] + bj[q]);
+        for (int q = 0; q < 4; ++q) v[q] = act_rcp<ACT>(acc[i][j][q] + bj[q]);
         if (pok && cw + cb < p.Cout) {
           if (p.res) {
             const u32x2 rv = *reinterpret_cast<const u32x2*>(rrow + cb * 2);
@@ -528,16 +514,6 @@ __global__ __launch_bounds__(512, 4) void conv_big_mix_kernel(const BigParams a0
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
-int big_num_cu() {
-  static int numCU = 0;
-  if (!numCU) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&numCU, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || numCU <= 0) numCU = 256;
-  }
-  return numCU;
-}
-
 // Tile shape for a BM-pixel workgroup: fewest tiles per image first (least padding waste), then the smallest halo; the
 // halo of a 64-channel chunk plus the two weight buffers must fit `lds_cap` bytes.  Returns false if nothing fits.
 // LDS geometry of the halo image for a TH x TW tile: valid size IH x IW, column slots (stride 2: de-interleaved halves of
@@ -742,7 +718,7 @@ int branch_tail_prepare(BigParams& p, int& ntb, int& bm, size_t& lds, const void
   p.de.keys_only = (p.de.best_keys && UPA_OPT(opts, keys_only)) ? 1 : 0;
   p.no_xcd = UPA_OPT(opts, no_xcd);
   const long px = (long)n * h * w;
-  bm = (px + 255) / 256 < big_num_cu() ? 128 : 256;  // 128-pixel workgroups (one m-tile per wave) on the small levels
+  bm = (px + 255) / 256 < upa_num_cus() ? 128 : 256;  // 128-pixel workgroups (one m-tile per wave) on the small levels
   if (const int f = UPA_OPT(opts, branch_tail_bm); f == 128 || f == 256) bm = f;
   if (!big_pick_tile(p, bm, ntb, 80 * 1024 - 512) && !big_pick_tile(p, bm, ntb, 160 * 1024)) return UPA_EUNSUPPORTED;
   p.tilesX = cdiv(p.OW, p.TW);
@@ -933,11 +909,11 @@ int big_prepare(BigParams& p, int& ntb, int& bm, size_t& lds, const upa_opts* op
   if (p.NTn == 9 && p.KS == 3 && p.stride == 1) ntb = 9;  // 144 = 64 + 80: both first convs of a Detect level, one halo, nine tiles
   if (force_ntb == 5 && p.NTn <= 5 && p.KS == 3 && p.stride == 1) ntb = 5;  // a 64-channel problem sharing a grid with an 80-channel one
   const long px = (long)p.N * p.OH * p.OW;
-  if (ntb == 8 && p.NTn % 4 == 0 && (px + 127) / 128 * cdiv(p.NTn, 8) < big_num_cu()) ntb = 4;
+  if (ntb == 8 && p.NTn % 4 == 0 && (px + 127) / 128 * cdiv(p.NTn, 8) < upa_num_cus()) ntb = 4;
   const int cols = cdiv(p.NTn, ntb);
   // 256-pixel workgroups unless that leaves most of the chip idle (fewer workgroups than CUs): then 128-pixel ones
   bm = 256;
-  if ((px + 255) / 256 * cols < big_num_cu()) bm = 128;
+  if ((px + 255) / 256 * cols < upa_num_cus()) bm = 128;
   if (const int f = UPA_OPT(opts, conv_big_bm); f == 128 || f == 256 || (f == 512 && p.KS == 3 && p.stride == 1 && (ntb == 4 || ntb == 5))) bm = f;
   if (query_only) return UPA_OK;
   if (p.KS == 1) {  // pointwise: an NHWC view has one uniform pixel stride - flatten (n, h, w) into one row

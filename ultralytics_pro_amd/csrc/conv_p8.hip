@@ -28,11 +28,6 @@
 #include "common.h"
 #include "conv_pipe.h"
 
-typedef __attribute__((address_space(1))) const void* p8gptr_t;
-typedef __attribute__((address_space(3))) void* p8lptr_t;
-
-__device__ __attribute__((aligned(16))) unsigned g_p8_zero16[4] = {0u, 0u, 0u, 0u};
-
 namespace {
 constexpr int P8_NTB = 8;                   // n-tiles per workgroup (128 channels)
 constexpr int P8_WBUF = 2 * P8_NTB * 1024;  // one (tap, chunk) weight slab
@@ -40,12 +35,6 @@ constexpr int P8_RING = 4;                  // slabs in LDS
 constexpr int P8_HP = 6;                    // halo pieces (64 items of 16 B) per wave per chunk: halo <= 8 * 6 * 64 items
 constexpr int P8_TRASH = 8 * 1024;          // where the pieces past the end of the halo image land
 
-template <int ACT>
-__device__ __forceinline__ float p8_act(float v) {
-  if constexpr (ACT == UPA_ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-  else if constexpr (ACT == UPA_ACT_RELU) return fmaxf(v, 0.0f);
-  else return v;
-}
 // s_waitcnt vmcnt(n) with n a constant after unrolling (the instruction takes an immediate)
 __device__ __forceinline__ void p8_wait_vm(const int n) {
   switch (n) {
@@ -119,11 +108,11 @@ __global__ __launch_bounds__(512, 2) void conv_p8_kernel(const BigParams p) {
     const int qx = pix - py * p.IWp;
     const int iy = iy0 + py, ix = ix0 + qx;
     const int ch = c * 64 + cg * 8;
-    const char* src = reinterpret_cast<const char*>(g_p8_zero16);
+    const char* src = reinterpret_cast<const char*>(g_zero16);
     if (idx < haloItems && qx < p.IW && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W && ch < p.Cin && c < nChunks)
       src = p.x + ((((size_t)n * p.H + iy) * p.W + ix) * (size_t)p.ldx + ch) * 2;
     char* dst = base < haloPadded ? hal0 + (size_t)(c & 1) * haloPadded * 16 + base * 16 : trash + wave * 1024;
-    __builtin_amdgcn_global_load_lds((p8gptr_t)src, (p8lptr_t)dst, 16, 0, 0);
+    lds_dma16(src, dst);
   };
   // this wave's two fragments (wave, wave + 8 of 16: f = kt * 8 + j) of slab s = chunk * 9 + tap -> ring slot s & 3 (past the end: zeros)
   auto stage_w = [&](int c, int tap, int slot) __attribute__((always_inline)) {
@@ -131,9 +120,9 @@ __global__ __launch_bounds__(512, 2) void conv_p8_kernel(const BigParams p) {
     for (int kt = 0; kt < 2; ++kt) {
       const int ktg = c * 2 + kt;
       const int nt = ntb0 + wave;
-      const char* src = reinterpret_cast<const char*>(g_p8_zero16);
+      const char* src = reinterpret_cast<const char*>(g_zero16);
       if (ktg < p.KTT && nt < p.NTn && c < nChunks) src = p.w + (((size_t)(tap * p.KTT + ktg) * p.NTn + nt) * 64 + lane) * 16;
-      __builtin_amdgcn_global_load_lds((p8gptr_t)src, (p8lptr_t)(wbuf + slot * P8_WBUF + (kt * P8_NTB + wave) * 1024), 16, 0, 0);
+      lds_dma16(src, wbuf + slot * P8_WBUF + (kt * P8_NTB + wave) * 1024);
     }
   };
 
@@ -227,8 +216,8 @@ __global__ __launch_bounds__(512, 2) void conv_p8_kernel(const BigParams p) {
         float v0[4], v1[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          v0[q] = p8_act<ACT>(acc[i][j][q] + biasv[j][q]);
-          v1[q] = p8_act<ACT>(acc[i][j + 1][q] + biasv[j + 1][q]);
+          v0[q] = act_rcp<ACT>(acc[i][j][q] + biasv[j][q]);
+          v1[q] = act_rcp<ACT>(acc[i][j + 1][q] + biasv[j + 1][q]);
         }
         const bool ok = pok && cw + cb < p.Cout;
         if (p.res) {

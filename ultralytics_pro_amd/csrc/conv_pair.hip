@@ -20,20 +20,6 @@
 #include "common.h"
 #include "conv_pipe.h"
 
-typedef __attribute__((address_space(1))) const void* pgptr_t;
-typedef __attribute__((address_space(3))) void* plptr_t;
-
-__device__ __attribute__((aligned(16))) unsigned g_pair_zero16[4] = {0u, 0u, 0u, 0u};
-
-namespace {
-template <int ACT>
-__device__ __forceinline__ float pair_act(float v) {
-  if constexpr (ACT == UPA_ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-  else if constexpr (ACT == UPA_ACT_RELU) return fmaxf(v, 0.0f);
-  else return v;
-}
-}  // namespace
-
 // CK = k-tiles (32 channels) of C: 1 (C = 32) or 2 (C = 64); NT = C / 16 n-tiles, all in every wave
 // CV2 (CK = 1 only): the Bottleneck is the single one of a C2f(.., 64, n = 1) and the C2f's cv2 follows at once - its input
 // cat(y0, y1, b) is three 32-channel k-steps: y0 straight from global memory in B-fragment order, y1 = this kernel's own input
@@ -87,10 +73,10 @@ __global__ __launch_bounds__(512, 4) void conv_pair_kernel(const PairParams p) {
     const int py = (int)__umulhi((unsigned)pix, p.magicIW);
     const int px = pix - py * IWp;
     const int iy = oy0 - 2 + py, ix = ox0 - 2 + px;
-    const char* src = reinterpret_cast<const char*>(g_pair_zero16);
+    const char* src = reinterpret_cast<const char*>(g_zero16);
     if (idx < haloItems && px < IW && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W)
       src = p.x + ((((size_t)n * p.H + iy) * p.W + ix) * (size_t)p.ldx + cg * 8) * 2;
-    __builtin_amdgcn_global_load_lds((pgptr_t)src, (plptr_t)(hal + base * 16), 16, 0, 0);
+    lds_dma16(src, hal + base * 16);
   }
   // weight slab of one tap: CK * NT fragments of 1 KiB, wave w brings fragments w, w + 8, ...
   auto stage_w = [&](const char* w, int tap, int b) __attribute__((always_inline)) {
@@ -98,8 +84,7 @@ __global__ __launch_bounds__(512, 4) void conv_pair_kernel(const PairParams p) {
     for (int f0 = 0; f0 < CK * NTM; f0 += 8) {
       const int f = f0 + wave;
       if (f < CK * NTM)
-        __builtin_amdgcn_global_load_lds((pgptr_t)(w + (((size_t)tap * CK * NTM + f) * 64 + lane) * 16),
-                                         (plptr_t)(wbuf + b * WBUF + f * 1024), 16, 0, 0);
+        lds_dma16(w + (((size_t)tap * CK * NTM + f) * 64 + lane) * 16, wbuf + b * WBUF + f * 1024);
     }
   };
   stage_w(p.w1, 0, 0);
@@ -180,7 +165,7 @@ __global__ __launch_bounds__(512, 4) void conv_pair_kernel(const PairParams p) {
       for (int j = 0; j < NTM; ++j) {
         float v[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = inside ? pair_act<UPA_ACT_SILU>(acc[i][j][q] + bv[j][q]) : 0.f;
+        for (int q = 0; q < 4; ++q) v[q] = inside ? act_rcp<UPA_ACT_SILU>(acc[i][j][q] + bv[j][q]) : 0.f;
         // channels 16j + 4g .. + 3: 16-byte group 2j + (g >> 1), half (g & 1)
         const int cg = 2 * j + (g >> 1);
         *reinterpret_cast<u32x2*>(row + ((cg ^ sw) << 4) + (g & 1) * 8) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
@@ -220,8 +205,8 @@ __global__ __launch_bounds__(512, 4) void conv_pair_kernel(const PairParams p) {
       float v0[4], v1[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        v0[q] = pair_act<UPA_ACT_SILU>(acc[i][0][q] + bv[0][q]);
-        v1[q] = pair_act<UPA_ACT_SILU>(acc[i][1][q] + bv[1][q]);
+        v0[q] = act_rcp<UPA_ACT_SILU>(acc[i][0][q] + bv[0][q]);
+        v1[q] = act_rcp<UPA_ACT_SILU>(acc[i][1][q] + bv[1][q]);
       }
       if constexpr (RES) {
         const char* xrow = hal + hp * PB;
@@ -252,8 +237,8 @@ __global__ __launch_bounds__(512, 4) void conv_pair_kernel(const PairParams p) {
         float w0[4], w1[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          w0[q] = pair_act<UPA_ACT_SILU>(o[j][q]);
-          w1[q] = pair_act<UPA_ACT_SILU>(o[j + 1][q]);
+          w0[q] = act_rcp<UPA_ACT_SILU>(o[j][q]);
+          w1[q] = act_rcp<UPA_ACT_SILU>(o[j + 1][q]);
         }
         auto lo = __builtin_amdgcn_permlane16_swap(pack_bf16x2(w0[0], w0[1]), pack_bf16x2(w1[0], w1[1]), false, false);
         auto hi = __builtin_amdgcn_permlane16_swap(pack_bf16x2(w0[2], w0[3]), pack_bf16x2(w1[2], w1[3]), false, false);
@@ -277,8 +262,8 @@ __global__ __launch_bounds__(512, 4) void conv_pair_kernel(const PairParams p) {
       float v0[4], v1[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        v0[q] = pair_act<UPA_ACT_SILU>(acc[i][j][q] + bv[j][q]);
-        v1[q] = pair_act<UPA_ACT_SILU>(acc[i][j + 1][q] + bv[j + 1][q]);
+        v0[q] = act_rcp<UPA_ACT_SILU>(acc[i][j][q] + bv[j][q]);
+        v1[q] = act_rcp<UPA_ACT_SILU>(acc[i][j + 1][q] + bv[j + 1][q]);
       }
       if constexpr (RES) {  // x + ...: the lane's own 4 channels of tiles j and j + 1, from the halo tile in LDS
         const u32x2 r0 = *reinterpret_cast<const u32x2*>(xrow + (((2 * j + (g >> 1)) ^ xsw) << 4) + (g & 1) * 8);

@@ -23,11 +23,6 @@
 #include "common.h"
 #include "conv_pipe.h"
 
-typedef __attribute__((address_space(1))) const void* pgptr_t;
-typedef __attribute__((address_space(3))) void* plptr_t;
-
-__device__ __attribute__((aligned(16))) unsigned g_pipe_zero16[4] = {0u, 0u, 0u, 0u};
-
 namespace {
 constexpr int TH = 8, TW = 16;             // output tile of one wave
 constexpr int IH = TH + 2, IW = TW + 2;    // halo
@@ -89,8 +84,8 @@ __global__ __launch_bounds__(WAVES * 64, 1) void conv3x3_pipe_kernel(const PipeP
     for (int k = 0; k < NDMA; ++k) {
       const int m = meta[k];
       const bool valid = ((m & (emask | 16)) == 0) && ((m >> 5) < grpmax);
-      const char* src = valid ? xk + rel[k] : reinterpret_cast<const char*>(g_pipe_zero16);
-      __builtin_amdgcn_global_load_lds((pgptr_t)src, (plptr_t)(hb + buf * HB + k * 1024), 16, 0, 0);
+      const char* src = valid ? xk + rel[k] : reinterpret_cast<const char*>(g_zero16);
+      lds_dma16(src, hb + buf * HB + k * 1024);
     }
   };
   // weight fragments: packed [tap][ktile][ntile][lane][16 B]; tap = kh*3 + kw
@@ -139,7 +134,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void conv3x3_pipe_kernel(const PipeP
   };
 
   auto act = [](float v) __attribute__((always_inline)) {
-    if constexpr (ACT == UPA_ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
+    if constexpr (ACT == UPA_ACT_SILU) return silu_rcp(v);
     else return v;
   };
   auto epilogue_pool = [&](const TileCtx& c) __attribute__((always_inline)) {
@@ -343,8 +338,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void conv3x3_c16_kernel(const PipePa
 #pragma unroll
     for (int k = 0; k < c16::NDMA; ++k) {
       const bool valid = (meta[k] & (c.em | 16)) == 0;
-      const char* src = valid ? c.xb + rel[k] : reinterpret_cast<const char*>(g_pipe_zero16);
-      __builtin_amdgcn_global_load_lds((pgptr_t)src, (plptr_t)(hb + buf * c16::HB + k * 1024), 16, 0, 0);
+      const char* src = valid ? c.xb + rel[k] : reinterpret_cast<const char*>(g_zero16);
+      lds_dma16(src, hb + buf * c16::HB + k * 1024);
     }
   };
   // A fragments of the five tap pairs (standard packing: [tap][ktile 0][ntile 0][lane][16 B], lanes kg 0/1 = channels 0-15)
@@ -367,7 +362,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void conv3x3_c16_kernel(const PipePa
   for (int nt = 0; nt < NT; ++nt) biasn[nt] = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + nt * 16 + kg * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
   const f32x4 biasv = biasn[0];
   auto act = [](float v) __attribute__((always_inline)) {
-    if constexpr (ACT == UPA_ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
+    if constexpr (ACT == UPA_ACT_SILU) return silu_rcp(v);
     else return v;
   };
 

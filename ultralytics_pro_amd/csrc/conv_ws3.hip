@@ -31,18 +31,7 @@
 #include "conv_pipe.h"
 UPA_STAMP_DEFINE(conv_ws3)
 
-typedef __attribute__((address_space(1))) const void* wgptr_t;
-typedef __attribute__((address_space(3))) void* wlptr_t;
-
-__device__ __attribute__((aligned(16))) unsigned g_ws3_zero16[4] = {0u, 0u, 0u, 0u};
-
 namespace ws3 {
-template <int ACT>
-__device__ __forceinline__ float act(float v) {
-  if constexpr (ACT == UPA_ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-  else if constexpr (ACT == UPA_ACT_RELU) return fmaxf(v, 0.0f);
-  else return v;
-}
 constexpr int TH = 8, IH = TH + 2;  // tile rows, halo rows
 constexpr int IW = 18;           // halo pitch = tile width 16 + 2
 }  // namespace ws3
@@ -95,8 +84,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ws3_kernel(const BigParams p)
       if (it * NTHR + wave * 64 >= HITP) break;  // wave-uniform: the last pass is partial
       const int iy = iy0 + (hitem[it] & 255), ix = ix0 + ((hitem[it] >> 8) & 255);
       const bool ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W && (hitem[it] >> 16) * 8 < p.Cin;  // (row 255 fails iy < H)
-      const char* src = ok ? xt + hoff[it] : reinterpret_cast<const char*>(g_ws3_zero16);
-      __builtin_amdgcn_global_load_lds((wgptr_t)src, (wlptr_t)(hal + b * HB + (it * NTHR + wave * 64) * 16), 16, 0, 0);
+      const char* src = ok ? xt + hoff[it] : reinterpret_cast<const char*>(g_zero16);
+      lds_dma16(src, hal + b * HB + (it * NTHR + wave * 64) * 16);
     }
   };
 
@@ -117,7 +106,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ws3_kernel(const BigParams p)
     for (int kt = 0; kt < 2; ++kt) {
       // Cin <= 32 has one k-tile: the second comes from the zero page (an unconditional load, no branch per fragment)
       const char* src = kt < p.KTT ? p.w + (((size_t)(tap * p.KTT + kt) * p.NTn + wave) * 64 + lane) * 16
-                                   : reinterpret_cast<const char*>(g_ws3_zero16);
+                                   : reinterpret_cast<const char*>(g_zero16);
       wr[tap][kt] = *reinterpret_cast<const u32x4*>(src);
     }
 
@@ -210,7 +199,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ws3_kernel(const BigParams p)
       for (int i = 0; i < TH; ++i) {
         float v[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = act<ACT>(acc[i][q] + biasv[q]);
+        for (int q = 0; q < 4; ++q) v[q] = act_rcp<ACT>(acc[i][q] + biasv[q]);
         if (p.res) {
           v[0] += __uint_as_float(rv[i][0] << 16); v[1] += __uint_as_float(rv[i][0] & 0xFFFF0000u);
           v[2] += __uint_as_float(rv[i][1] << 16); v[3] += __uint_as_float(rv[i][1] & 0xFFFF0000u);
@@ -256,18 +245,6 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ws3_kernel(const BigParams p)
   UPA_STAMP_AT(7);
 }
 
-namespace {
-int ws3_num_cu() {
-  static int numCU = 0;
-  if (!numCU) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&numCU, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || numCU <= 0) numCU = 256;
-  }
-  return numCU;
-}
-}  // namespace
-
 // Dispatch rule (upa_opts.conv_ws3: 0 = by size, 1 = never, 2 = every shape the kernel can run).
 bool upa_conv_ws3_eligible(const ConvShape& s, const upa_opts* opts) {
   const int mode = UPA_OPT(opts, conv_ws3);
@@ -288,7 +265,7 @@ int upa_conv_ws3_launch(BigParams p, int query_only, int* variant, void* stream,
 // p.stats != nullptr (act none, no residual, no bias): the convolution + the first stage of the batch statistics; *rows = rows written
 // (one per workgroup, at most two per CU)
 int upa_conv_ws3_launch_stats(BigParams p, int* rows, long max_rows, void* stream, const upa_opts* opts) {
-  if (!p.stats || p.res || p.bias || p.act != UPA_ACT_NONE || max_rows < 2 * ws3_num_cu()) return UPA_EUNSUPPORTED;
+  if (!p.stats || p.res || p.bias || p.act != UPA_ACT_NONE || max_rows < 2 * upa_num_cus()) return UPA_EUNSUPPORTED;
   return ws3_launch(p, 0, nullptr, rows, stream);
 }
 static int ws3_launch(BigParams p, int query_only, int* variant, int* rows, void* stream) {
@@ -307,7 +284,7 @@ static int ws3_launch(BigParams p, int query_only, int* variant, int* rows, void
     upa_set_error("conv_ws3: cannot raise LDS limit: %s", hipGetErrorString(e));
     return UPA_ELAUNCH;
   }
-  const int cus = ws3_num_cu();
+  const int cus = upa_num_cus();
   const unsigned grid = (unsigned)(tiles < 2 * cus ? tiles : 2 * cus);
   if (p.stats) {
     if (hipError_t e = upa_full_lds<conv_ws3_kernel<4, true>>(); e != hipSuccess) {

@@ -8,9 +8,6 @@
 // contiguous in NHWC (whole 128/160-byte lines per lane), the (B, C, A) stores are coalesced along the anchor axis.
 #include "common.h"
 
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 // One wave = 64 consecutive anchors of one level.  Their logits are brought into LDS by LDS-DMA as whole 16-byte groups
 // (lanes sweep the channel groups of consecutive anchors, so global reads are full contiguous lines), XOR-swizzled by
 // anchor so that the per-lane row reads that follow are bank-conflict free; outputs are written channel-major with the
@@ -40,7 +37,7 @@ __global__ __launch_bounds__(WAVES * 64) void detect_decode_kernel(const char* b
     long gid = wbase + row;
     if (gid >= total) gid = total - 1;
     const char* src = box + ((size_t)gid * ldb + grp * E) * sizeof(T);
-    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(bsm + k * 16), 16, 0, 0);
+    lds_dma16(src, bsm + k * 16);
   }
   for (int k = 0; k < 64 * gcp; k += 64) {
     const int item = k + lane;
@@ -50,7 +47,7 @@ __global__ __launch_bounds__(WAVES * 64) void detect_decode_kernel(const char* b
     if (gid >= total) gid = total - 1;
     if (grp >= gc) grp = gc - 1;  // padding slots: any valid address (never read back)
     const char* src = cls + ((size_t)gid * ldc + grp * E) * sizeof(T);
-    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(csm + k * 16), 16, 0, 0);
+    lds_dma16(src, csm + k * 16);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();

@@ -32,12 +32,6 @@
 #include "common.h"
 #include "detect_epi.h"
 
-typedef __attribute__((address_space(1))) const void* ds_gptr_t;
-typedef __attribute__((address_space(3))) void* ds_lptr_t;
-typedef __attribute__((ext_vector_type(4))) short ds_s16x4;
-
-__device__ __attribute__((aligned(64))) unsigned int g_ds_zero_page[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
 struct DsBranch {
   const char *w1, *w2, *wt;     // upa_pack_conv_weight layouts: 3x3 64 -> C, 3x3 C -> C, 1x1 C -> 16 NTT
   const float *b1, *b2, *bt;    // f32, padded to a multiple of 16
@@ -98,26 +92,6 @@ template <int C> struct Geo {
   static constexpr int LDS = DUMMY + 1024;
 };
 static_assert(XPLANE % 256 == 0 && T1PLANE % 256 == 0 && T2PLANE % 256 == 0, "planes keep the ds_read_b128 lane groups on disjoint banks");
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-__device__ __forceinline__ float silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-__device__ __forceinline__ f32x4 mfma32(const u32x4& a, const u32x4& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(&a), *reinterpret_cast<const bf16x8*>(&b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16(const u32x2& a, const u32x2& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(*reinterpret_cast<const ds_s16x4*>(&a), *reinterpret_cast<const ds_s16x4*>(&b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 mfma3232(const u32x4& a, const u32x4& b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(&a), *reinterpret_cast<const bf16x8*>(&b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void shape_fence() {  // between MFMA shapes on one accumulator chain (see c2f_stream.hip: f_role)
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_nop 15" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ u32x4 lds128(const char* sm, int off) { return *reinterpret_cast<const u32x4*>(sm + off); }
-__device__ __forceinline__ u32x2 lds64(const char* sm, int off) { return *reinterpret_cast<const u32x2*>(sm + off); }
 
 // Geometry of one 3x3 stage.  STG 0: x ring -> t1 (32 columns, rows {2s - 1, 2s} at step s);  STG 1: t1 ring -> t2 (30 columns, rows {2s - 4, 2s - 3}).
 template <int C, int STG> struct StageGeo {
@@ -213,7 +187,7 @@ struct Conv32 {
         e_oa = in0 + out_d + (row & SG::OUT_MASK) * TROWB;
       }
       if (k < 16) {
-        sv[k & 3] = silu(a[k]);
+        sv[k & 3] = silu_rcp(a[k]);
         if ((k & 3) == 3) {
           const u32x2 o = u32x2{pack_bf16x2(sv[0], sv[1]) & e_m, pack_bf16x2(sv[2], sv[3]) & e_m};
           *reinterpret_cast<u32x2*>(sm + (e_ok ? e_oa + (k >> 2) * SG::OUT_PLANE : G::DUMMY + x.lane * 8)) = o;
@@ -230,7 +204,7 @@ struct Conv32 {
 #pragma unroll
       for (int f = 0; f < NF; ++f) {
         const int t = u * NF + f;
-        a = mfma3232(w[f / KS][f % KS], buf[t % NBUF], a);
+        a = mfma32x32(w[f / KS][f % KS], buf[t % NBUF], a);
         if (t + NBUF < NTOT) buf[t % NBUF] = rd(t + NBUF);
         if (PIPE && u > 0) {  // row 0's sixteen epilogue slices, spread evenly over row 1's MFMAs (a slice is ~28 issue cycles, an MFMA 32 of pipe)
 #pragma unroll
@@ -318,7 +292,7 @@ struct Conv16 {
         e_oa = in0 + out_d + (row & SG::OUT_MASK) * TROWB;
       }
       const int q = k >> 2;
-      sv[k & 3] = silu(acc[u][q][k & 3]);
+      sv[k & 3] = silu_rcp(acc[u][q][k & 3]);
       if ((k & 3) == 3) {
         const unsigned m = e_m & colm[q];
         const u32x2 o = u32x2{pack_bf16x2(sv[0], sv[1]) & m, pack_bf16x2(sv[2], sv[3]) & m};
@@ -347,7 +321,7 @@ struct Conv16 {
         __builtin_amdgcn_sched_barrier(0);
       }
       if constexpr (SG::K16 != 0) {
-        shape_fence();
+        mfma_shape_fence();
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
           u32x2 nx[2][3];
@@ -477,7 +451,7 @@ struct Tail {
         for (int j = 0; j < NTT; ++j) v[j] = mfma32(w32[kt][j], b32[u][kt], v[j]);
       if (s == 10 && u == 0) DS_STAMP(x.slot, 45, 0);
       if constexpr (G::K16 != 0) {
-        shape_fence();
+        mfma_shape_fence();
 #pragma unroll
         for (int j = 0; j < NTT; ++j) v[j] = mfma16(w16[j], b16[u], v[j]);
       }
@@ -548,7 +522,7 @@ struct Dma {
   }
   __device__ __forceinline__ void band(const Ctx& x, int b) {
     if (2 * b >= x.LP) return;  // wave-uniform
-    const char* zp = reinterpret_cast<const char*>(g_ds_zero_page);
+    const char* zp = reinterpret_cast<const char*>(g_zero16);
 #pragma unroll
     for (int rr = 0; rr < 2; ++rr) {
       const int gy = x.py0 - 2 + 2 * b + rr;
@@ -557,7 +531,7 @@ struct Dma {
       const int dst = XB + ((2 * b + rr) & (XROWS - 1)) * XROWB;  // + lane * 16 by the hardware
 #pragma unroll
       for (int cg = 0; cg < 8; ++cg)
-        __builtin_amdgcn_global_load_lds((ds_gptr_t)(src + (ok ? cg * 16 : 0)), (ds_lptr_t)(x.sm + dst + cg * XPLANE), 16, 0, 0);
+        lds_dma16(src + (ok ? cg * 16 : 0), x.sm + dst + cg * XPLANE);
     }
   }
 };

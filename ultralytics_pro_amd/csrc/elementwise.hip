@@ -232,7 +232,7 @@ __global__ __launch_bounds__(512) void sppf_front_kernel(const char* x, int N, i
       // lane (kg, l16): channels 16 j + 4 kg .. + 3 of pixel pix
       float v[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = acc[r] * __builtin_amdgcn_rcpf(1.0f + __expf(-acc[r]));
+      for (int r = 0; r < 4; ++r) v[r] = silu_rcp(acc[r]);
       const u32x2 pk = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
       if (pix[q] < HW) {
         *reinterpret_cast<u32x2*>(yn + ((size_t)pix[q] * ldy + j * 16 + kg * 4) * 2) = pk;

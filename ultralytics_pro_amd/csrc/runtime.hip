@@ -23,6 +23,17 @@ __global__ void upa_zero_words_kernel(unsigned* p, int n) {
 extern "C" int upa_version(void) { return 3; }  // 2: upa_opts argument on the dispatching entry points; 3: conv_force / conv_mm left upa_opts
 extern "C" size_t upa_opts_size(void) { return sizeof(upa_opts); }
 
+// C++11 static initialisation: thread safe, one query per process (of the device current at the first call, as every launcher
+// cached it before)
+int upa_num_cus() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    (void)hipGetDevice(&dev);
+    return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
+  }();
+  return cus;
+}
+
 // Device -> pinned host copy as a KERNEL (the device writes the host-mapped allocation through its unified address): a step
 // captured into a hipGraph can hand its detections to the host with no memcpy node (with several graphs of the step in flight
 // the runtime's memset / memcpy nodes have misbehaved, see upa_zero_words) and no extra host call per step.

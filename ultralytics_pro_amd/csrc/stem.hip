@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemParams p) {
 #pragma unroll
   for (int c = 0; c < CO_T; ++c) {
     float t = acc[c];
-    if constexpr (SILU) t = F32 ? t / (1.0f + expf(-t)) : t * __builtin_amdgcn_rcpf(1.0f + __expf(-t));
+    if constexpr (SILU) t = F32 ? t / (1.0f + expf(-t)) : silu_rcp(t);
     v[c] = t;
   }
   if constexpr (F32) {
@@ -191,9 +191,6 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemParams p) {
 // All geometry is compile time (no integer divisions in the kernel); the patch origin is rounded down to 8 pixels so a
 // bf16 NCHW input whose width is a multiple of 8 is staged by LDS-DMA in 16-byte chunks (no VGPR round trip).
 typedef __attribute__((ext_vector_type(4))) short stem_s16x4;
-typedef __attribute__((address_space(1))) const void* sgptr_t;
-typedef __attribute__((address_space(3))) void* slptr_t;
-__device__ __attribute__((aligned(16))) unsigned g_stem_zero16[4] = {0u, 0u, 0u, 0u};
 
 template <int KS, int S>
 struct StemGeo {
@@ -231,8 +228,8 @@ __device__ __forceinline__ void stem_stage(const StemParams& p, int tile, unsign
       const int iy = iy0 + row, ix = ixa + ch * 8;
       const bool in = item < G::ITEMS && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W && !UPA_ABL(p, 1);
       const char* src = in ? reinterpret_cast<const char*>(xb + ci * plane + iy * p.W + ix)
-                           : reinterpret_cast<const char*>(g_stem_zero16);
-      __builtin_amdgcn_global_load_lds((sgptr_t)src, (slptr_t)((char*)buf + (it * 256 + wave * 64) * 16), 16, 0, 0);
+                           : reinterpret_cast<const char*>(g_zero16);
+      lds_dma16(src, (char*)buf + (it * 256 + wave * 64) * 16);
     }
   } else if (p.x_bf16 == 2) {
     // uint8 HWC BGR frames (engine/predictor.py:151-173): BGR->RGB, HWC->CHW, /255 fused into the load
@@ -445,7 +442,7 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(const StemParams p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               float t = acc[sx][nt][r];
-              if (!UPA_ABL(p, 4)) t = t * __builtin_amdgcn_rcpf(1.0f + __expf(-t));
+              if (!UPA_ABL(p, 4)) t = silu_rcp(t);
               vkeep[sx][nt][r] = rr == 0 ? t : fmaxf(vkeep[sx][nt][r], t);
             }
         if (rr == 0) continue;
@@ -478,7 +475,7 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(const StemParams p) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             float t = acc[sx][nt][r];
-            if constexpr (SILU) if (!UPA_ABL(p, 4)) t = t * __builtin_amdgcn_rcpf(1.0f + __expf(-t));
+            if constexpr (SILU) if (!UPA_ABL(p, 4)) t = silu_rcp(t);
             v[r] = t;
           }
           u32x2 pk = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
@@ -670,6 +667,8 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void stem_conv_fused_kernel(const 
     it_col[it] = ch * 8;
     it_off[it] = ci * plane + row * p.W + ch * 8;
   }
+  // (the builtin spelled out, here and in stem_conv_fused32_kernel: through lds_dma16 (common.h) hipcc allocates the registers of these two
+  // kernels differently - same code otherwise; kept as it was so that the kernels stay instruction-identical)
   auto stage = [&](int tile, char* buf) __attribute__((always_inline)) {
     const int n = tile / tilesPerImg;
     const int t2 = tile - n * tilesPerImg;
@@ -686,13 +685,13 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void stem_conv_fused_kernel(const 
       const int first = it * NTH + wave * 64;   // this wave's 64 items of the pass (wave-uniform)
       if (first >= ITEMS) continue;             // all padding: nothing reads those LDS bytes (7 of 8 waves in the last of the k = 3 form's 3 passes)
       if (inside && first + 64 <= ITEMS) {
-        __builtin_amdgcn_global_load_lds((sgptr_t) reinterpret_cast<const char*>(xt + it_off[it]), (slptr_t)(buf + first * 16), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr_t)(xt + it_off[it]), (lptr_t)(buf + first * 16), 16, 0, 0);
         continue;
       }
       const int iy = iy0 + it_row[it], ix = ixa + it_col[it];
       const bool in = iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-      const char* src = in ? reinterpret_cast<const char*>(xt + it_off[it]) : reinterpret_cast<const char*>(g_stem_zero16);
-      __builtin_amdgcn_global_load_lds((sgptr_t)src, (slptr_t)(buf + first * 16), 16, 0, 0);
+      const char* src = in ? reinterpret_cast<const char*>(xt + it_off[it]) : reinterpret_cast<const char*>(g_zero16);
+      __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(buf + first * 16), 16, 0, 0);
     }
   };
   // XCD-aware walk (common.h: upa_xcd_tile): slot = blockIdx.x + i * gridDim.x names the XCD by slot & 7 when the grid is a multiple
@@ -844,7 +843,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void stem_conv_fused_kernel(const 
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
               const float u = acc[t];
-              v[t] = inmap ? u * __builtin_amdgcn_rcpf(1.0f + __expf(-u)) : 0.f;
+              v[t] = inmap ? silu_rcp(u) : 0.f;
             }
             // (only the tile's last segment has lanes past its end: the store of every other segment needs no exec mask)
             if ((i + 1) * NW * 16 <= S0H * S0W || sg_out[i] >= 0) *reinterpret_cast<u32x2*>(stile + sg_out[i]) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
@@ -877,8 +876,8 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void stem_conv_fused_kernel(const 
       float v0[4], v1[4];
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        v0[t] = acc[0][t] * __builtin_amdgcn_rcpf(1.0f + __expf(-acc[0][t]));
-        v1[t] = acc[1][t] * __builtin_amdgcn_rcpf(1.0f + __expf(-acc[1][t]));
+        v0[t] = silu_rcp(acc[0][t]);
+        v1[t] = silu_rcp(acc[1][t]);
       }
       auto lo = __builtin_amdgcn_permlane16_swap(pack_bf16x2(v0[0], v0[1]), pack_bf16x2(v1[0], v1[1]), false, false);
       auto hi = __builtin_amdgcn_permlane16_swap(pack_bf16x2(v0[2], v0[3]), pack_bf16x2(v1[2], v1[3]), false, false);
@@ -965,13 +964,13 @@ __global__ __launch_bounds__(512, 4) void stem_conv_fused32_kernel(const StemFus
       const int first = it * NTH + wave * 64;
       if (first >= ITEMS) continue;
       if (inside && first + 64 <= ITEMS) {
-        __builtin_amdgcn_global_load_lds((sgptr_t) reinterpret_cast<const char*>(xt + it_off[it]), (slptr_t)(buf + first * 16), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr_t)(xt + it_off[it]), (lptr_t)(buf + first * 16), 16, 0, 0);
         continue;
       }
       const int iy = iy0 + it_row[it], ix = ixa + it_col[it];
       const bool in = iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-      const char* src = in ? reinterpret_cast<const char*>(xt + it_off[it]) : reinterpret_cast<const char*>(g_stem_zero16);
-      __builtin_amdgcn_global_load_lds((sgptr_t)src, (slptr_t)(buf + first * 16), 16, 0, 0);
+      const char* src = in ? reinterpret_cast<const char*>(xt + it_off[it]) : reinterpret_cast<const char*>(g_zero16);
+      __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(buf + first * 16), 16, 0, 0);
     }
   };
   const bool xcd = !p.no_xcd && ((gridDim.x & 7) == 0 || (int)gridDim.x >= ntiles);
@@ -1094,7 +1093,7 @@ __global__ __launch_bounds__(512, 4) void stem_conv_fused32_kernel(const StemFus
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
             const float u = acc[t];
-            v[t] = inmap ? u * __builtin_amdgcn_rcpf(1.0f + __expf(-u)) : 0.f;
+            v[t] = inmap ? silu_rcp(u) : 0.f;
           }
           if (qin) *reinterpret_cast<u32x2*>(dst + nt * 32) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
         }
@@ -1120,7 +1119,7 @@ __global__ __launch_bounds__(512, 4) void stem_conv_fused32_kernel(const StemFus
       const int oy = oy0 + i, ox = ox0 + l16;
       float v[4];
 #pragma unroll
-      for (int t = 0; t < 4; ++t) v[t] = acc[t] * __builtin_amdgcn_rcpf(1.0f + __expf(-acc[t]));
+      for (int t = 0; t < 4; ++t) v[t] = silu_rcp(acc[t]);
       if (oy < p.OH && ox < p.OW)
         *reinterpret_cast<u32x2*>(p.y + ((size_t)((n * p.OH + oy) * p.OW + ox) * p.ldy + nt1 * 16 + kg * 4) * 2) =
             u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};

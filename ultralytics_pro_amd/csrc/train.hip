@@ -643,9 +643,6 @@ UPA_STAMP_DEFINE(train)
 #define WG_T(v) do {} while (0)
 #define WG_ACC(a, t0_, t1_) do {} while (0)
 #endif
-typedef __attribute__((address_space(1))) const void* wg_gptr_t;
-typedef __attribute__((address_space(3))) void* wg_lptr_t;
-__device__ __attribute__((aligned(16))) unsigned g_wg_zero16[4] = {0u, 0u, 0u, 0u};
 
 // The DMA is issued from inline asm: through the builtin the compiler knows that it writes LDS and puts s_waitcnt vmcnt(0)
 // in front of the next LDS read - with stages in flight behind the one being read that wait is the whole pipeline.  Issued
@@ -688,7 +685,7 @@ __global__ __launch_bounds__(R1_NW * 64) void wgrad_k1_ring_kernel(const WgradPa
   const int pxb = wave * 4 + kg;
   const int cl = ((((lane & 15) >> 1) ^ (pxb & 7)) << 1) | (lane & 1);
   const bool zok = co0 + cl * 8 < p.Cout, xok = ci0 + cl * 8 < p.Cin;
-  const char* const zero = reinterpret_cast<const char*>(g_wg_zero16);
+  const char* const zero = reinterpret_cast<const char*>(g_zero16);
   const char* const zsrc = p.dz + ((size_t)pxb * p.lddz + co0 + cl * 8) * 2;
   const char* const xsrc = p.x + ((size_t)pxb * p.ldx + ci0 + cl * 8) * 2;
   auto stage = [&](int i) __attribute__((always_inline)) {   // tile i of this workgroup -> ring slot i % RING (past the end: zeros)
@@ -823,7 +820,7 @@ __global__ __launch_bounds__((R3Geo<S, BCI>::NW * 64)) void wgrad_k3_ring_kernel
       if (ci0 + cl * 8 < p.Cin) rr[q] = py;
     }
   }
-  const char* const zero = reinterpret_cast<const char*>(g_wg_zero16);
+  const char* const zero = reinterpret_cast<const char*>(g_zero16);
   auto stage = [&](int i) __attribute__((always_inline)) {   // tile i of this workgroup -> ring slot i % RING (past the end: zeros)
     const int tile = (int)blockIdx.x + i * Gx;
     const int n = tile / tilesPerImg;

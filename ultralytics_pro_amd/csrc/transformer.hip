@@ -543,9 +543,6 @@ extern "C" int upa_conv2d_bias_act(const void*, int, int, int, int, int, const v
 // without a barrier: 4 exact-f32 MFMAs (v_mfma_f32_16x16x4_f32) per 16-byte fragment pair, one accumulator chain over the whole K
 // (K <= 1024: no partial-sum folding needed at f32 accuracy).  Epilogue from the accumulators: bias, ReLU / SiLU (precise), residual,
 // 16-byte f32 stores.
-typedef __attribute__((address_space(1))) const void* lgptr_t;
-typedef __attribute__((address_space(3))) void* llptr_t;
-__device__ __attribute__((aligned(16))) unsigned g_lin_zero16[4] = {0u, 0u, 0u, 0u};
 
 struct LinParams {
   const char* x; const char* w; const float* bias; const char* res; char* y;
@@ -568,9 +565,9 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const LinParams p) {
     const int it = base + lane;
     const int row = it / G, slot = it - row * G;
     const int cg = slot ^ (row & 7);
-    const char* src = reinterpret_cast<const char*>(g_lin_zero16);
+    const char* src = reinterpret_cast<const char*>(g_zero16);
     if (row0 + row < p.M) src = p.x + ((size_t)(row0 + row) * p.ldx + cg * 4) * 4;
-    __builtin_amdgcn_global_load_lds((lgptr_t)src, (llptr_t)(lsm + base * 16), 16, 0, 0);
+    lds_dma16(src, lsm + base * 16);
   }
   const bool live = nt < p.NTn;  // wave-uniform: column blocks past N only help staging
   // ---- A fragments of this n-tile: [k-tile][n-tile][lane][16 B]; 16 k-tiles (256 channels) per register set
@@ -661,9 +658,9 @@ __global__ __launch_bounds__(256) void linear_bf16_kernel(const LinParams p) {
     const int it = base + lane;
     const int row = it / G, slot = it - row * G;
     const int cg = slot ^ (row & 7);
-    const char* src = reinterpret_cast<const char*>(g_lin_zero16);
+    const char* src = reinterpret_cast<const char*>(g_zero16);
     if (row0 + row < p.M) src = p.x + ((size_t)(row0 + row) * p.ldx + cg * GE) * (XB ? 2 : 4);
-    __builtin_amdgcn_global_load_lds((lgptr_t)src, (llptr_t)(lsm + base * 16), 16, 0, 0);
+    lds_dma16(src, lsm + base * 16);
   }
   const bool live = nt < p.NTn;
   // A fragments of this n-tile: [k-tile of 32][n-tile][lane][16 B]; 8 k-tiles (256 channels) per register set
