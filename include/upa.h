@@ -475,12 +475,12 @@ int upa_conv2d_bn_act_fwd(const void* x, int n, int h, int w, int cin, int ldx, 
                           int stride, int pad, float momentum, float* mean, float* var, float* running_mean, float* running_var,
                           const float* gamma, const float* beta, float eps, int act, void* y, int ldy, const void* residual, int ldr,
                           double* ws, int dtype, const upa_opts* opts, void* stream);
-/* y = act(gamma * (z - mean) / sqrt(var + eps) + beta) (+ residual) */
+/* y = act(gamma * (z - mean) / sqrt(var + eps) + beta) (+ residual).  ldz, ldy (and ldr with a residual): multiples of 16 bytes. */
 int upa_bn_act_fwd(const void* z, long npix, int c, int ldz, const float* mean, const float* var, const float* gamma,
                    const float* beta, float eps, int act, void* y, int ldy, const void* residual, int ldr, int dtype,
                    void* stream);
 /* Backward of the above (z saved from the forward): dgamma, dbeta (f32, optionally accumulated) and dz.
- * ws: upa_channel_reduce_workspace_bytes(c). */
+ * ws: upa_channel_reduce_workspace_bytes(c).  ldz, lddy, lddz: multiples of 16 bytes (UPA_EINVAL otherwise). */
 int upa_bn_act_bwd(const void* z, const void* dy, long npix, int c, int ldz, int lddy, const float* mean, const float* var,
                    const float* gamma, const float* beta, float eps, int act, void* dz, int lddz, float* dgamma, float* dbeta,
                    int accumulate, double* ws, int dtype, void* stream);
@@ -506,21 +506,23 @@ int upa_conv2d_wgrad(const void* x, int n, int h, int w, int cin, int ldx, const
  * pixels itself.  UPA_EUNSUPPORTED (nothing launched) outside the fused form: run the phase conv + upa_interleave2x. */
 int upa_conv2d_dgrad_s2(const void* dz, int n, int oh, int ow, int cout, int lddz, const void* phase_w_packed, void* dx, int h, int w,
                         int cin, int lddx, int accumulate, int dtype, const upa_opts* opts, void* stream);
-/* dst (n,h,w,c) = zero-inserted src (n,oh,ow,c): dst[y,x] = src[y/2,x/2] for even y, x (data gradient of stride 2). */
+/* dst (n,h,w,c) = zero-inserted src (n,oh,ow,c): dst[y,x] = src[y/2,x/2] for even y, x (data gradient of stride 2).
+ * lds, ldd: multiples of 16 bytes. */
 int upa_dilate2x(const void* src, int n, int oh, int ow, int c, int lds, void* dst, int h, int w, int ldd, int dtype,
                  void* stream);
 /* Data gradient of a 3x3 stride-2 pad-1 conv by output parity: four 2x2 stride-1 correlations over dz (1/2/2/4 live taps)
  * instead of a 9-tap one over the zero-inserted dz.  upa_dgrad_s2_phase_weights writes V[phase = 2*py+px][ci][co][2][2] (f32,
  * "OIHW" with O = cin); each V[phase] is packed with upa_pack_conv_weight_dev(cout' = cin, cin' = cout, k = 2) and run as
  * upa_conv2d_bias_act(dz, k 2, stride 1, pad 1) into a phase map of (oh+1, ow+1) pixels; upa_interleave2x scatters
- * dx[2i+py][2j+px] (+)= phase[py][px][i+1][j+1]. */
+ * dx[2i+py][2j+px] (+)= phase[py][px][i+1][j+1].  upa_interleave2x: ldt, lddx multiples of 16 bytes. */
 int upa_dgrad_s2_phase_weights(const float* w_oihw, int cout, int cin, float* v, void* stream);
 int upa_interleave2x(const void* t00, const void* t01, const void* t10, const void* t11, int n, int oh1, int ow1, int c, int ldt,
                      void* dx, int h, int w, int lddx, int accumulate, int dtype, void* stream);
-/* dx (n,h,w,c) (+)= 2x2 block sums of dy (n,2h,2w,c): backward of nn.Upsample(scale 2, nearest). */
+/* dx (n,h,w,c) (+)= 2x2 block sums of dy (n,2h,2w,c): backward of nn.Upsample(scale 2, nearest).  lddy, lddx: multiples of 16 bytes. */
 int upa_upsample2x_bwd(const void* dy, int n, int h, int w, int c, int lddy, void* dx, int lddx, int accumulate, int dtype,
                        void* stream);
-/* Backward of nn.MaxPool2d(k, stride, pad): dy goes to the first maximum of each window (torch's index rule). */
+/* Backward of nn.MaxPool2d(k, stride, pad): dy goes to the first maximum of each window (torch's index rule).
+ * ldx, lddy, lddx: multiples of 16 bytes; k <= 15, pad <= k / 2 and k <= min(h, w) + 2 pad (at least one window), UPA_EINVAL otherwise. */
 size_t upa_maxpool2d_bwd_workspace_bytes(int n, int h, int w, int c, int k, int stride, int pad);
 int upa_maxpool2d_bwd(const void* x, const void* dy, int n, int h, int w, int c, int ldx, int lddy, int k, int stride, int pad,
                       void* dx, int lddx, int accumulate, int dtype, void* workspace, size_t workspace_bytes, void* stream);
@@ -547,7 +549,7 @@ int upa_sgd_nesterov_ema_scaled(float* p, float* g, float* momentum_buf, float* 
 int upa_grad_scaler_update(float* scaler_state, const double* grad_sumsq, float growth_factor, float backoff_factor,
                            int growth_interval, void* stream);
 int upa_ema_update(float* ema, const float* v, long n, float d, const float* d_dev, void* stream);
-/* dst view = src view converted between f32 and bf16 (head maps enter the loss as f32; c, strides multiples of 8). */
+/* dst view = src view converted between f32 and bf16 (head maps enter the loss as f32; c, lds, ldd positive multiples of 8). */
 int upa_cast_view(const void* src, int src_dtype, int lds, void* dst, int dst_dtype, int ldd, long npix, int c, void* stream);
 /* v8DetectionLoss forward + gradient wrt the raw head maps.  feats[l] / grads[l]: NHWC f32 rows [(b,y,x)][4*reg_max+nc]
  * with row stride lds[l]; gt: (b, max_gt, 5) rows (cls, x1, y1, x2, y2) in pixels, n_gt[b] valid rows; max_gt = the row

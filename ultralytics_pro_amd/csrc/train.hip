@@ -1417,6 +1417,13 @@ static int check_view(long npix, int c, int ld, int dtype, const char* what) {
   return UPA_OK;
 }
 
+// every further pitch of a call: the kernels move 16-byte packets at (pixel * ld + group * E) elements
+static int check_pitch(int ld, int dtype, const char* what, const char* name) {
+  const int E = 16 / upa_elem_size(dtype);
+  UPA_CHECK_ARG(ld > 0 && ld % E == 0, "%s: %s must be a positive multiple of %d", what, name, E);
+  return UPA_OK;
+}
+
 extern "C" size_t upa_channel_reduce_workspace_bytes(int c) {
   return (size_t)(2048 + 1) * 2 * c * sizeof(double);  // per-block partials + the combined sums
 }
@@ -1449,7 +1456,7 @@ extern "C" int upa_bn_stats(const void* z, long npix, int c, int ldz, double* ws
 
 extern "C" int upa_bn_finalize(const double* ws, long npix, int c, float momentum, float* mean, float* var,
                                float* running_mean, float* running_var, void* stream) {
-  UPA_CHECK_ARG(ws && mean && var && npix > 0, "bn_finalize: bad args");
+  UPA_CHECK_ARG(ws && mean && var && npix > 0 && c > 0, "bn_finalize: bad args");
   CombineParams q{};
   q.part = ws; q.nblocks = reduce_grid(npix); q.c = c; q.npix = npix; q.momentum = momentum; q.mean = mean; q.var = var;
   q.running_mean = running_mean; q.running_var = running_var;
@@ -1474,6 +1481,10 @@ extern "C" int upa_bn_act_fwd(const void* z, long npix, int c, int ldz, const fl
   UPA_CHECK_ARG(z && y && mean && var && gamma && beta, "bn_act_fwd: null pointer");
   UPA_CHECK_ARG(act == UPA_ACT_SILU || act == UPA_ACT_NONE, "bn_act_fwd: activation must be SiLU or none");
   if (int rc = check_view(npix, c, ldz, dtype, "bn_act_fwd")) return rc;
+  if (int rc = check_pitch(ldy, dtype, "bn_act_fwd", "ldy")) return rc;
+  if (residual) {
+    if (int rc = check_pitch(ldr, dtype, "bn_act_fwd", "ldr")) return rc;
+  }
   BnApplyParams p{};
   p.z = (const char*)z; p.y = (char*)y; p.aux = (const char*)residual; p.npix = npix; p.c = c; p.ldz = ldz; p.ldy = ldy; p.ldaux = ldr;
   p.mean = mean; p.var = var; p.gamma = gamma; p.beta = beta; p.eps = eps; p.act = act;
@@ -1491,6 +1502,8 @@ extern "C" int upa_bn_act_bwd(const void* z, const void* dy, long npix, int c, i
   UPA_CHECK_ARG(z && dy && dz && mean && var && gamma && beta && dgamma && dbeta && ws, "bn_act_bwd: null pointer");
   UPA_CHECK_ARG(act == UPA_ACT_SILU || act == UPA_ACT_NONE, "bn_act_bwd: activation must be SiLU or none");
   if (int rc = check_view(npix, c, ldz, dtype, "bn_act_bwd")) return rc;
+  if (int rc = check_pitch(lddy, dtype, "bn_act_bwd", "lddy")) return rc;
+  if (int rc = check_pitch(lddz, dtype, "bn_act_bwd", "lddz")) return rc;
   hipStream_t s = (hipStream_t)stream;
   ReduceParams r{};
   r.z = (const char*)z; r.dy = (const char*)dy; r.npix = npix; r.c = c; r.ldz = ldz; r.lddy = lddy;
@@ -1770,6 +1783,7 @@ extern "C" int upa_dilate2x(const void* src, int n, int oh, int ow, int c, int l
                             void* stream) {
   UPA_CHECK_ARG(src && dst, "dilate2x: null pointer");
   if (int rc = check_view((long)n * h * w, c, lds_, dtype, "dilate2x")) return rc;
+  if (int rc = check_pitch(ldd, dtype, "dilate2x", "ldd")) return rc;
   const int E = 16 / upa_elem_size(dtype);
   const long total = (long)n * h * w * (c / E);
   if (dtype == UPA_BF16) hipLaunchKernelGGL((dilate2x_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
@@ -1784,6 +1798,7 @@ extern "C" int upa_upsample2x_bwd(const void* dy, int n, int h, int w, int c, in
                                   void* stream) {
   UPA_CHECK_ARG(dy && dx, "upsample2x_bwd: null pointer");
   if (int rc = check_view((long)n * h * w, c, lddy, dtype, "upsample2x_bwd")) return rc;
+  if (int rc = check_pitch(lddx, dtype, "upsample2x_bwd", "lddx")) return rc;
   const int E = 16 / upa_elem_size(dtype);
   const long total = (long)n * h * w * (c / E);
   if (dtype == UPA_BF16) hipLaunchKernelGGL((upsample2x_bwd_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
@@ -1804,6 +1819,11 @@ extern "C" int upa_maxpool2d_bwd(const void* x, const void* dy, int n, int h, in
                                  void* stream) {
   UPA_CHECK_ARG(x && dy && dx && k >= 1 && k <= 15 && stride >= 1, "maxpool2d_bwd: bad args");
   if (int rc = check_view((long)n * h * w, c, ldx, dtype, "maxpool2d_bwd")) return rc;
+  if (int rc = check_pitch(lddy, dtype, "maxpool2d_bwd", "lddy")) return rc;
+  if (int rc = check_pitch(lddx, dtype, "maxpool2d_bwd", "lddx")) return rc;
+  UPA_CHECK_ARG(pad >= 0 && pad <= k / 2, "maxpool2d_bwd: pad must be in 0 .. k / 2 (pad=%d k=%d)", pad, k);
+  UPA_CHECK_ARG(h + 2 * pad >= k && w + 2 * pad >= k, "maxpool2d_bwd: k larger than the padded map (k=%d h=%d w=%d pad=%d): no output pixel",
+                k, h, w, pad);
   const int oh = (h + 2 * pad - k) / stride + 1, ow = (w + 2 * pad - k) / stride + 1;
   UPA_CHECK_ARG(workspace && workspace_bytes >= (size_t)n * oh * ow * c, "maxpool2d_bwd: workspace too small");
   const int E = 16 / upa_elem_size(dtype);
@@ -1884,7 +1904,8 @@ extern "C" int upa_ema_update(float* ema, const float* v, long n, float d, const
 
 extern "C" int upa_cast_view(const void* src, int src_dtype, int lds_, void* dst, int dst_dtype, int ldd, long npix, int c,
                              void* stream) {
-  UPA_CHECK_ARG(src && dst && npix > 0 && c % 8 == 0 && lds_ % 8 == 0 && ldd % 8 == 0, "cast_view: bad args (c, strides multiples of 8)");
+  UPA_CHECK_ARG(src && dst && npix > 0 && c > 0 && c % 8 == 0 && lds_ > 0 && lds_ % 8 == 0 && ldd > 0 && ldd % 8 == 0,
+                "cast_view: bad args (c, strides positive multiples of 8)");
   const int grid = grid_for(npix * (c / 8));
   hipStream_t s = (hipStream_t)stream;
   if (src_dtype == UPA_BF16 && dst_dtype == UPA_F32)
@@ -1910,6 +1931,7 @@ extern "C" int upa_interleave2x(const void* t00, const void* t01, const void* t1
                                 int ldt, void* dx, int h, int w, int lddx, int accumulate, int dtype, void* stream) {
   UPA_CHECK_ARG(t00 && t01 && t10 && t11 && dx, "interleave2x: null pointer");
   if (int rc = check_view((long)n * h * w, c, lddx, dtype, "interleave2x")) return rc;
+  if (int rc = check_pitch(ldt, dtype, "interleave2x", "ldt")) return rc;
   const int E = 16 / upa_elem_size(dtype);
   const long total = (long)n * h * w * (c / E);
   if (dtype == UPA_BF16)
