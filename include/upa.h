@@ -615,6 +615,58 @@ int upa_resize_bilinear(const float* x, int planes, int h, int w, int top, int l
  * 16-byte multiples, where upa_copy_view does not apply). */
 int upa_copy_rows(const float* src, long rows, int cols, long lds, float* dst, long ldd, void* stream);
 
+/* ---- segmentation validation: mask IoU and mask true positives on bit masks ----------------------------------------------------
+ * Bit layout of every entry below: a mask of mh x mw pixels is words = ceil(mh * mw / 32) uint32, bit k of word w = pixel 32 w + k
+ * in row-major order.  Bits past mh * mw in the last word are zero when one of these entries writes them; every reader masks them
+ * off.  Areas are int32 pixel counts; every count is an integer below 2^24, so the f32 IoU
+ *     inter / ((area_a + area_b) - inter + eps)
+ * is the value of the reference's float matmul form (utils/metrics.py:146-161) in any summation order.
+ *
+ * upa_pack_mask_bits: ground-truth masks -> bits (b, max_gt, words) + areas (b, max_gt); rows k >= ngt[b] are zero.
+ *   form UPA_MASKS_PLANES: src = (rows, mh, mw) binary planes, the per-instance form (models/yolo/segment/val.py:136, :139-141): the
+ *     plane of (image i, label k) is row base[i] + k, base = exclusive prefix sum of ngt (on the device); bit = v > 0.5; planes at or
+ *     past `rows` read as empty.  src_type UPA_MASK_U8 | UPA_MASK_F32.
+ *   form UPA_MASKS_OVERLAP: src = (b, mh, mw) index maps (val.py:131-134): label k of image i is v == k + 1; `rows` is ignored.
+ *     src_type UPA_MASK_U8 | UPA_MASK_I32 | UPA_MASK_F32.
+ *   ngt: (b,) int32 on the device, or NULL = max_gt labels in every image. */
+enum { UPA_MASKS_PLANES = 0, UPA_MASKS_OVERLAP = 1 };
+enum { UPA_MASK_U8 = 0, UPA_MASK_F32 = 1, UPA_MASK_I32 = 2 };
+int upa_pack_mask_bits(const void* src, int src_type, int form, long rows, int b, int max_gt, int mh, int mw, const int32_t* ngt,
+                       uint32_t* bits, int32_t* areas, void* stream);
+/* mask_iou (utils/metrics.py:146-161) on bit rows: out[i, j] = IoU(a[i], b[j]), a = (n, words), b = (m, words), npix pixels per
+ * mask, areas as upa_pack_mask_bits writes them.  out: (n, m) f32. */
+int upa_mask_iou_bits(const uint32_t* a, const int32_t* area_a, int n, const uint32_t* b, const int32_t* area_b, int m, int npix,
+                      float eps, float* out, void* stream);
+/* The mask half of SegmentationValidator for one batch (models/yolo/segment/val.py:94-117 postprocess with process_mask, :145-172
+ * _process_batch, utils/metrics.py:146-161 mask_iou, engine/validator.py:267-308 match_predictions), fused: the mask of detection d is
+ * process_mask(..., upsample = False) (utils/ops.py:517-545) - coefficients . protos, crop_mask with box x (crop_sx, crop_sy), > 0 -
+ * bit for bit what upa_process_mask writes in mode 0 with out = (mh, mw); it lives in LDS only, is ANDed and popcounted against the
+ * label rows of the detection's class, and the matching is upa_match_predictions' (best same-class label per detection, ties to the
+ * larger label index; per (label, threshold) the smallest claiming detection index wins).
+ *   protos: NHWC (b, mh, mw, nm) view, pixel stride ldp, f32 | bf16; rows: (b, max_det) rows of ld floats [box, conf, cls, nm
+ *   coefficients] as upa_nms_gather_extra writes them; counts (b,), gt_cls - the class of label l of image i is gt_cls[(i * max_gt + l) * gt_cls_ld]: 1 for a (b, max_gt) f32 array,
+ *   5 for the (b, max_gt, 5) label rows of upa_match_predictions -, gt_bits / gt_area from upa_pack_mask_bits,
+ *   ngt (b,): all on the device and read there (no host sync, no memset node: graph-capturable).  iou_thresholds: 10 floats, HOST.
+ *   tp_m: (b, max_det, 10) bytes, rows past counts zero.
+ *   Optional (NULL = not written) outputs for tests and mask_iou: pred_bits (b, max_det, words) with pred_area (b, max_det) - both or
+ *   neither - and iou_out (b, max_det, max_gt) f32; class-unequal pairs, rows past counts and columns past ngt are 0.
+ *   workspace: upa_segment_match_workspace_bytes(b, max_det) bytes (each detection's best label and IoU between the two launches).
+ * UPA_EINVAL for null required pointers, nm or ldp that are not 16-byte groups, a max_gt whose claim table exceeds LDS or a short
+ * workspace; UPA_EUNSUPPORTED for nm > 128, another dtype or a map whose bit rows exceed the LDS of a workgroup.  A refused call
+ * launches nothing. */
+size_t upa_segment_match_workspace_bytes(int b, int max_det);
+int upa_segment_match(const void* protos, int b, int mh, int mw, int nm, int ldp, int dtype, const float* rows, int ld, int max_det,
+                      const int32_t* counts, float crop_sx, float crop_sy, const float* gt_cls, int gt_cls_ld, const uint32_t* gt_bits,
+                      const int32_t* gt_area, const int32_t* ngt, int max_gt, const float* iou_thresholds, int n_thr,
+                      unsigned char* tp_m, uint32_t* pred_bits, int32_t* pred_area, float* iou_out, void* workspace,
+                      size_t workspace_bytes, void* stream);
+/* The same from given detection masks (SegmentationValidator._process_batch alone, val.py:145-172): det_bits (b, max_det, words) with
+ * det_area (b, max_det) take the place of protos and coefficients; rows: (b, max_det) rows of ld >= 6 floats, the class in column 5. */
+int upa_segment_match_bits(const uint32_t* det_bits, const int32_t* det_area, int b, int mh, int mw, const float* rows, int ld,
+                           int max_det, const int32_t* counts, const float* gt_cls, int gt_cls_ld, const uint32_t* gt_bits, const int32_t* gt_area,
+                           const int32_t* ngt, int max_gt, const float* iou_thresholds, int n_thr, unsigned char* tp_m, float* iou_out,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- HIP graph helpers (capture a launch sequence once, replay per batch) -------------------------------------
  * upa_graph_begin / _end bracket a stream capture of upa_* launches; upa_graph_launch replays the instantiated graph.
  * Two rules for graphs that run concurrently with other graphs (several steps in flight on separate streams), both found

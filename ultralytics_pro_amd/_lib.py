@@ -16,6 +16,8 @@ import torch  # noqa: F401  (loads libamdhip64.so.7 first - see module docstring
 UPA_F32, UPA_BF16, UPA_U8_BGR_HWC = 0, 1, 2
 UPA_EUNSUPPORTED = -2
 ACT_NONE, ACT_SILU, ACT_RELU = 0, 1, 2
+MASKS_PLANES, MASKS_OVERLAP = 0, 1          # upa_pack_mask_bits: source form
+MASK_U8, MASK_F32, MASK_I32 = 0, 1, 2       # ... and source element type
 
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("UPA_HIP_LIB", _PKG / "libupa_hip.so"))
@@ -213,6 +215,12 @@ PROTOTYPES = {
     "upa_crop_mask": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "upa_resize_bilinear": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "upa_copy_rows": (_i, [_vp, C.c_long, _i, C.c_long, _vp, C.c_long, _vp]),
+    "upa_pack_mask_bits": (_i, [_vp, _i, _i, C.c_long, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "upa_mask_iou_bits": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _f, _vp, _vp]),
+    "upa_segment_match_workspace_bytes": (_sz, [_i, _i]),
+    "upa_segment_match": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp,
+                               _vp, _sz, _vp]),
+    "upa_segment_match_bits": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "upa_graph_begin": (_i, [_vp]),
     "upa_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "upa_graph_launch": (_i, [_vp, _vp]),

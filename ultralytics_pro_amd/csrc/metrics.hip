@@ -2,6 +2,7 @@
 // Replaces ultralytics/utils/metrics.py:54-74 as used by DetectionValidator._process_batch (models/yolo/detect/val.py:286).
 // One lane per (i, j) pair, j fastest (coalesced row writes); f32 arithmetic in the reference's operation order.
 #include "common.h"
+#include "match_claim.h"
 #pragma clang fp contract(off)
 
 __global__ __launch_bounds__(256) void box_iou_kernel(const float* b1, const float* b2, float* out, int N, int M, float eps) {
@@ -65,12 +66,6 @@ extern "C" int upa_scale_boxes(float* rows, long n, int row_stride, float gain, 
 // label index - what the reversed ascending sort gives for the stable small-array case.
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
-constexpr int MP_NT = 10;
-
-struct MatchThr {
-  float v[MP_NT];
-};
-
 __global__ __launch_bounds__(256) void match_predictions_kernel(const float* det, const int* counts, int max_det, const float* gt,
                                                                 const int* ngt, int max_gt, MatchThr thr, float eps,
                                                                 unsigned char* tp) {
@@ -98,16 +93,9 @@ __global__ __launch_bounds__(256) void match_predictions_kernel(const float* det
         const float iou = inter / ((ax2 - ax1) * (ay2 - ay1) + (bx2 - bx1) * (by2 - by1) - inter + eps);
         if (iou >= bi) { bi = iou; bl = l; }
       }
-      if (bl >= 0)
-        for (int k = 0; k < MP_NT; ++k)
-          if (bi >= thr.v[k]) atomicMin(&s_min[bl * MP_NT + k], d);
     }
-    __syncthreads();
-    // rows of this round can only be decided once every detection with a smaller index has claimed its label: detections
-    // are visited in increasing rounds, and a later round can only LOWER no minimum below an index of this round
-    if (d < max_det)
-      for (int k = 0; k < MP_NT; ++k) T[d * MP_NT + k] = (d < N && bl >= 0 && bi >= thr.v[k] && s_min[bl * MP_NT + k] == d) ? 1 : 0;
-    __syncthreads();
+    // rows of this round can only be decided once every detection with a smaller index has claimed its label (match_claim.h)
+    match_claim_round(s_min, d, N, max_det, bl, bi, thr, T);
   }
 }
 }  // namespace

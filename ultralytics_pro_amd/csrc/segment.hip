@@ -9,6 +9,7 @@
 //    taps read (nm-deep dot products, one-pixel halo) into LDS, crops them with crop_mask's float comparisons, resamples with
 //    torch's upsample_bilinear2d rule (align_corners = False, source index clamped at 0), thresholds at > 0 and writes bytes.
 #include "common.h"
+#include "mask_dot.h"
 
 namespace {
 
@@ -204,30 +205,10 @@ __global__ __launch_bounds__(256) void process_mask_kernel(PMArgs A) {
     for (int i = tid; i < wr * wc; i += 256) {
       const int wy = i / wc, wx = i - wy * wc;
       const int py = A.top + ys0 + wy, px = A.left + xs0 + wx;
-      float acc = 0.f;  // masks_in @ protos: k ascending, one fma per term
-      if (A.bf16) {
-        const bf16_t* pr = (const bf16_t*)A.protos + ((size_t)img * A.mh * A.mw + (size_t)py * A.mw + px) * A.ldp;
-        for (int k = 0; k < A.nm; k += 8) {
-          const u32x4 v = *reinterpret_cast<const u32x4*>(pr + k);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            acc = fmaf(coef[k + 2 * e], __uint_as_float(v[e] << 16), acc);
-            acc = fmaf(coef[k + 2 * e + 1], __uint_as_float(v[e] & 0xffff0000u), acc);
-          }
-        }
-      } else {
-        const float* pr = (const float*)A.protos + ((size_t)img * A.mh * A.mw + (size_t)py * A.mw + px) * A.ldp;
-        for (int k = 0; k < A.nm; k += 4) {
-          const f32x4 v = *reinterpret_cast<const f32x4*>(pr + k);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc = fmaf(coef[k + e], v[e], acc);
-        }
-      }
-      if (A.mode == 0) {
-        const float fx = (float)px, fy = (float)py;
-        const bool in = fx >= cx1 && fx < cx2 && fy >= cy1 && fy < cy2;
-        acc = in ? acc : 0.f;
-      }
+      float acc;  // masks_in @ protos: k ascending, one fma per term (mask_dot.h)
+      if (A.bf16) acc = mask_dot_bf16(coef, (const bf16_t*)A.protos + ((size_t)img * A.mh * A.mw + (size_t)py * A.mw + px) * A.ldp, A.nm);
+      else acc = mask_dot_f32(coef, (const float*)A.protos + ((size_t)img * A.mh * A.mw + (size_t)py * A.mw + px) * A.ldp, A.nm);
+      if (A.mode == 0) acc = mask_in_crop((float)px, (float)py, cx1, cy1, cx2, cy2) ? acc : 0.f;
       win[i] = acc;
     }
     __syncthreads();

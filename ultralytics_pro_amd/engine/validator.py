@@ -1,4 +1,4 @@
-"""Validation loop of the detect path on the HIP kernels, one process per GPU (reference: engine/validator.py:195-260 and
+"""Validation loop of the detect and segment paths on the HIP kernels, one process per GPU (reference: engine/validator.py:195-260 and
 models/yolo/detect/val.py:168-288).
 
 Per batch shard: model forward -> `non_max_suppression` with the validator's defaults (conf 0.001, iou 0.7, multi_label,
@@ -20,8 +20,10 @@ from ..utils.nms import nms_raw
 
 
 class DetectionValidator:
+    accepts_segment = False  # a Segment head needs mask statistics next to the box ones: SegmentationValidator below
+
     def __init__(self, model=None, conf: float = 0.001, iou: float = 0.7, max_det: int = 300, max_gt: int = 64):
-        if model is not None and any(type(m).__name__ == "Segment" for m in model.modules()):
+        if model is not None and not self.accepts_segment and any(type(m).__name__ == "Segment" for m in model.modules()):
             raise L.UpaError("segmentation models (Segment head) cannot be validated here: mask mAP is out of scope")
         self.model, self.conf, self.iou, self.max_det, self.max_gt = model, conf, iou, max_det, max_gt
         self.reset()
@@ -112,21 +114,139 @@ class DetectionValidator:
         gcls, ngt = dp.gather_ragged(gcls, ngt)
         return rows, cnt, gcls, ngt
 
-    def get_stats(self):
-        """{"tp", "conf", "pred_cls", "target_cls"} numpy arrays over all images of all ranks (val.py:212-240) and the class
-        metrics `DetMetrics.process` derives from them."""
+    stat_cols = 12  # conf | cls | tp (10 IoU thresholds)
+
+    def _gathered(self):
+        """(kept statistics rows of all images of all ranks (n, stat_cols) f32, target classes (m,) f32) as numpy arrays."""
         rows, cnt, gcls, ngt = (t.cpu() for t in self.gather_stats())
         cnt, ngt = cnt.tolist(), ngt.tolist()
         sel = [rows[i, :cnt[i]] for i in range(len(cnt))]
-        allr = torch.cat(sel, 0).numpy() if sel else np.zeros((0, 12), np.float32)
+        allr = torch.cat(sel, 0).numpy() if sel else np.zeros((0, self.stat_cols), np.float32)
         tcls = np.concatenate([gcls[i, :ngt[i]].numpy() for i in range(len(ngt))]) if ngt else np.zeros(0, np.float32)
-        stats = dict(tp=allr[:, 2:].astype(bool), conf=allr[:, 0], pred_cls=allr[:, 1], target_cls=tcls)
-        if len(stats["tp"]) and len(tcls):
-            p, r, f1, ap, uc = M.ap_per_class(stats["tp"], stats["conf"], stats["pred_cls"], tcls)
+        return allr, tcls
+
+    @staticmethod
+    def _class_metrics(tp, conf, pred_cls, tcls):
+        """{p, r, f1, ap, classes, mean} of one true-positive matrix (`Metric` of DetMetrics / SegmentMetrics)."""
+        if len(tp) and len(tcls):
+            p, r, f1, ap, uc = M.ap_per_class(tp, conf, pred_cls, tcls)
             mp, mr, map50, map5095 = M.mean_results(p, r, ap)
         else:
             p = r = f1 = np.zeros(0)
             ap, uc = np.zeros((0, 10)), np.zeros(0, int)
             mp = mr = map50 = map5095 = 0.0
-        stats.update(p=p, r=r, f1=f1, ap=ap, classes=uc, mean=(mp, mr, map50, map5095))
+        return dict(p=p, r=r, f1=f1, ap=ap, classes=uc, mean=(mp, mr, map50, map5095))
+
+    def get_stats(self):
+        """{"tp", "conf", "pred_cls", "target_cls"} numpy arrays over all images of all ranks (val.py:212-240) and the class
+        metrics `DetMetrics.process` derives from them."""
+        allr, tcls = self._gathered()
+        stats = dict(tp=allr[:, 2:12].astype(bool), conf=allr[:, 0], pred_cls=allr[:, 1], target_cls=tcls)
+        stats.update(self._class_metrics(stats["tp"], stats["conf"], stats["pred_cls"], tcls))
+        return stats
+
+
+class SegmentationValidator(DetectionValidator):
+    """Validation of a Segment model: box AND mask P / R / mAP50 / mAP50-95 (models/yolo/segment/val.py:94-172, utils/metrics.py
+    SegmentMetrics.process).  Per batch, all on the device with fixed shapes and no host sync: val-mode NMS -> the kept anchors' mask
+    coefficients (`upa_nms_gather_extra`) -> box true positives (`upa_match_predictions`) -> mask true positives
+    (`upa_segment_match`: the predicted masks are assembled, ANDed and popcounted against the packed label masks on the chip; no
+    mask buffer exists).  The statistics rows are 22 wide: conf | cls | tp | tp_m.
+
+    Scope: the validator's default mask path, `process_mask` at proto resolution.  `save_json` / `save_txt` (which switch the
+    reference to `process_mask_native`), RLE export and plots are not provided."""
+
+    accepts_segment = True
+    stat_cols = 22
+
+    def __init__(self, model=None, conf: float = 0.001, iou: float = 0.7, max_det: int = 300, max_gt: int = 64, overlap_mask: bool = True):
+        self.overlap_mask = overlap_mask
+        super().__init__(model, conf, iou, max_det, max_gt)
+
+    def reset(self):
+        super().reset()
+        self._tpm = []
+
+    # ---- per batch ------------------------------------------------------------------------------------------------------
+    def pack_masks(self, labels: dict, batch_size: int, proto_hw, device):
+        """labels["masks"] -> (bit rows (B, max_gt, words) int32, areas (B, max_gt) int32, see utils.metrics.pack_mask_bits) for the
+        labels `pack_labels` packs (same order, same padded width): SegmentationValidator._prepare_batch (segment/val.py:119-143).
+        With `overlap_mask` (the default) the masks are (B, h, w) index maps, instance k + 1 of an image being its label k as
+        `Format` leaves them; else (n, h, w) binary planes in label order.  Masks that are not at proto resolution are resampled
+        with `upa_resize_bilinear` and thresholded at > 0.5 (val.py:138-141); an index map is expanded to planes for that."""
+        mh, mw = int(proto_hw[0]), int(proto_hw[1])
+        bi = labels["batch_idx"].view(-1).long().cpu()
+        per = [int((bi == j).sum()) for j in range(batch_size)]
+        cap = max(self.max_gt, max(per + [1]))
+        ngt = torch.tensor(per, dtype=torch.int32).to(device)
+        masks = labels["masks"]
+        if masks.dtype not in (torch.uint8, torch.bool, torch.float32, torch.int32):
+            masks = masks.float()
+        masks = masks.to(device)
+        overlap = self.overlap_mask
+        if overlap and masks.dtype == torch.bool:
+            masks = masks.to(torch.uint8)
+        if tuple(masks.shape[1:]) != (mh, mw):
+            if overlap:  # an index map cannot be interpolated: its instances as planes first (val.py:133-134)
+                planes = [masks[j][None] == torch.arange(1, k + 1, device=device).view(k, 1, 1).to(masks.dtype) for j, k in enumerate(per) if k]
+                masks = torch.cat(planes, 0) if planes else masks[:0]
+                overlap = False
+            src = masks.float().contiguous()
+            n, h, w = src.shape
+            masks = torch.empty((n, mh, mw), dtype=torch.float32, device=device)
+            if n:
+                L.check(L.lib().upa_resize_bilinear(src.data_ptr(), n, h, w, 0, 0, h, w, masks.data_ptr(), mh, mw,
+                                                    L.current_stream(device)), "resize_bilinear")
+        elif not overlap and masks.dtype == torch.int32:
+            masks = masks.float()
+        return M.pack_mask_bits(masks, batch_size, cap, ngt, overlap=overlap)
+
+    def update(self, preds, gt: torch.Tensor, ngt: torch.Tensor, gt_bits: torch.Tensor, gt_area: torch.Tensor, key=None,
+               record: bool = True):
+        """preds: the Segment model's eval output (y, (raw, mc, protos)); gt / ngt from `pack_labels`, gt_bits / gt_area from
+        `pack_masks` of the same images.  `key` names the step's static buffers and `record = False` leaves the statistics to a later
+        `add_batch_stats` when the call is captured into a graph.  Returns the step's device tensors (out, counts, tp, tp_m)."""
+        from ..engine import runtime as R
+        from ..utils import ops
+        y, mc, p = ops._seg_parts(preds, 0)
+        b, nm, a = mc.shape
+        out, counts, keep = nms_raw(y, self.conf, self.iou, multi_label=True, max_det=self.max_det, key=key)
+        rows = R.alloc_plain((b, self.max_det, 6 + nm), torch.float32, y.device, key=(key, "segval_rows") if key is not None else None)
+        L.check(L.lib().upa_nms_gather_extra(mc.data_ptr(), b, nm, a, keep.data_ptr(), counts.data_ptr(), int(self.max_det), out.data_ptr(),
+                                             rows.data_ptr(), 6 + nm, L.current_stream(y.device)), "nms_gather_extra")
+        return self.update_detections(out, counts, gt, ngt, rows, ops._protos_nhwc(p), gt_bits, gt_area, key=key, record=record)
+
+    def update_detections(self, out: torch.Tensor, counts: torch.Tensor, gt: torch.Tensor, ngt: torch.Tensor, rows: torch.Tensor,
+                          protos: torch.Tensor, gt_bits: torch.Tensor, gt_area: torch.Tensor, key=None, record: bool = True):
+        """Already post-processed detections - out (B, max_det, 6), rows (B, max_det, 6 + nm) with the mask coefficients, counts -
+        and the protos (NHWC view): match boxes and masks and keep the batch's statistics."""
+        from ..engine import runtime as R
+        mh, mw = int(protos.shape[2]), int(protos.shape[3])
+        tp = R.alloc_plain(tuple(out.shape[:2]) + (10,), torch.uint8, out.device, key=(key, "tp")) if key is not None else None
+        tp = M.match_predictions_batched(out, counts, gt, ngt, out=tp)
+        # the boxes are in network-input pixels, 4 x the proto map (segment/val.py:105: imgsz = 4 * proto.shape[2:])
+        tp_m = M.match_masks_batched(protos, rows, counts, (4 * mh, 4 * mw), gt, gt_bits, gt_area, ngt, key=key)
+        if record:
+            self.add_batch_stats(out, counts, tp, gt, ngt, tp_m)
+        return out, counts, tp, tp_m
+
+    def add_batch_stats(self, out: torch.Tensor, counts: torch.Tensor, tp: torch.Tensor, gt: torch.Tensor, ngt: torch.Tensor,
+                        tp_m: torch.Tensor):
+        """Statistics of a batch whose matching already ran (e.g. inside a captured step)."""
+        super().add_batch_stats(out[:, :, :6], counts, tp, gt, ngt)
+        self._tpm.append(tp_m.clone())
+
+    # ---- end of run -----------------------------------------------------------------------------------------------------
+    def local_stats(self):
+        """As DetectionValidator.local_stats with (I, max_det, 22) rows: conf | cls | tp | tp_m."""
+        rows, cnt, gcls, ngt = super().local_stats()
+        return torch.cat([rows, torch.cat(self._tpm, 0).float()], 2).contiguous(), cnt, gcls, ngt
+
+    def get_stats(self):
+        """What DetectionValidator.get_stats returns for the boxes, plus "tp_m" and "seg" = {p, r, f1, ap, classes, mean} of the
+        masks: the same `ap_per_class` on the mask true positives, as SegmentMetrics.process does (utils/metrics.py)."""
+        allr, tcls = self._gathered()
+        stats = dict(tp=allr[:, 2:12].astype(bool), tp_m=allr[:, 12:22].astype(bool), conf=allr[:, 0], pred_cls=allr[:, 1], target_cls=tcls)
+        stats.update(self._class_metrics(stats["tp"], stats["conf"], stats["pred_cls"], tcls))
+        stats["seg"] = self._class_metrics(stats["tp_m"], stats["conf"], stats["pred_cls"], tcls)
         return stats

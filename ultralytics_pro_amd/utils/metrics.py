@@ -1,4 +1,4 @@
-"""Detection validation metrics with the reference's function names (ultralytics/utils/metrics.py,
+"""Detection and segmentation validation metrics with the reference's function names (ultralytics/utils/metrics.py,
 engine/validator.py:267-308, models/yolo/detect/val.py:274-288).
 
 IoU and the greedy prediction-to-label matching run on the GPU for a whole batch at once (`upa_match_predictions` on the
@@ -58,6 +58,142 @@ def process_batch(pred_boxes: torch.Tensor, pred_cls: torch.Tensor, gt_boxes: to
     cnt = torch.tensor([n], dtype=torch.int32, device=dev)
     ng = torch.tensor([m], dtype=torch.int32, device=dev)
     return match_predictions_batched(det, cnt, gt, ng)[0].cpu().numpy().astype(bool)
+
+
+# ---- mask IoU and mask true positives on bit masks (csrc/segval.hip) -------------------------------------------------------------------
+# A mask of mh x mw pixels is ceil(mh * mw / 32) int32 words, bit k of word w = pixel 32 w + k.  (torch has no uint32 arithmetic worth
+# the name: the rows are int32 tensors that the kernels read as uint32.)
+
+_SRC_TYPE = {torch.uint8: L.MASK_U8, torch.bool: L.MASK_U8, torch.float32: L.MASK_F32, torch.int32: L.MASK_I32}
+
+
+def mask_words(npix: int) -> int:
+    return (int(npix) + 31) // 32
+
+
+def pack_mask_bits(src: torch.Tensor, batch: int, max_gt: int, ngt: torch.Tensor | None = None, overlap: bool = False, key=None):
+    """Ground-truth masks on the GPU -> (bits (batch, max_gt, words) int32, areas (batch, max_gt) int32) (`upa_pack_mask_bits`).
+    `overlap`: src = (batch, mh, mw) index maps, label k of image b is `src[b] == k + 1` (segment/val.py:131-134; uint8, int32 or
+    float32); else src = (rows, mh, mw) binary planes, bit = v > 0.5, the plane of (image b, label k) being row sum(ngt[:b]) + k
+    (uint8 / bool or float32).  Rows k >= ngt[b] are zero; ngt None = max_gt labels everywhere."""
+    from ..engine import runtime as R
+    L.require_gpu(src, "pack_mask_bits")
+    if src.dim() != 3 or src.dtype not in _SRC_TYPE or (src.dtype == torch.int32 and not overlap):
+        raise L.UpaError(f"pack_mask_bits: {tuple(src.shape)} {src.dtype} masks are outside the supported forms")
+    src = src.contiguous()
+    mh, mw = int(src.shape[1]), int(src.shape[2])
+    dev = src.device
+    bits = R.alloc_plain((batch, max_gt, mask_words(mh * mw)), torch.int32, dev, key=(key, "gt_bits") if key is not None else None)
+    areas = R.alloc_plain((batch, max_gt), torch.int32, dev, key=(key, "gt_area") if key is not None else None)
+    if bits.numel() == 0 or mh * mw == 0:
+        return bits.zero_(), areas.zero_()
+    if src.shape[0] == 0:  # no plane at all: a valid (never dereferenced) address for the null check
+        src = torch.zeros((1, mh, mw), dtype=src.dtype, device=dev)
+    L.check(L.lib().upa_pack_mask_bits(src.data_ptr(), _SRC_TYPE[src.dtype], L.MASKS_OVERLAP if overlap else L.MASKS_PLANES,
+                                       int(src.shape[0]), int(batch), int(max_gt), mh, mw, None if ngt is None else ngt.data_ptr(),
+                                       bits.data_ptr(), areas.data_ptr(), L.current_stream(dev)), "pack_mask_bits")
+    return bits, areas
+
+
+def mask_iou(mask1: torch.Tensor, mask2: torch.Tensor, eps: float = 1e-7) -> torch.Tensor:
+    """(N, n), (M, n) flattened 0/1 masks (float or uint8) on the GPU -> (N, M) IoU (utils/metrics.py:146-161): the rows are packed
+    to bits, the intersections are popcounts (`upa_mask_iou_bits`); bit for bit the reference's float matmul form for 0/1 rows."""
+    L.require_gpu(mask1, "mask_iou")
+    L.require_gpu(mask2, "mask_iou")
+    n, m, npix = int(mask1.shape[0]), int(mask2.shape[0]), int(mask1.shape[1])
+    if int(mask2.shape[1]) != npix:
+        raise L.UpaError(f"mask_iou: rows of {npix} and {int(mask2.shape[1])} pixels")
+    out = torch.empty((n, m), dtype=torch.float32, device=mask1.device)
+    if out.numel() == 0:
+        return out
+    if npix == 0:
+        return out.zero_()
+    prep = lambda t: (t if t.dtype in (torch.uint8, torch.bool, torch.float32) else t.float()).reshape(t.shape[0], 1, npix)  # noqa: E731
+    b1, a1 = pack_mask_bits(prep(mask1), 1, n)
+    b2, a2 = pack_mask_bits(prep(mask2), 1, m)
+    L.check(L.lib().upa_mask_iou_bits(b1.data_ptr(), a1.data_ptr(), n, b2.data_ptr(), a2.data_ptr(), m, npix, float(eps), out.data_ptr(),
+                                      L.current_stream(mask1.device)), "mask_iou")
+    return out
+
+
+def _cls_ld(gt: torch.Tensor) -> int:
+    """Label classes as (B, max_gt) f32 or as the (B, max_gt, 5) [cls, box] rows of `match_predictions_batched`: the element stride."""
+    if gt.dtype != torch.float32 or not gt.is_contiguous() or gt.dim() not in (2, 3):
+        raise L.UpaError("label classes must be a contiguous float32 (B, max_gt) or (B, max_gt, 5) tensor")
+    return 1 if gt.dim() == 2 else int(gt.shape[2])
+
+
+def _match_workspace(b, max_det, dev, key):
+    from ..engine import runtime as R
+    nbytes = L.lib().upa_segment_match_workspace_bytes(int(b), int(max_det))
+    return R.alloc_plain((max(nbytes // 8, 1),), torch.int64, dev, key=(key, "segmatch_ws") if key is not None else None), nbytes
+
+
+def match_masks_batched(protos: torch.Tensor, rows: torch.Tensor, counts: torch.Tensor, imgsz, gt_cls: torch.Tensor,
+                        gt_bits: torch.Tensor, gt_area: torch.Tensor, ngt: torch.Tensor, iouv=IOUV, out: torch.Tensor | None = None,
+                        pred_bits: torch.Tensor | None = None, pred_area: torch.Tensor | None = None,
+                        iou_out: torch.Tensor | None = None, key=None) -> torch.Tensor:
+    """Mask true-positive matrices of a whole batch on the GPU (`upa_segment_match`; models/yolo/segment/val.py:94-117 + :145-172):
+    protos - the Segment head's (B, nm, mh, mw) NHWC view, f32 or bf16 -, rows (B, max_det, 6 + nm) [box, conf, cls, coefficients] +
+    counts (B,) as `nms_raw` returns them for a Segment output, imgsz = (H, W) of the network input the boxes are in, gt_cls
+    (B, max_gt) f32 or the (B, max_gt, 5) label rows, gt_bits / gt_area from `pack_mask_bits`, ngt (B,) -> (B, max_det, 10) uint8, no host sync.  The predicted masks
+    exist on the chip only; `pred_bits` (B, max_det, words) int32 + `pred_area` (B, max_det) int32 and `iou_out` (B, max_det, max_gt)
+    f32 receive them for tests."""
+    from ..engine import runtime as R
+    L.require_gpu(rows, "match_masks")
+    vp = R.view_of(protos)
+    b, max_det, ld = rows.shape
+    dev = rows.device
+    thr = np.ascontiguousarray(np.asarray(iouv, dtype=np.float32))
+    tp = out if out is not None else R.alloc_plain((b, max_det, thr.shape[0]), torch.uint8, dev, key=(key, "tp_m") if key is not None else None)
+    ws, nbytes = _match_workspace(b, max_det, dev, key)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    L.check(L.lib().upa_segment_match(vp.ptr, vp.n, vp.h, vp.w, vp.c, vp.ld, vp.dtype, rows.data_ptr(), int(ld), int(max_det),
+                                      counts.data_ptr(), float(vp.w / imgsz[1]), float(vp.h / imgsz[0]), gt_cls.data_ptr(), _cls_ld(gt_cls),
+                                      gt_bits.data_ptr(), gt_area.data_ptr(), ngt.data_ptr(), int(gt_cls.shape[1]), thr.ctypes.data,
+                                      int(thr.shape[0]), tp.data_ptr(), ptr(pred_bits), ptr(pred_area), ptr(iou_out), ws.data_ptr(),
+                                      nbytes, L.current_stream(dev)), "segment_match")
+    return tp
+
+
+def match_mask_bits_batched(det_bits: torch.Tensor, det_area: torch.Tensor, det: torch.Tensor, counts: torch.Tensor, map_hw,
+                            gt_cls: torch.Tensor, gt_bits: torch.Tensor, gt_area: torch.Tensor, ngt: torch.Tensor, iouv=IOUV,
+                            iou_out: torch.Tensor | None = None) -> torch.Tensor:
+    """`match_masks_batched` from given detection masks (`upa_segment_match_bits`): det_bits (B, max_det, words) int32 + det_area
+    (B, max_det) int32 of (mh, mw) = map_hw masks, det (B, max_det, >= 6) rows with the class in column 5."""
+    L.require_gpu(det, "match_mask_bits")
+    b, max_det, ld = det.shape
+    dev = det.device
+    thr = np.ascontiguousarray(np.asarray(iouv, dtype=np.float32))
+    tp = torch.empty((b, max_det, thr.shape[0]), dtype=torch.uint8, device=dev)
+    ws, nbytes = _match_workspace(b, max_det, dev, None)
+    L.check(L.lib().upa_segment_match_bits(det_bits.data_ptr(), det_area.data_ptr(), int(b), int(map_hw[0]), int(map_hw[1]),
+                                           det.data_ptr(), int(ld), int(max_det), counts.data_ptr(), gt_cls.data_ptr(), _cls_ld(gt_cls),
+                                           gt_bits.data_ptr(), gt_area.data_ptr(), ngt.data_ptr(), int(gt_cls.shape[1]), thr.ctypes.data,
+                                           int(thr.shape[0]), tp.data_ptr(), None if iou_out is None else iou_out.data_ptr(),
+                                           ws.data_ptr(), nbytes, L.current_stream(dev)), "segment_match_bits")
+    return tp
+
+
+def process_batch_masks(pred_masks: torch.Tensor, pred_cls: torch.Tensor, gt_masks: torch.Tensor, gt_cls: torch.Tensor) -> np.ndarray:
+    """Mask true-positive matrix of one image (segment/val.py:165-170) - the single-image form of the batched matching: pred_masks
+    (N, h, w) and gt_masks (M, h, w) binary (uint8 / bool / float32) on the GPU, classes (N,), (M,) -> (N, 10) bool."""
+    n, m = int(pred_cls.shape[0]), int(gt_cls.shape[0])
+    if m == 0 or n == 0:
+        return np.zeros((n, len(IOUV)), dtype=bool)
+    L.require_gpu(pred_masks, "process_batch_masks")
+    dev = pred_masks.device
+    hw = tuple(int(v) for v in pred_masks.shape[1:])
+    if tuple(int(v) for v in gt_masks.shape[1:]) != hw:
+        raise L.UpaError(f"process_batch_masks: predicted masks {hw} and label masks {tuple(gt_masks.shape[1:])} differ in size")
+    pb, pa = pack_mask_bits(pred_masks, 1, n)
+    gb, ga = pack_mask_bits(gt_masks, 1, m)
+    det = torch.zeros((1, n, 6), dtype=torch.float32, device=dev)
+    det[0, :, 5] = pred_cls.float()
+    cnt = torch.tensor([n], dtype=torch.int32, device=dev)
+    ng = torch.tensor([m], dtype=torch.int32, device=dev)
+    tp = match_mask_bits_batched(pb, pa, det, cnt, hw, gt_cls.float().view(1, m).contiguous(), gb, ga, ng)
+    return tp[0].cpu().numpy().astype(bool)
 
 
 # ---- host-side AP arithmetic.  These three functions are a numerical RECIPE, not a design: validation mAP has to come out equal to
