@@ -24,3 +24,18 @@ def test_pack_targets_grows_past_64_rows():
               "bboxes": torch.rand(n, 4).clamp(0.05, 0.9)}
     gt, ngt = pack_targets(labels, 2, 640, 640)
     assert tuple(gt.shape) == (2, 192, 5) and ngt.tolist() == [n, 0]
+
+
+def test_pack_targets_refuses_a_class_outside_the_model():
+    """The loss kernels index the class logits with the label unchecked: a class id outside [0, nc) is an error on the host."""
+    import pytest
+    from ultralytics_pro_amd._lib import UpaError
+    from ultralytics_pro_amd.engine.trainer import pack_targets
+    box = torch.tensor([[.5, .5, .2, .2], [.3, .4, .1, .2]])
+    ok = {"batch_idx": torch.tensor([0., 1.]), "cls": torch.tensor([0., 7.]), "bboxes": box}
+    gt, ngt = pack_targets(ok, 2, 64, 64, nc=8)
+    assert ngt.tolist() == [1, 1] and gt[1, 0, 0] == 7
+    assert torch.equal(pack_targets(dict(ok, cls=torch.tensor([0., 8.])), 2, 64, 64)[0][1, 0, 0], torch.tensor(8.))  # unchecked without nc
+    for bad in (8., -1., 80.):
+        with pytest.raises(UpaError, match="outside"):
+            pack_targets(dict(ok, cls=torch.tensor([0., bad])), 2, 64, 64, nc=8)

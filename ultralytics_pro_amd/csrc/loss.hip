@@ -529,7 +529,17 @@ extern "C" int upa_detection_loss_scaled(const float* const* feats, float* const
     a += hs[l] * ws[l];
   }
   L.A = a;
+  // every refusal comes before the first launch.  The top-k kernel takes TOPK distinct anchors per box (torch.topk raises for k
+  // larger than the size), and keeps the per-gt metric row of all anchors in dynamic LDS: A * 4 bytes + 2 KB static <= 160 KB
+  // (imgsz up to ~1400 square)
+  UPA_CHECK_ARG(a >= TOPK, "detection_loss: %d anchors, the assigner takes the %d best per box", a, TOPK);
+  UPA_CHECK_ARG((size_t)a * sizeof(float) + 2048 <= 160 * 1024, "detection_loss: %d anchors do not fit the LDS metric row", a);
   UPA_CHECK_ARG(workspace_bytes >= upa_detection_loss_workspace_bytes(b, a, max_gt), "detection_loss: workspace too small");
+  // raise the top-k kernel's dynamic LDS limit to the whole CU (the 64 KB default ends at imgsz ~ 900)
+  if (hipError_t e = upa_full_lds<tal_topk_kernel>(); e != hipSuccess) {
+    upa_set_error("detection_loss: cannot raise the LDS limit of tal_topk: %s", hipGetErrorString(e));
+    return UPA_ELAUNCH;
+  }
   char* wsb = (char*)workspace;
   double* scal = (double*)wsb;                // [0] tss, [1..3] sums, then n_fg
   int* n_fg = (int*)(scal + 4);
@@ -542,15 +552,6 @@ extern "C" int upa_detection_loss_scaled(const float* const* feats, float* const
   const long total = (long)b * a;
   const int grid = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
   hipLaunchKernelGGL(loss_decode_kernel, dim3(grid), dim3(256), 0, s, L, pbox);
-  {
-    // the per-gt metric row of all anchors lives in dynamic LDS: raise the kernel's limit to the whole CU (the 64 KB default
-    // ends at imgsz ~ 900) and refuse shapes past it (A * 4 bytes + 2 KB static <= 160 KB: imgsz up to ~1400 square)
-    if (hipError_t e = upa_full_lds<tal_topk_kernel>(); e != hipSuccess) {
-      upa_set_error("detection_loss: cannot raise the LDS limit of tal_topk: %s", hipGetErrorString(e));
-      return UPA_ELAUNCH;
-    }
-    UPA_CHECK_ARG((size_t)a * sizeof(float) + 2048 <= 160 * 1024, "detection_loss: %d anchors do not fit the LDS metric row", a);
-  }
   hipLaunchKernelGGL(tal_topk_kernel, dim3(b * max_gt), dim3(256), (size_t)a * sizeof(float), s, L, pbox, gt, n_gt, cand);
   hipLaunchKernelGGL(tal_resolve_kernel, dim3(b), dim3(256), 0, s, L, pbox, gt, n_gt, cand, asg, count, scal, n_fg);
   const long tot_c = total * nc;

@@ -977,7 +977,7 @@ class DetectionTrainer:
 
     def _upload_labels(self, labels, batch_size):
         imgsz_h, imgsz_w = self._imgsz
-        gt, ngt = pack_targets(labels, batch_size, imgsz_h, imgsz_w)
+        gt, ngt = pack_targets(labels, batch_size, imgsz_h, imgsz_w, nc=self.detect.nc)
         need = int(gt.shape[1])
         if self.gt_d is None or self.gt_d.shape[0] != batch_size or need > self.gt_d.shape[1]:
             if self._graphs is not None or self._capturing:
@@ -1182,12 +1182,13 @@ class DetectT(_Seq):
         return items
 
 
-def pack_targets(labels, batch_size, imgsz_h, imgsz_w, min_rows=MAX_GT):
+def pack_targets(labels, batch_size, imgsz_h, imgsz_w, min_rows=MAX_GT, nc=None):
     """loss.py:445-461 on the host: (n,) image index, (n,) class, (n,4) normalised xywh -> padded (B, rows, 5)
     [cls, x1, y1, x2, y2] in pixels + per-image counts (host tensors; a few hundred bytes per step).  `rows` = the largest
     per-image count rounded up to a multiple of 64 (at least `min_rows`), as the reference pads to counts.max().  Boxes
     whose xyxy coordinates sum to zero are dropped: the reference masks them (`mask_gt = gt_bboxes.sum(2) > 0`,
-    loss.py:489), so they never take part in the assignment."""
+    loss.py:489), so they never take part in the assignment.  With `nc` given, a class id outside [0, nc) is refused here: the
+    kernels index the class logits with it unchecked (the reference fails on the host with an index error)."""
     bi = labels["batch_idx"].view(-1).cpu().long()
     cls = labels["cls"].view(-1).cpu().float()
     bb = labels["bboxes"].view(-1, 4).cpu().float()
@@ -1196,6 +1197,9 @@ def pack_targets(labels, batch_size, imgsz_h, imgsz_w, min_rows=MAX_GT):
     xy, wh = xywh[:, :2], xywh[:, 2:] / 2
     xyxy = torch.cat([xy - wh, xy + wh], 1)
     keep = xyxy.sum(1) > 0
+    if nc is not None and bool(((cls < 0) | (cls >= nc)).any()):
+        bad = cls[(cls < 0) | (cls >= nc)]
+        raise L.UpaError(f"label class {float(bad[0]):g} is outside [0, {nc}) of the model's classes")
     per = [((bi == j) & keep).nonzero().view(-1) for j in range(batch_size)]
     most = max([int(ix.numel()) for ix in per] + [1])
     rows = max(min_rows, (most + 63) // 64 * 64)
