@@ -30,7 +30,10 @@ def box_iou(box1: torch.Tensor, box2: torch.Tensor, eps: float = 1e-7) -> torch.
 
 def greedy_nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> torch.Tensor:
     """Greedy hard-NMS; survivor iff IoU <= thr with every kept higher-scored box; IoU has no eps
-    (utils/nms.py:239-296).  Stable descending sort: ties keep ascending index order."""
+    (utils/nms.py:239-296).  Stable descending sort: ties keep ascending index order.
+    The early exit on `inter.sum() == 0` is part of the result, not a shortcut: it is what makes degenerate boxes survive.  A kept
+    box of zero area (w == 0 or h == 0) intersects nothing, so every later box stays; without the exit two zero-area boxes would
+    meet as 0 / (0 + 0 - 0) = NaN, and `NaN <= thr` is False - suppressed, wherever they lie."""
     if boxes.numel() == 0:
         return torch.empty((0,), dtype=torch.int64)
     x1, y1, x2, y2 = boxes.unbind(1)

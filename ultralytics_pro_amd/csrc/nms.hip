@@ -22,8 +22,11 @@
 // batch of 32) is written only for flagged images (nms_candidates with `only_redo`), which then take the 16384-prefix and at last the
 // exact top-max_nms path.  The result is the reference's in every case: greedy NMS over the score-ordered candidates cut at max_nms,
 // cut at max_det.
-// IoU arithmetic follows the reference op for op in f32 (class offset added to the boxes first, areas from the offset
-// boxes, no eps, survivor iff iou <= thr); FP contraction is disabled so no FMA changes a keep/suppress decision.
+// IoU arithmetic follows the reference in f32, in its operation order (class offset added to the boxes first, areas from the offset
+// boxes, no eps, survivor iff iou <= thr); FP contraction is disabled so no FMA changes a keep/suppress decision.  One rule is not in
+// the arithmetic: a pair that does not intersect (inter == 0) never suppresses.  TorchNMS.nms leaves its suppression step early when
+// the kept box intersects nothing, which is what lets zero-area boxes (w == 0 or h == 0) survive each other there - the quotient
+// alone would be 0 / (0 + 0 - 0) = NaN, "not kept", wherever the two boxes lie (tests/test_hip_postprocess.py, the degenerate scenes).
 #include "common.h"
 #pragma clang fp contract(off)
 
@@ -592,7 +595,9 @@ __device__ __forceinline__ bool iou_gt(float ax1, float ay1, float ax2, float ay
   const float h = fmaxf(fminf(ay2, by2) - fmaxf(ay1, by1), 0.f);
   const float inter = w * h;
   const float iou = inter / (aarea + barea - inter);
-  return !(iou <= thr);  // reference keeps `iou <= thr`; NaN is not kept either
+  // reference keeps `iou <= thr`; a NaN from inf / NaN coordinates is not kept either (inter is NaN then, not 0); inter == 0 keeps:
+  // for two zero-area boxes the quotient is 0 / 0, and the reference never gets that far (its early exit on an empty intersection)
+  return inter != 0.f && !(iou <= thr);
 }
 // (A wave-uniform shortcut - skip the IEEE division when no lane's box overlaps the broadcast one at all, inter == 0 - was measured
 // SLOWER: the vote and the branch cost more than the division they save in one wave out of a few: phase 1 1744 -> 2501 cycles per chunk
