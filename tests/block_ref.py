@@ -1,0 +1,371 @@
+"""Float64 CPU restatement of the whole-block kernels (csrc/c2f_fused.hip, c2f_stream.hip, c2f16_stream.hip, c2f64.hip, conv_pair.hip,
+detect_stream.hip) as chains of `stage`s with DECIDED rounding points, and the per-element bound those kernels are held to.
+
+A whole-block kernel keeps its intermediates in LDS and rounds them to bf16 between stages.  Whether such a rounding may fall the other
+way in the kernel (another f32 summation order) is decided per element here: `stage` carries a bound e on |kernel's stored value - reference's
+stored value| through the chain, and at a bf16 store turns the pre-rounding bound into the number of ulps the stored value can move - 0
+wherever the interval around the float64 value holds no rounding boundary.  On the non-negative `positive` family (no cancellation: S = |v|)
+most block outputs come out with bound 0: the kernel must reproduce the reference's bf16 bits there, and is within one ulp elsewhere.
+
+Plain torch on the CPU; nothing here imports the HIP package's kernels.  tests/test_block_ref.py pins these functions; tests/test_hip_blocks.py
+compares every whole-block form with them (CASES below is the list both files walk)."""
+
+import functools
+
+import torch
+import torch.nn.functional as F
+
+from tests.conv_ref import ACT_NONE, ACT_SILU, F64, U24, act_ref, conv_ref
+
+BF16 = torch.bfloat16
+
+
+def rn_bf16(a):
+    """Round-to-nearest-even of float64 values into bf16 (8 significant bits), returned as float64.  One rounding: not through float32."""
+    a = a.to(F64).contiguous()
+    tiny = (a != 0) & (a.abs() < 2.0 ** -120)
+    assert not bool(tiny.any()), "bf16 subnormal range: not restated here"
+    bits = a.view(torch.int64)
+    drop = 52 - 7
+    lsb = (bits >> drop) & 1
+    out = (bits + ((1 << (drop - 1)) - 1) + lsb) & ~((1 << drop) - 1)
+    return out.view(F64)
+
+
+def store_bf16(a, e_pre):
+    """The bf16 store of float64 values `a` known to e_pre: (t, e_out) = (rn(a), max(|rn(a + e_pre) - t|, |rn(a - e_pre) - t|)).  Rounding is
+    monotone: every value of [a - e_pre, a + e_pre] rounds into [t - e_out, t + e_out], and e_out is 0 where the interval holds no boundary."""
+    t = rn_bf16(a)
+    return t, torch.maximum((rn_bf16(a + e_pre) - t).abs(), (rn_bf16(a - e_pre) - t).abs())
+
+
+def stage(x, e_in, w, bias, k, stride, act, residual=None, e_res=None, out_dtype=BF16):
+    """One Conv (+ folded BN bias, activation, optional residual) with its store.  x: the reference's stored input (float64 / float32
+    holding bf16-exact values), e_in >= 0: bound on |kernel's stored input - x| per element (None: exact).  Returns (t, e_out): the
+    reference's stored output as float64 and the bound on |kernel's stored output - t|.
+
+    Pre-rounding bound (the kernels add the residual in f32 before their single rounding: `v[e] += bf16 bits << 16` after `silu_rcp`,
+    c2f_fused.hip:180-183 / 284-287, c2f_stream.hip:171-176, c2f16_stream.hip:228-231, c2f64.hip:77-81, conv_pair.hip:270-277):
+
+      e_pre = L (1.01 (K + 1) 2^-24 S + conv(e_in, |w|)) + (|v| + 6) 2^-24 |act(v)| [+ e_res + 2^-23 |act(v) + res|]
+
+    L and the activation term are those of conv_ref.conv_bound (SiLU: L = 1.1; silu_rcp = v * v_rcp_f32(1 + __expf(-v)), common.h:89, is
+    the "reciprocal" form that term already covers).  bf16 store: t = rn(a), e_out = max(|rn(a + e_pre) - t|, |rn(a - e_pre) - t|) -
+    rounding is monotone, so this is 0 where [a - e_pre, a + e_pre] holds no rounding boundary.  f32 store: t = a, e_out = e_pre + 2^-23 |a|."""
+    x = x.to(F64)
+    cin = x.shape[1]
+    K = cin * k * k
+    pad = k // 2
+    v, S, a = conv_ref(x, w, bias, residual, k, stride, pad, act)
+    lip = 1.1 if act == ACT_SILU else 1.0
+    e_pre = 1.01 * (K + 1) * U24 * S
+    if e_in is not None:
+        e_pre = e_pre + F.conv2d(e_in.to(F64), w.to(F64).abs(), None, stride=stride, padding=pad)
+    e_pre = lip * e_pre
+    if act == ACT_SILU:
+        e_pre = e_pre + (v.abs() + 6.0) * U24 * act_ref(v, act).abs()
+    if residual is not None:
+        e_pre = e_pre + (0.0 if e_res is None else e_res.to(F64)) + 2.0 ** -23 * a.abs()
+    if out_dtype == BF16:
+        return store_bf16(a, e_pre)
+    assert out_dtype == torch.float32
+    return a, e_pre + 2.0 ** -23 * a.abs()
+
+
+def ulp_bf16(t):
+    """The spacing of bf16 values at |t| (float64; the lower spacing at a power of two is half of it)."""
+    m, e = torch.frexp(t.to(F64).abs().clamp_min(2.0 ** -120))
+    return torch.ldexp(torch.ones_like(m), e - 8)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# chains.  Weights are dicts of (w OIHW, bias) pairs; `stage_fn` is `stage` or a stand-in with its signature (the f32 emulation
+# and the negative controls of tests/test_block_ref.py), so that every consumer walks the same chain.
+# ---------------------------------------------------------------------------------------------------------------------
+def bottleneck_pair(x, e_x, wts, shortcut, stage_fn=stage, trace=None):
+    """x + cv2(cv1(x)) of a Bottleneck (block.py:644-668): two 3x3 stages, the residual added to the second before its rounding."""
+    (wa, ba), (wb, bb) = wts
+    t, et = stage_fn(x, e_x, wa, ba, 3, 1, ACT_SILU)
+    b, eb = stage_fn(t, et, wb, bb, 3, 1, ACT_SILU, residual=x if shortcut else None, e_res=e_x if shortcut else None)
+    if trace is not None:
+        trace += [(t, et), (b, eb)]
+    return b, eb
+
+
+def c2f(x, wts, n, shortcut, stage_fn=stage, skip_cv1=False, trace=None):
+    """cv1 -> chunk -> n x (3x3, 3x3 [+ input]) -> concat -> cv2 (block.py:457-488).  wts: {"cv1", "m": [(a, b)] * n, "cv2"}.
+    skip_cv1: x IS cv1's stored output (the Bottleneck + cv2 launch, upa_bottleneck_pair_cv2)."""
+    if skip_cv1:
+        y, e = x.to(F64), None
+    else:
+        y, e = stage_fn(x, None, *wts["cv1"], 1, 1, ACT_SILU)
+    c = y.shape[1] // 2
+    ys = [(y[:, :c], None if e is None else e[:, :c]), (y[:, c:], None if e is None else e[:, c:])]
+    if trace is not None:
+        trace.append((y, e))
+    for i in range(n):
+        ys.append(bottleneck_pair(ys[-1][0], ys[-1][1], wts["m"][i], shortcut, stage_fn, trace))
+    cat = torch.cat([q[0] for q in ys], 1)
+    ecat = torch.cat([torch.zeros_like(q[0]) if q[1] is None else q[1] for q in ys], 1)
+    out, eo = stage_fn(cat, ecat, *wts["cv2"], 1, 1, ACT_SILU)
+    if trace is not None:
+        trace.append((out, eo))
+    return out, eo
+
+
+def c2f_down(x, wts, stage_fn=stage, trace=None):
+    """C2f(32, 32, n = 1, shortcut), its bf16 store, then Conv 3x3 stride 2 (upa_c2f16_down_fused)."""
+    o, eo = c2f(x, wts, 1, True, stage_fn, trace=trace)
+    return stage_fn(o, eo, *wts["down"], 3, 2, ACT_SILU)
+
+
+def detect_branch(x, wts, stage_fn=stage):
+    """3x3 -> 3x3 -> 1x1 f32 logits of one Detect branch (head.py:94-100).  Returns (logits, e_logits, e_t2)."""
+    t1, e1 = stage_fn(x, None, *wts[0], 3, 1, ACT_SILU)
+    t2, e2 = stage_fn(t1, e1, *wts[1], 3, 1, ACT_SILU)
+    lg, el = stage_fn(t2, e2, *wts[2], 1, 1, ACT_NONE, out_dtype=torch.float32)
+    return lg, el, e2
+
+
+def detect_level(x, wts, stage_fn=stage):
+    """Both branches of a Detect level: {"box": 3 convs, "cls": 3 convs} -> (box logits, e, cls logits, e, [e_t2 box, e_t2 cls])."""
+    bl, be, b2 = detect_branch(x, wts["box"], stage_fn)
+    cl, ce, c2 = detect_branch(x, wts["cls"], stage_fn)
+    return bl, be, cl, ce, [b2, c2]
+
+
+def upcat(u, skip):
+    """Virtual Upsample + Concat: input construction only."""
+    return torch.cat([F.interpolate(u, scale_factor=2, mode="nearest"), skip], 1)
+
+
+def detect_decode(bl, be, cl, ce, stride):
+    """Decode in float64 from the reference logits (N, 64, H, W) / (N, nc, H, W) with their bounds.  Returns a dict:
+      box (N, 4, A) xywh, e_box; score (N, nc, A), e_score.
+    scores  sigma(l), bound e / 4 + 2 * 2^-24 (the project's sigmoid bound: slope <= 1 / 4, v_exp_f32 + v_rcp_f32);
+    DFL     per side E = sum p_j j with the f64 softmax p; bound 1.01 sum p_j |j - E| e_j + 16 * 2^-24 * 15 (first order with the 1.01 cover,
+            and a 16-term f32 softmax and dot);
+    xywh    detect_epi.h:69-71 forms x1 = cx - d0, x2 = cx + d2 and then (x1 + x2) / 2 or x2 - x1, times the stride: the side bounds
+            pass through as (e0 + e2) / 2 or e0 + e2; the roundings of x1 and x2 are 2^-24 (|x1| + |x2|) whatever is left after the
+            subtraction (a width of 1 px at column 60 carries the ulp of 60, not of 1: this term comes from those lines, it is not
+            part of 4 * 2^-24 |value|), and the last add and the multiply are within 4 * 2^-24 |value|."""
+    n, _, h, w = bl.shape
+    lg = bl.reshape(n, 4, 16, h * w)
+    el = be.reshape(n, 4, 16, h * w)
+    p = torch.softmax(lg, 2)
+    j = torch.arange(16, dtype=F64).view(1, 1, 16, 1)
+    E = (p * j).sum(2)
+    eE = 1.01 * (p * (j - E.unsqueeze(2)).abs() * el).sum(2) + 16 * U24 * 15
+    ax = (torch.arange(w, dtype=F64) + 0.5).repeat(h)
+    ay = (torch.arange(h, dtype=F64) + 0.5).repeat_interleave(w)
+    x1, y1, x2, y2 = ax - E[:, 0], ay - E[:, 1], ax + E[:, 2], ay + E[:, 3]
+    box = torch.stack([(x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1], 1) * stride
+    ex, ey = eE[:, 0] + eE[:, 2], eE[:, 1] + eE[:, 3]
+    rx, ry = U24 * (x1.abs() + x2.abs()), U24 * (y1.abs() + y2.abs())
+    e_box = torch.stack([ex / 2 + rx, ey / 2 + ry, ex + rx, ey + ry], 1) * stride + 4 * U24 * box.abs()
+    score = torch.sigmoid(cl).reshape(n, -1, h * w)
+    e_score = (ce / 4 + 2 * U24).reshape(n, -1, h * w)
+    return {"box": box, "e_box": e_box, "score": score, "e_score": e_score}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# input families
+# ---------------------------------------------------------------------------------------------------------------------
+def _bf(t):
+    return t.to(BF16).float()
+
+
+def impulse_pixels(h, w, seams_x=(), seams_y=()):
+    """The pixels the `impulse` family lights: the four corners, one pixel on each side of every seam column (strip or tile boundary
+    `s`: columns s - 1 and s, on alternating rows) and of every seam row (tile boundary, or the row where a row part ends)."""
+    px = {(0, 0), (0, w - 1), (h - 1, 0), (h - 1, w - 1)}
+    for i, s in enumerate(seams_x):
+        if 0 < s < w:
+            r = (h // 2 + i) % h
+            px |= {(r, s - 1), (r, s)}
+    for i, s in enumerate(seams_y):
+        if 0 < s < h:
+            c = (w // 2 + i) % w
+            px |= {(s - 1, c), (s, c)}
+    return sorted(px)
+
+
+def family_input(family, g, n, c, h, w, seams_x=(), seams_y=()):
+    """x (n, c, h, w) float32, bf16-exact.  positive: uniform in [0, 1.5].  impulse: zero except impulse_pixels, dealt out to the images
+    in turn (pixel j goes to image j % n: every image gets different pixels), values in [0.5, 1.5] per channel."""
+    if family == "positive":
+        return _bf(torch.rand(n, c, h, w, generator=g) * 1.5)
+    assert family == "impulse", family
+    x = torch.zeros(n, c, h, w)
+    for j, (py, px) in enumerate(impulse_pixels(h, w, seams_x, seams_y)):
+        x[j % n, :, py, px] = 0.5 + torch.rand(c, generator=g)
+    return _bf(x)
+
+
+def family_conv(family, g, cout, cin, k, signed_tail=False, wscale=3.0):
+    """(w OIHW bf16-exact, bias f32) of one BN-folded conv.  Weights in [0, 3 / K] so that outputs stay O(1); bias in [0, 0.5], zero in the
+    3x3 stages of `impulse` (outside the lit pixels the 3x3 convs then see only the constant SiLU(cv1 bias) field and the zero padding
+    around it: a padding value of SiLU(bias) or a leak from another image shows as whole taps).  signed_tail: a Detect 1x1 tail -
+    weights in [-6 / K, 6 / K], bias in [-2, 1]: its output is an f32 logit, no rounding follows, and the scores span (0, 1).
+    wscale: the 3 of 3 / K.  The C2f(c1, 128, n = 2) cases use 1: with 64-channel halves a 3x3 stage has K = 576 and cv1 up to K = 384, and at
+    3 / K the four chained 3x3 stages left only 38 to 70 % of the block outputs decided (below the 50 % the conditions of
+    tests/test_block_ref.py ask for at c1 = 384); at 1 / K the bias carries more of every sum, a flipped tie moves its consumers less, and
+    91 to 99 % are decided.  The family's scale was changed, not the condition."""
+    K = cin * k * k
+    if signed_tail:
+        return _bf((torch.rand(cout, cin, k, k, generator=g) * 2 - 1) * 6.0 / K), torch.rand(cout, generator=g) * 3 - 2
+    wt = _bf(torch.rand(cout, cin, k, k, generator=g) * wscale / K)
+    bias = torch.rand(cout, generator=g) * 0.5
+    if family == "impulse" and k == 3:
+        bias = torch.zeros(cout)
+    return wt, bias
+
+
+def c2f_weights(family, g, c1, c, c2, n, down=None, wscale=3.0):
+    def fc(*a):
+        return family_conv(family, g, *a, wscale=wscale)
+    wts = {"cv1": fc(2 * c, c1, 1), "m": [(fc(c, c, 3), fc(c, c, 3)) for _ in range(n)], "cv2": fc(c2, (2 + n) * c, 1)}
+    if down:
+        wts["down"] = family_conv(family, g, down, c2, 3)
+    return wts
+
+
+def detect_weights(family, g, nc):
+    out = {}
+    for name, c, cout in (("box", 64, 64), ("cls", 80, nc)):
+        out[name] = [family_conv(family, g, c, 64, 3), family_conv(family, g, c, c, 3), family_conv(family, g, cout, c, 1, signed_tail=True)]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the cases of tests/test_hip_blocks.py (tests/test_block_ref.py checks the reference's conditions on every one of them)
+# ---------------------------------------------------------------------------------------------------------------------
+def _shapes(T, TY, min_h=1, min_w=1, even=False):
+    """(N, H, W) for strip / tile width T and row seam TY (tile height, or the rows of a part): W in {1, T - 1, T, T + 1, 2 T + 1},
+    H in {1, 2, 3, an odd height above two row steps, a height with a seam inside}; N = 2 and 3.  min_h / min_w: the form's own lower
+    limits replace the 1s; even: a virtual Upsample in front needs even maps, so the odd sizes move up by one."""
+    shp = [(2, 1, 1), (3, 2, T - 1), (2, 3, T), (2, 5, T + 1), (3, TY + 3, 2 * T + 1)]
+    out = []
+    for n, h, w in shp:
+        h, w = max(h, min_h), max(w, min_w)
+        if even:
+            h, w = h + (h & 1), w + (w & 1)
+        if (n, h, w) not in out:
+            out.append((n, h, w))
+    return out
+
+
+def _cases():
+    cs = []
+
+    def add(form, shapes, seams, **kw):
+        tx, ty = seams
+        for n, h, w in shapes:
+            k2 = dict(kw)
+            if k2["opts"].get("c2f_stream_rows") == "whole":  # one part: that many INPUT rows (even, >= 4)
+                k2["opts"] = dict(k2["opts"], c2f_stream_rows=max(4, (h + 1) & ~1))
+            cs.append(dict(form=form, n=n, h=h, w=w, seams_x=tuple(range(tx, w, tx)) if tx else (), seams_y=tuple(range(ty, h, ty)) if ty else (), **k2))
+
+    # upa_c2f_fused (32, 16, 32, 1): 16 x 16 tiles (c2f_fused.hip:36) | 20-column strips, two rows per step (c2f16_stream.hip:56-58; h, w >= 2)
+    add("c2f", _shapes(16, 16), (16, 16), c1=32, c=16, c2=32, nb=1, sc=True, opts=dict(c2f_stream=1), kernel="c2f16 tile")
+    add("c2f", _shapes(20, 4, 2, 2), (20, 4), c1=32, c=16, c2=32, nb=1, sc=True, opts=dict(c2f_stream_rows=4), kernel="c2f16 stream")
+    add("c2f", _shapes(20, 4, 2, 2)[-2:], (20, 0), c1=32, c=16, c2=32, nb=1, sc=True, opts=dict(), kernel="c2f16 stream")
+    # upa_c2f_fused (64, 32, 64, 2): 16 x 16 | 10 x 16 tiles (c2f_fused.hip:646-659), 20-column strips with either role set (c2f_stream.hip:57, 794)
+    for sc in (True, False):
+        add("c2f", _shapes(16, 16) if sc else _shapes(16, 16)[-2:], (16, 16), c1=64, c=32, c2=64, nb=2, sc=sc, opts=dict(c2f_stream=1, c2f32_th=16), kernel="c2f32 tile16")
+        add("c2f", _shapes(16, 10)[-2:], (16, 10), c1=64, c=32, c2=64, nb=2, sc=sc, opts=dict(c2f_stream=1, c2f32_th=10), kernel="c2f32 tile10")
+        add("c2f", _shapes(20, 4) if sc else _shapes(20, 4)[-2:], (20, 4), c1=64, c=32, c2=64, nb=2, sc=sc, opts=dict(c2f_stream_rows=4), kernel="c2f32 stream2")
+        add("c2f", _shapes(20, 4)[-2:], (20, 4), c1=64, c=32, c2=64, nb=2, sc=sc, opts=dict(c2f_stream=2, c2f_stream_rows=4), kernel="c2f32 stream roles1")
+    add("c2f", _shapes(20, 4)[-1:], (20, 0), c1=64, c=32, c2=64, nb=2, sc=True, opts=dict(), kernel="c2f32 stream2")
+    # upa_c2f_fused (64, 32, 64, 1): the n = 1 line-buffer kernel and its tile form
+    add("c2f", _shapes(20, 4), (20, 4), c1=64, c=32, c2=64, nb=1, sc=True, opts=dict(c2f_stream_rows=4), kernel="c2f32 stream1")
+    add("c2f", _shapes(16, 16)[-2:], (16, 16), c1=64, c=32, c2=64, nb=1, sc=False, opts=dict(c2f_stream=1), kernel="c2f32 tile n1")
+    # upa_c2f32_up_fused: c1 128 | 192, with and without the half-resolution source, line-buffer and tile form
+    for c1, upc in ((128, 0), (128, 64), (192, 0), (192, 128)):
+        ev = bool(upc)
+        add("c2f", _shapes(20, 4, even=ev)[1:] if c1 == 192 else _shapes(20, 4, even=ev)[-2:], (20, 4), c1=c1, c=32, c2=64, nb=1, sc=c1 == 128, upc=upc,
+            opts=dict(c2f_stream_rows=4), kernel="c2f32up stream1")
+        add("c2f", _shapes(16, 16, even=ev)[-2:], (16, 16), c1=c1, c=32, c2=64, nb=1, sc=c1 == 192, upc=upc, opts=dict(c2f_stream=1), kernel="c2f32up tile")
+    # upa_c2f16_down_fused: 10 output columns = 20 block columns per strip (c2f16_stream.hip:56-58), parts of `rows` input rows; h, w >= 2
+    for rows in (0, 4, "whole"):
+        add("c2f_down", _shapes(20, 4, 2, 2) if rows == 4 else _shapes(20, 4, 2, 2)[-2:], (20, 4 if rows == 4 else 0), c1=32, c=16, c2=32, nb=1, sc=True,
+            opts=dict(c2f_stream_rows=rows), kernel="c2f16 down")
+    # upa_c2f64_fused: 10 x 10 tiles for n = 2, 10 x 20 for n = 1 (c2f64.hip:378); 1, 3 and 6 input chunks
+    for nb, c1, upc, sc in ((2, 64, 0, True), (2, 192, 0, False), (2, 192, 128, True), (2, 384, 256, False), (1, 64, 0, False), (1, 192, 128, True), (1, 192, 0, False), (1, 384, 256, True)):
+        T = 10 if nb == 2 else 20
+        shp = _shapes(T, 10, even=bool(upc))
+        add("c2f", shp if c1 == 64 else shp[-2:], (T, 10), c1=c1, c=64, c2=128, nb=nb, sc=sc, upc=upc, opts=dict(), kernel="c2f64", **({"wscale": 1.0} if nb == 2 else {}))
+    # the Bottleneck pair kernels (conv_pair.hip): square 6 x 6 tiles forced through pair_tile32 / pair_tile64, and the host's own choice
+    for form, c, cm in (("pair", 32, 32), ("pair", 64, 64), ("pair_e", 64, 32), ("pair_cv2", 32, 32)):
+        for sc in (True, False):
+            t = "pair_tile64" if c == 64 else "pair_tile32"
+            add(form, _shapes(6, 6) if sc else _shapes(6, 6)[-2:], (6, 6), c=c, cm=cm, sc=sc, opts={t: 6}, kernel=form)
+        add(form, [(2, 17, 19)], (0, 0), c=c, cm=cm, sc=True, opts=dict(), kernel=form)
+    # upa_detect_level_stream: 30-column strips (detect_stream.hip:71), w >= 8, h >= 2, parts of 4 rows or the whole height
+    for nc in (80, 20):
+        for rows in (0, 4):
+            for keys in (0, 1):
+                shp = _shapes(30, 4, 2, 8)
+                add("detect", shp if (nc == 80 and rows == 4) else shp[-2:], (30, 4 if rows else 0), nc=nc, opts=dict(detect_stream=2, detect_stream_rows=rows, keys_only=keys),
+                    kernel="detect stream")
+    for i, c in enumerate(cs):
+        c["seed"] = 1000 + i
+        c["id"] = "-".join([c["kernel"].replace(" ", "_")] + [f"{k}{c[k]}" for k in ("c1", "c", "nb", "nc", "upc") if c.get(k)] + (["s"] if c.get("sc") else [])
+                           + [f"{c['n']}x{c['h']}x{c['w']}"] + [f"{k}{v}" for k, v in c["opts"].items()])
+    return cs
+
+
+CASES = _cases()
+FAMILIES = ("positive", "impulse")
+
+
+def case_data(case, family):
+    """The inputs and weights of one case (CPU float32, exact in their storage types)."""
+    g = torch.Generator().manual_seed(case["seed"] + (0 if family == "positive" else 500000))
+    n, h, w, form = case["n"], case["h"], case["w"], case["form"]
+    sx, sy = case["seams_x"], case["seams_y"]
+    d = {}
+    if form in ("c2f", "c2f_down"):
+        c1, upc = case["c1"], case.get("upc", 0)
+        if upc:
+            # the half-resolution source: positive or, for impulse, the lit pixels of the full map at half coordinates
+            d["u"] = family_input(family, g, n, upc, h // 2, w // 2, tuple(s // 2 for s in sx), tuple(s // 2 for s in sy))
+            d["skip"] = family_input(family, g, n, c1 - upc, h, w, sx, sy)
+            d["x"] = upcat(d["u"], d["skip"])
+        else:
+            d["x"] = family_input(family, g, n, c1, h, w, sx, sy)
+        d["wts"] = c2f_weights(family, g, c1, case["c"], case["c2"], case["nb"], down=64 if form == "c2f_down" else None, wscale=case.get("wscale", 3.0))
+    elif form in ("pair", "pair_e"):
+        d["x"] = family_input(family, g, n, case["c"], h, w, sx, sy)
+        d["wts"] = (family_conv(family, g, case["cm"], case["c"], 3), family_conv(family, g, case["c"], case["cm"], 3))
+    elif form == "pair_cv2":
+        d["x"] = family_input(family, g, n, 64, h, w, sx, sy)  # cv1's stored output [y0 | y1]
+        d["wts"] = c2f_weights(family, g, 64, 32, 64, 1)
+    else:
+        assert form == "detect", form
+        d["x"] = family_input(family, g, n, 64, h, w, sx, sy)
+        d["wts"] = detect_weights(family, g, case["nc"])
+    return d
+
+
+def case_reference(case, d, stage_fn=stage, trace=None):
+    """The chain of one case on its data -> (out, e_out) (Detect: the tuple of detect_level)."""
+    form = case["form"]
+    if form == "c2f":
+        return c2f(d["x"], d["wts"], case["nb"], case["sc"], stage_fn, trace=trace)
+    if form == "c2f_down":
+        return c2f_down(d["x"], d["wts"], stage_fn, trace=trace)
+    if form in ("pair", "pair_e"):
+        return bottleneck_pair(d["x"].to(F64), None, d["wts"], case["sc"], stage_fn, trace)
+    if form == "pair_cv2":
+        return c2f(d["x"], d["wts"], 1, case["sc"], stage_fn, skip_cv1=True, trace=trace)
+    return detect_level(d["x"], d["wts"], stage_fn)
+
+
+@functools.lru_cache(maxsize=None)
+def reference(case_index, family):
+    """(data, reference) of CASES[case_index], computed once per process and shared (treat as read-only)."""
+    case = CASES[case_index]
+    d = case_data(case, family)
+    with torch.no_grad():
+        return d, case_reference(case, d)
