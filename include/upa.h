@@ -134,15 +134,29 @@ int upa_bottleneck_pair_e(const void* x, int n, int h, int w, int c, int cmid, i
 
 
 /* First layer: reads the model input NCHW (f32 or bf16, 1..4 channels) directly, writes NHWC.   conv.py:188-197
- * w = device copy of the upa_pack_stem_weight output ([tap][ci][cout padded to 16] f32), bias f32[cout] on the device. */
+ * w = device copy of the upa_pack_stem_weight output ([tap][ci][cout padded to 16] f32), bias f32[cout] on the device.
+ * x aligned to its element size; a bf16 input that is not 16-byte aligned is staged through registers instead of by 16-byte LDS-DMA.
+ * UPA_EINVAL for n, h, w <= 0, pad >= k or an empty output. */
 size_t upa_stem_packed_weight_bytes(int cout, int cin, int k);
 int upa_pack_stem_weight(const float* w_oihw, int cout, int cin, int k, float* out /* host */);
 int upa_conv2d_stem_nchw(const void* x_nchw, int x_dtype, int n, int cin, int h, int w,
                          const float* w_oihw, const float* bias, void* y, int cout, int ldy,
                          int k, int stride, int pad, int act, int dtype, const upa_opts* opts, void* stream);
 
+/* Dispatch query of upa_conv2d_stem_nchw (pool = 0) / upa_conv2d_stem_nchw_pool2 (pool = 1): the scalar arguments of the launch, its
+ * upa_opts and the low four bits of the input address in; what the call would run out, or the negative UPA_E* code with which it would
+ * refuse (argument rules that do not look at a pointer).  Launches nothing.  The launcher and the query go through one selector.
+ *   bits 0-2   family: UPA_STEM_SCALAR | UPA_STEM_MFMA | UPA_STEM_MFMA_G16 (k 3, stride 1, pad 1, SiLU: 16-deep gather) | UPA_STEM_FUSED16 | UPA_STEM_FUSED32
+ *   bits 3-5   NT: 16-channel tiles of the (first) conv's output, 0 for the scalar kernel      bits 6-8  KS      bits 9-10  S (first conv)
+ *   bit 11     POOL          bit 12  SILU          bits 13-14  staging: UPA_STEM_STAGE_DMA (16-byte LDS-DMA) | _VGPR | _U8
+ *   bits 15-18 waves per workgroup          bit 19  float32 output (scalar kernel)          bits 32-62  workgroups launched */
+enum { UPA_STEM_SCALAR = 1, UPA_STEM_MFMA = 2, UPA_STEM_MFMA_G16 = 3, UPA_STEM_FUSED16 = 4, UPA_STEM_FUSED32 = 5 };
+enum { UPA_STEM_STAGE_DMA = 0, UPA_STEM_STAGE_VGPR = 1, UPA_STEM_STAGE_U8 = 2 };
+long long upa_stem_variant(int x_dtype, int n, int cin, int h, int w, int cout, int ldy, int k, int stride, int pad, int act, int dtype,
+                           int pool, const upa_opts* opts, int x_align);
+
 /* Conv(3,16,3,2,1)+SiLU -> Conv(16,32,3,2,1)+SiLU fused (yolov8n rows 0-1, cfg/models/v8/yolov8.yaml): bf16 NCHW input
- * (w % 8 == 0, h % 4 == 0), the 16-channel stem output only ever exists as an LDS tile.  w0 / b0: upa_pack_stem_weight
+ * (w % 8 == 0, h % 4 == 0, x 16-byte aligned: staged by LDS-DMA only), the 16-channel stem output only ever exists as an LDS tile.  w0 / b0: upa_pack_stem_weight
  * layout + folded bias; w1 / b1: upa_pack_conv_weight(UPA_BF16) layout + folded bias; y: NHWC bf16 (n, h/4, w/4, 32). */
 int upa_stem_conv_fused(const void* x, int n, int h, int w, const float* w0, const float* b0, const void* w1,
                         const float* b1, void* y, int ldy, const upa_opts* opts, void* stream);
@@ -157,6 +171,10 @@ int upa_stem_conv_fused_c(const void* x, int n, int h, int w, int k0, int c0, co
  * rows 0-1, cfg/models/v3/Detect/yolov3-rtdetr.yaml).  y: NHWC bf16 view (n, h / (2 s0), w / (2 s0), 2 * c0). */
 int upa_stem_conv_fused_s(const void* x, int n, int h, int w, int k0, int s0, int c0, const float* w0, const float* b0,
                           const void* w1, const float* b1, void* y, int ldy, const upa_opts* opts, void* stream);
+
+/* Dispatch query of upa_stem_conv_fused_s (upa_stem_conv_fused / _k / _c: k0 = 3, s0 = 2, c0 = 16 where they take no such argument), in the
+ * bit layout of upa_stem_variant.  The fused kernels stage by 16-byte LDS-DMA only: x_align != 0 is UPA_EINVAL, here and in the launch. */
+long long upa_stem_fused_variant(int n, int h, int w, int k0, int s0, int c0, int ldy, const upa_opts* opts, int x_align);
 
 /* ---- pooling / resampling / concat (HBM-bound) --------------------------------------------------------------- */
 /* nn.MaxPool2d(k, s, p) with -inf padding; pad_br>0 emulates nn.ZeroPad2d([0,pad_br,0,pad_br]) in front of it

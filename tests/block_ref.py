@@ -39,7 +39,7 @@ def store_bf16(a, e_pre):
     return t, torch.maximum((rn_bf16(a + e_pre) - t).abs(), (rn_bf16(a - e_pre) - t).abs())
 
 
-def stage(x, e_in, w, bias, k, stride, act, residual=None, e_res=None, out_dtype=BF16):
+def stage(x, e_in, w, bias, k, stride, act, residual=None, e_res=None, out_dtype=BF16, pad=None, store=None):
     """One Conv (+ folded BN bias, activation, optional residual) with its store.  x: the reference's stored input (float64 / float32
     holding bf16-exact values), e_in >= 0: bound on |kernel's stored input - x| per element (None: exact).  Returns (t, e_out): the
     reference's stored output as float64 and the bound on |kernel's stored output - t|.
@@ -51,11 +51,13 @@ def stage(x, e_in, w, bias, k, stride, act, residual=None, e_res=None, out_dtype
 
     L and the activation term are those of conv_ref.conv_bound (SiLU: L = 1.1; silu_rcp = v * v_rcp_f32(1 + __expf(-v)), common.h:89, is
     the "reciprocal" form that term already covers).  bf16 store: t = rn(a), e_out = max(|rn(a + e_pre) - t|, |rn(a - e_pre) - t|) -
-    rounding is monotone, so this is 0 where [a - e_pre, a + e_pre] holds no rounding boundary.  f32 store: t = a, e_out = e_pre + 2^-23 |a|."""
+    rounding is monotone, so this is 0 where [a - e_pre, a + e_pre] holds no rounding boundary.  f32 store: t = a, e_out = e_pre + 2^-23 |a|.
+    pad: the conv's zero padding (default k // 2; the k = 6, pad = 2 stem of tests/stem_ref.py states its own).  store: a stand-in for
+    store_bf16 with its signature (tests/stem_ref.py: the families whose outputs reach below 2^-120)."""
     x = x.to(F64)
     cin = x.shape[1]
     K = cin * k * k
-    pad = k // 2
+    pad = k // 2 if pad is None else pad
     v, S, a = conv_ref(x, w, bias, residual, k, stride, pad, act)
     lip = 1.1 if act == ACT_SILU else 1.0
     e_pre = 1.01 * (K + 1) * U24 * S
@@ -67,7 +69,7 @@ def stage(x, e_in, w, bias, k, stride, act, residual=None, e_res=None, out_dtype
     if residual is not None:
         e_pre = e_pre + (0.0 if e_res is None else e_res.to(F64)) + 2.0 ** -23 * a.abs()
     if out_dtype == BF16:
-        return store_bf16(a, e_pre)
+        return (store or store_bf16)(a, e_pre)
     assert out_dtype == torch.float32
     return a, e_pre + 2.0 ** -23 * a.abs()
 

@@ -257,3 +257,31 @@ def test_product_builds_on_cpu_but_refuses_to_run_there():
     assert sum(p.numel() for p in m.parameters()) == 3157200
     with pytest.raises(UpaError):
         m(torch.zeros(1, 3, 64, 64))
+
+
+def test_stem_dispatch_query_names_what_every_stem_case_runs():
+    """`upa_stem_variant` / `upa_stem_fused_variant` are host logic (the one selector the launchers go through): without a GPU they must answer
+    every case of tests/stem_ref.py with the family, instantiation, staging form, waves and workgroup count the case states, follow the
+    input's alignment (a bf16 input off its 16 bytes: VGPR staging for the plain stem, UPA_EINVAL for the fused pair) and refuse with the
+    launch's own codes."""
+    import ctypes as C
+    from tests import stem_ref as S
+    from ultralytics_pro_amd import _lib as L
+    lib = L.lib()
+    code = {"f32": L.UPA_F32, "bf16": L.UPA_BF16, "u8": L.UPA_U8_BGR_HWC}
+    for c in S.SINGLE_CASES + S.POOL_CASES:
+        ld = 16 + c["cout"] + (-c["cout"] % 8)
+        v = lib.upa_stem_variant(code[c["fmt"]], c["n"], c["cin"], c["h"], c["w"], c["cout"], ld, c["k"], c["s"], c["pad"], c["act"], code[c["out"]],
+                                 c["pool"], C.pointer(L.Opts(**c["opts"])), 2 if c["misalign"] else 0)
+        assert v >= 0 and S.decode_variant(v) == c["expect"], (c["id"], v)
+    for c in S.FUSED_CASES:
+        q = (c["n"], c["h"], c["w"], c["k0"], c["s0"], c["c0"], 2 * c["c0"] + 16, C.pointer(L.Opts(**c["opts"])))
+        v = lib.upa_stem_fused_variant(*q, 0)
+        assert v >= 0 and S.decode_variant(v) == c["expect"], (c["id"], v)
+        assert lib.upa_stem_fused_variant(*q, 2) == L.UPA_EINVAL
+    q = (L.UPA_BF16, 2, 3, 18, 136, 16, 32, 3, 2, 1, L.ACT_SILU, L.UPA_BF16, 0, None)
+    assert [S.decode_variant(lib.upa_stem_variant(*q, a))["staging"] for a in (0, 2, 8, 16)] == [S.DMA, S.VGPR, S.VGPR, S.DMA]
+    assert lib.upa_stem_variant(*q, 1) == L.UPA_EINVAL                                      # a bf16 input at an odd address
+    assert lib.upa_stem_variant(*q[:9], 3, *q[10:], 0) == L.UPA_EINVAL                      # pad >= k
+    assert lib.upa_stem_variant(*q[:3], 1, *q[4:9], 0, *q[10:], 0) == L.UPA_EINVAL          # h 1, k 3, pad 0: no output row
+    assert lib.upa_stem_variant(*q[:12], 1, None, 0) == L.UPA_EUNSUPPORTED                  # pool on a stride-2 stem

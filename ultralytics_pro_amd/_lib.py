@@ -14,6 +14,7 @@ from pathlib import Path
 import torch  # noqa: F401  (loads libamdhip64.so.7 first - see module docstring)
 
 UPA_F32, UPA_BF16, UPA_U8_BGR_HWC = 0, 1, 2
+UPA_EINVAL = -1
 UPA_EUNSUPPORTED = -2
 ACT_NONE, ACT_SILU, ACT_RELU = 0, 1, 2
 MASKS_PLANES, MASKS_OVERLAP = 0, 1          # upa_pack_mask_bits: source form
@@ -122,6 +123,8 @@ PROTOTYPES = {
     "upa_stem_conv_fused_k": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _op, _vp]),
     "upa_stem_conv_fused_c": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _op, _vp]),
     "upa_stem_conv_fused_s": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _op, _vp]),
+    "upa_stem_variant": (C.c_longlong, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _op, _i]),
+    "upa_stem_fused_variant": (C.c_longlong, [_i, _i, _i, _i, _i, _i, _i, _op, _i]),
     "upa_maxpool2d": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "upa_sppf_pool3": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "upa_upsample2x": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),

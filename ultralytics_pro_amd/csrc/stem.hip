@@ -21,6 +21,8 @@ struct StemParams {
   int wgs;  // stem_mfma_kernel: persistent workgroup cap
   int pool; // stem_mfma_kernel: 1 = y holds MaxPool2d(2, 2)(act(conv)) at (OH / 2, OW / 2)
   int no_xcd;  // 1 = tiles walked in slot order (upa_opts.no_xcd: A/B of the XCD-aware walk)
+  int dma;     // stem_mfma_kernel: 1 = the patch goes by 16-byte LDS-DMA (bf16 NCHW, W % 8 == 0, x 16-byte aligned: stem_select)
+  int pair;    // stem_conv_kernel: 1 = bf16 column pairs may be read as one aligned dword (W even, x 4-byte aligned: stem_select)
 #ifdef UPA_ABLATE
   int ablate;  // debug build only (upa_opts.ablate_stem)
 #endif
@@ -89,8 +91,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemParams p) {
     const int nlines = p.Cin * p.PR;
     const bool colOK = colid < ncols;
     const int ix = bf ? ixa + 2 * colid : ix0 + colid;
-    const bool evenW = (p.W & 1) == 0;
-    const bool pairFast = bf && ix >= 0 && ix + 1 < p.W && evenW;
+    const bool pairFast = bf && ix >= 0 && ix + 1 < p.W && p.pair;
     const bf16_t* xb = (const bf16_t*)p.x;
     const float* xf = (const float*)p.x;
     int ci = 0, row = line0;                  // line0 < PR always (LSTEP <= 8 <= PR for k >= 3 ... guarded below)
@@ -206,7 +207,8 @@ struct StemGeo {
 };
 
 // Stage the patch of output tile `tile` into `buf` (bf16 [3][PR][LS], column 0 = the tile's first input column rounded
-// down to 8).  bf16 NCHW inputs with W % 8 == 0 go by LDS-DMA (asynchronous: caller waits vmcnt); the rest through VGPRs.
+// down to 8).  16-byte aligned bf16 NCHW inputs with W % 8 == 0 go by LDS-DMA (p.dma, decided once by stem_select; asynchronous:
+// caller waits vmcnt); the rest through VGPRs.
 template <int KS, int S>
 __device__ __forceinline__ void stem_stage(const StemParams& p, int tile, unsigned short* buf, int tid, int wave) {
   using G = StemGeo<KS, S>;
@@ -217,7 +219,7 @@ __device__ __forceinline__ void stem_stage(const StemParams& p, int tile, unsign
   const int iy0 = tyi * G::TH * S - p.pad, ix0 = txi * G::TW * S - p.pad;
   const int ixa = ix0 & ~7;                     // two's complement: floors negatives too
   const int plane = p.H * p.W;                  // 3 * plane < 2^31 (checked by the launcher)
-  if (p.x_bf16 == 1 && (p.W & 7) == 0 && !UPA_ABL(p, 16)) {
+  if (p.dma && !UPA_ABL(p, 16)) {
     // lane = one 16-byte chunk (8 pixels of one line); chunks are entirely inside or outside the image
     const bf16_t* xb = (const bf16_t*)p.x + (size_t)n * 3 * plane;
 #pragma unroll
@@ -527,38 +529,46 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(const StemParams p) {
   }
 }
 
+// What a stem call runs: filled by stem_select / stem_fused_select below - the ONE place that chooses - and read both by the
+// launchers and by the dispatch queries (upa_stem_variant / upa_stem_fused_variant), so the two cannot disagree.
+enum { STEM_SCALAR = 1, STEM_MFMA = 2, STEM_MFMA_G16 = 3, STEM_FUSED16 = 4, STEM_FUSED32 = 5 };  // UPA_STEM_* of include/upa.h
+enum { STEM_STAGE_DMA = 0, STEM_STAGE_VGPR = 1, STEM_STAGE_U8 = 2 };
+struct StemSel {
+  int family, nt, ks, s, pool, silu, staging, waves, f32out;
+  long wgs;     // workgroups launched (scalar kernel: grid x * grid y)
+  size_t lds;   // scalar kernel: dynamic LDS bytes
+};
+static long long stem_variant_bits(const StemSel& v) {
+  return (long long)(v.family | v.nt << 3 | v.ks << 6 | v.s << 9 | v.pool << 11 | v.silu << 12 | v.staging << 13 | v.waves << 15 | v.f32out << 19) |
+         ((long long)v.wgs << 32);
+}
+
 template <int NT, int KS, int S>
-static void launch_stem_mfma(const StemParams& p, int n, hipStream_t st) {
+static void launch_stem_mfma(const StemParams& q, const StemSel& v, hipStream_t st) {
   using G = StemGeo<KS, S>;
-  StemParams q = p;
-  q.TW = G::TW; q.TH = G::TH;
-  q.tilesX = cdiv(p.OW, G::TW);
-  q.tilesY = cdiv(p.OH, G::TH);
-  const long ntiles = (long)q.tilesX * q.tilesY * n;
-  const int wgs = p.wgs > 0 ? p.wgs : 1024;
-  dim3 grid((unsigned)(ntiles < wgs ? ntiles : wgs));
+  const dim3 grid((unsigned)v.wgs);
   const size_t lds = (size_t)2 * G::ITEMS_PAD * 16 + 4 * G::TW * NT * 32;
   if constexpr (S == 1 && KS == 3) {
-    if (p.pool && p.pad == 1) {  // (SiLU only: the launcher's caller checked)
+    if (v.pool && v.family == STEM_MFMA_G16) {
       auto kern = stem_mfma_kernel<NT, KS, S, true, true, true>;
       (void)upa_full_lds<stem_mfma_kernel<NT, KS, S, true, true, true>>();
       hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, q);
       return;
     }
-    if (p.pool) {
+    if (v.pool) {
       auto kern = stem_mfma_kernel<NT, KS, S, true, true>;
       (void)upa_full_lds<stem_mfma_kernel<NT, KS, S, true, true>>();
       hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, q);
       return;
     }
-    if (p.pad == 1 && p.act == UPA_ACT_SILU) {
+    if (v.family == STEM_MFMA_G16) {
       auto kern = stem_mfma_kernel<NT, KS, S, true, false, true>;
       (void)upa_full_lds<stem_mfma_kernel<NT, KS, S, true, false, true>>();
       hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, q);
       return;
     }
   }
-  if (p.act == UPA_ACT_SILU) {
+  if (v.silu) {
     auto kern = stem_mfma_kernel<NT, KS, S, true>;
     (void)upa_full_lds<stem_mfma_kernel<NT, KS, S, true>>();
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, q);
@@ -569,10 +579,10 @@ static void launch_stem_mfma(const StemParams& p, int n, hipStream_t st) {
   }
 }
 template <int KS, int S>
-static void launch_stem_mfma_nt(const StemParams& p, int n, int nt, hipStream_t st) {
-  if (nt == 1) launch_stem_mfma<1, KS, S>(p, n, st);
-  else if (nt == 2) launch_stem_mfma<2, KS, S>(p, n, st);
-  else launch_stem_mfma<4, KS, S>(p, n, st);
+static void launch_stem_mfma_nt(const StemParams& p, const StemSel& v, hipStream_t st) {
+  if (v.nt == 1) launch_stem_mfma<1, KS, S>(p, v, st);
+  else if (v.nt == 2) launch_stem_mfma<2, KS, S>(p, v, st);
+  else launch_stem_mfma<4, KS, S>(p, v, st);
 }
 
 // ---- Stem + second conv fused (yolov8n: Conv(3,16,3,2) -> Conv(16,32,3,2), both SiLU; yolov8.yaml rows 0-1).
@@ -1164,27 +1174,24 @@ extern "C" int upa_conv2d_stem_nchw_pool2(const void* x, int x_dtype, int n, int
   return stem_nchw_impl(x, x_dtype, n, cin, h, w, wt, bias, y, cout, ldy, k, stride, pad, act, dtype, opts, stream, 1);
 }
 
-static int stem_nchw_impl(const void* x, int x_dtype, int n, int cin, int h, int w, const float* wt, const float* bias, void* y,
-                          int cout, int ldy, int k, int stride, int pad, int act, int dtype, const upa_opts* opts, void* stream, int pool) {
-  UPA_CHECK_ARG(x && wt && y, "stem: null pointer");
+// Every rule of upa_conv2d_stem_nchw[_pool2] that does not look at a pointer, and the choice of kernel, staging form and grid: the scalar
+// arguments, the options and the low four bits of the input address in; the geometry fields of `p` and `v` out.  Launches nothing.
+static int stem_select(int x_dtype, int n, int cin, int h, int w, int cout, int ldy, int k, int stride, int pad, int act, int dtype,
+                       const upa_opts* opts, int pool, int x_align, StemParams& p, StemSel& v) {
   UPA_CHECK_ARG(x_dtype == UPA_F32 || x_dtype == UPA_BF16 || (x_dtype == UPA_U8_BGR_HWC && cin == 3),
                 "stem: input must be NCHW f32/bf16 or NHWC uint8 BGR with 3 channels");
-  UPA_CHECK_ARG(cin >= 1 && cin <= 4 && cout % 4 == 0 && ldy % 8 == 0 && (uintptr_t)y % 16 == 0,
-                "stem: cin must be <=4, cout %% 4 == 0, output view 16-byte aligned");
-  UPA_CHECK_ARG(k >= 1 && k <= 7 && stride >= 1 && stride <= 2 && pad >= 0, "stem: bad k/s/p");
-  StemParams p;
-  p.x = x; p.w = wt; p.bias = bias; p.y = (char*)y;
+  UPA_CHECK_ARG(dtype == UPA_F32 || dtype == UPA_BF16, "stem: bad output dtype");
+  UPA_CHECK_ARG(n > 0 && h > 0 && w > 0 && cout > 0, "stem: bad shape");
+  UPA_CHECK_ARG(cin >= 1 && cin <= 4 && cout % 4 == 0 && ldy % 8 == 0, "stem: cin must be <=4, cout %% 4 == 0, ldy %% 8 == 0");
+  UPA_CHECK_ARG(k >= 1 && k <= 7 && stride >= 1 && stride <= 2 && pad >= 0 && pad < k, "stem: bad k/s/p");
+  UPA_CHECK_ARG(h + 2 * pad >= k && w + 2 * pad >= k, "stem: the kernel does not fit the padded input (empty output)");
+  UPA_CHECK_ARG(x_dtype == UPA_U8_BGR_HWC || (x_align & (x_dtype == UPA_BF16 ? 1 : 3)) == 0, "stem: input not aligned to its element size");
+  memset(&p, 0, sizeof(p));
+  memset(&v, 0, sizeof(v));
   p.N = n; p.Cin = cin; p.H = h; p.W = w;
   p.OH = (h + 2 * pad - k) / stride + 1;
   p.OW = (w + 2 * pad - k) / stride + 1;
   p.Cout = cout; p.ldy = ldy; p.KS = k; p.stride = stride; p.pad = pad; p.act = act; p.x_bf16 = x_dtype == UPA_BF16 ? 1 : (x_dtype == UPA_U8_BGR_HWC ? 2 : 0);
-  p.TW = p.OW >= 64 ? 64 : (p.OW >= 32 ? 32 : 16);
-  p.TH = 256 / p.TW;
-  p.tilesX = cdiv(p.OW, p.TW);
-  p.tilesY = cdiv(p.OH, p.TH);
-  p.PR = (p.TH - 1) * stride + k;
-  p.PC = (p.TW - 1) * stride + k;
-  p.PCS = p.PC + 1;
   p.wgs = UPA_OPT(opts, stem_wgs);
   p.pool = pool;
   p.no_xcd = UPA_OPT(opts, no_xcd);
@@ -1193,35 +1200,83 @@ static int stem_nchw_impl(const void* x, int x_dtype, int n, int cin, int h, int
 #endif
   const bool no_mfma = UPA_OPT(opts, stem_no_mfma) != 0;
   const int nt16 = cout / 16;
-  if (pool && !(dtype == UPA_BF16 && !no_mfma && cin == 3 && cout % 16 == 0 && (nt16 == 1 || nt16 == 2 || nt16 == 4) && k == 3 &&
-                stride == 1 && act == UPA_ACT_SILU && p.OH % 2 == 0 && p.OW % 2 == 0 && (long)cin * h * w < (1L << 31) &&
-                (long)n * p.OH * p.OW < (1L << 31))) {
+  const bool mfma = dtype == UPA_BF16 && !no_mfma && cin == 3 && cout % 16 == 0 && (nt16 == 1 || nt16 == 2 || nt16 == 4) &&
+                    ((k == 3 && (stride == 1 || stride == 2)) || (k == 6 && stride == 2)) && (long)cin * h * w < (1L << 31) &&
+                    (long)n * p.OH * p.OW < (1L << 31);
+  if (pool && !(mfma && k == 3 && stride == 1 && act == UPA_ACT_SILU && p.OH % 2 == 0 && p.OW % 2 == 0)) {
     upa_set_error("stem + maxpool: outside the fused form (bf16, 3 -> 16 | 32 | 64 channels, k 3, stride 1, SiLU, even output size)");
     return UPA_EUNSUPPORTED;
   }
-  if (dtype == UPA_BF16 && !no_mfma && cin == 3 && cout % 16 == 0 && (nt16 == 1 || nt16 == 2 || nt16 == 4) &&
-      ((k == 3 && (stride == 1 || stride == 2)) || (k == 6 && stride == 2)) && (long)cin * h * w < (1L << 31) &&
-      (long)n * p.OH * p.OW < (1L << 31)) {
-    UPA_CHECK_ARG(act == UPA_ACT_SILU || act == UPA_ACT_NONE, "stem: activation must be SiLU or none");
-    hipStream_t stm = (hipStream_t)stream;
-    if (k == 3 && stride == 2) launch_stem_mfma_nt<3, 2>(p, n, nt16, stm);
-    else if (k == 3) launch_stem_mfma_nt<3, 1>(p, n, nt16, stm);
-    else launch_stem_mfma_nt<6, 2>(p, n, nt16, stm);
+  UPA_CHECK_ARG(act == UPA_ACT_SILU || act == UPA_ACT_NONE, "stem: activation must be SiLU or none");
+  v.ks = k; v.s = stride; v.pool = pool; v.silu = act == UPA_ACT_SILU; v.waves = 4;
+  if (mfma) {
+    // 8 x 64 output tiles (StemGeo), persistent workgroups; the 16-deep gather form for k 3 / stride 1 / pad 1 with SiLU
+    p.TW = 64; p.TH = 8;
+    p.tilesX = cdiv(p.OW, p.TW);
+    p.tilesY = cdiv(p.OH, p.TH);
+    p.dma = x_dtype == UPA_BF16 && (w & 7) == 0 && (x_align & 15) == 0;
+    const long ntiles = (long)p.tilesX * p.tilesY * n;
+    const int cap = p.wgs > 0 ? p.wgs : 1024;
+    v.family = (k == 3 && stride == 1 && pad == 1 && v.silu) ? STEM_MFMA_G16 : STEM_MFMA;
+    v.nt = nt16;
+    v.staging = p.dma ? STEM_STAGE_DMA : (p.x_bf16 == 2 ? STEM_STAGE_U8 : STEM_STAGE_VGPR);
+    v.wgs = ntiles < cap ? ntiles : cap;
+    return UPA_OK;
+  }
+  constexpr int CO_T = 16;
+  p.TW = p.OW >= 64 ? 64 : (p.OW >= 32 ? 32 : 16);
+  p.TH = 256 / p.TW;
+  p.tilesX = cdiv(p.OW, p.TW);
+  p.tilesY = cdiv(p.OH, p.TH);
+  p.PR = (p.TH - 1) * stride + k;
+  p.PC = (p.TW - 1) * stride + k;
+  p.PCS = p.PC + 1;
+  p.pair = x_dtype == UPA_BF16 && (w & 1) == 0 && (x_align & 3) == 0;
+  v.lds = (size_t)cin * p.PR * p.PCS * sizeof(float);
+  UPA_CHECK_ARG(v.lds <= 64 * 1024, "stem: patch does not fit LDS");
+  const long gx = (long)p.tilesX * p.tilesY * n;
+  UPA_CHECK_ARG(gx < (1L << 31), "stem: too many tiles");
+  v.family = STEM_SCALAR;
+  v.staging = p.x_bf16 == 2 ? STEM_STAGE_U8 : STEM_STAGE_VGPR;
+  v.f32out = dtype == UPA_F32;
+  v.wgs = gx * cdiv(cout, CO_T);
+  return UPA_OK;
+}
+
+/* Dispatch query of upa_conv2d_stem_nchw (pool = 0) / upa_conv2d_stem_nchw_pool2 (pool = 1): see include/upa.h for the bit layout. */
+extern "C" long long upa_stem_variant(int x_dtype, int n, int cin, int h, int w, int cout, int ldy, int k, int stride, int pad, int act,
+                                      int dtype, int pool, const upa_opts* opts, int x_align) {
+  StemParams p;
+  StemSel v;
+  const int rc = stem_select(x_dtype, n, cin, h, w, cout, ldy, k, stride, pad, act, dtype, opts, pool != 0, x_align & 15, p, v);
+  return rc == UPA_OK ? stem_variant_bits(v) : (long long)rc;
+}
+
+static int stem_nchw_impl(const void* x, int x_dtype, int n, int cin, int h, int w, const float* wt, const float* bias, void* y,
+                          int cout, int ldy, int k, int stride, int pad, int act, int dtype, const upa_opts* opts, void* stream, int pool) {
+  UPA_CHECK_ARG(x && wt && y, "stem: null pointer");
+  UPA_CHECK_ARG((uintptr_t)y % 16 == 0, "stem: output view must be 16-byte aligned");
+  StemParams p;
+  StemSel v;
+  if (const int rc = stem_select(x_dtype, n, cin, h, w, cout, ldy, k, stride, pad, act, dtype, opts, pool, (int)((uintptr_t)x & 15), p, v); rc != UPA_OK)
+    return rc;
+  p.x = x; p.w = wt; p.bias = bias; p.y = (char*)y;
+  hipStream_t st = (hipStream_t)stream;
+  if (v.family != STEM_SCALAR) {
+    if (k == 3 && stride == 2) launch_stem_mfma_nt<3, 2>(p, v, st);
+    else if (k == 3) launch_stem_mfma_nt<3, 1>(p, v, st);
+    else launch_stem_mfma_nt<6, 2>(p, v, st);
     UPA_LAUNCH_CHECK();
     return UPA_OK;
   }
   constexpr int CO_T = 16;
-  dim3 grid((unsigned)((long)p.tilesX * p.tilesY * n), (unsigned)cdiv(cout, CO_T));
-  const size_t lds = (size_t)cin * p.PR * p.PCS * sizeof(float);
-  UPA_CHECK_ARG(lds <= 64 * 1024, "stem: patch does not fit LDS");
-  UPA_CHECK_ARG(act == UPA_ACT_SILU || act == UPA_ACT_NONE, "stem: activation must be SiLU or none");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == UPA_BF16) {
-    if (act == UPA_ACT_SILU) hipLaunchKernelGGL((stem_conv_kernel<bf16_t, CO_T, true>), grid, dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((stem_conv_kernel<bf16_t, CO_T, false>), grid, dim3(256), lds, st, p);
+  const dim3 grid((unsigned)((long)p.tilesX * p.tilesY * n), (unsigned)cdiv(cout, CO_T));
+  if (!v.f32out) {
+    if (v.silu) hipLaunchKernelGGL((stem_conv_kernel<bf16_t, CO_T, true>), grid, dim3(256), v.lds, st, p);
+    else hipLaunchKernelGGL((stem_conv_kernel<bf16_t, CO_T, false>), grid, dim3(256), v.lds, st, p);
   } else {
-    if (act == UPA_ACT_SILU) hipLaunchKernelGGL((stem_conv_kernel<float, CO_T, true>), grid, dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((stem_conv_kernel<float, CO_T, false>), grid, dim3(256), lds, st, p);
+    if (v.silu) hipLaunchKernelGGL((stem_conv_kernel<float, CO_T, true>), grid, dim3(256), v.lds, st, p);
+    else hipLaunchKernelGGL((stem_conv_kernel<float, CO_T, false>), grid, dim3(256), v.lds, st, p);
   }
   UPA_LAUNCH_CHECK();
   return UPA_OK;
@@ -1231,40 +1286,69 @@ static int stem_nchw_impl(const void* x, int x_dtype, int n, int cin, int h, int
  * reaches HBM.  k0 = 3 (pad 1: yolov8.yaml rows 0-1) or 6 (pad 2: yolov5 rows 0-1, cfg/models/v5/Detect/yolov5-BoT3.yaml:15-16).
  * w0 / b0: stem weights packed by upa_pack_stem_weight (+ folded bias); w1 / b1: second conv packed by
  * upa_pack_conv_weight(bf16) (+ folded bias).  y: NHWC bf16 view (n, h/4, w/4, 32). */
-static int stem_conv_fused_impl(const void* x, int n, int h, int w, int k0, int c0, const float* w0, const float* b0, const void* w1,
-                                const float* b1, void* y, int ldy, const upa_opts* opts, void* stream, int s0 = 2) {
-  UPA_CHECK_ARG(x && w0 && w1 && y, "stem_conv_fused: null pointer");
+// The argument rules of upa_stem_conv_fused* that do not look at a pointer, and the choice of kernel and grid (as stem_select).  The fused
+// kernels stage by 16-byte LDS-DMA only: an input that is not 16-byte aligned is refused (callers run the two layers).
+static int stem_fused_select(int n, int h, int w, int k0, int s0, int c0, int ldy, const upa_opts* opts, int x_align, StemFusedParams& p,
+                             StemSel& v) {
+  UPA_CHECK_ARG(n > 0 && h > 0 && w > 0, "stem_conv_fused: bad shape");
   UPA_CHECK_ARG(k0 == 3 || k0 == 6, "stem_conv_fused: first conv k = 3 (pad 1) or 6 (pad 2)");
   UPA_CHECK_ARG(c0 == 16 || (c0 == 32 && k0 == 3), "stem_conv_fused: 3 -> 16 -> 32 channels (k 3 | 6) or 3 -> 32 -> 64 (k 3)");
   UPA_CHECK_ARG(s0 == 2 || (s0 == 1 && c0 == 32), "stem_conv_fused: first conv stride 2, or 1 for the 3 -> 32 -> 64 form");
   UPA_CHECK_ARG(w % 8 == 0 && h % (2 * s0) == 0 && w % (2 * s0) == 0 && (long)3 * h * w < (1L << 31), "stem_conv_fused: w %% 8, h %% (2 s0) == 0 required");
-  UPA_CHECK_ARG(ldy % 8 == 0 && (uintptr_t)y % 16 == 0, "stem_conv_fused: output view must be 16-byte aligned");
-  StemFusedParams p{};
-  p.x = x; p.w0 = w0; p.b0 = b0; p.w1 = (const char*)w1; p.b1 = b1; p.y = (char*)y;
+  UPA_CHECK_ARG((long)n * (h / (2 * s0)) * (w / (2 * s0)) < (1L << 31), "stem_conv_fused: too many output pixels");
+  UPA_CHECK_ARG(ldy % 8 == 0, "stem_conv_fused: output view must be 16-byte aligned");
+  UPA_CHECK_ARG((x_align & 15) == 0, "stem_conv_fused: the input must be 16-byte aligned (staged by LDS-DMA)");
+  memset(&p, 0, sizeof(p));
+  memset(&v, 0, sizeof(v));
   p.N = n; p.H = h; p.W = w; p.H0 = h / s0; p.W0 = w / s0; p.OH = h / (2 * s0); p.OW = w / (2 * s0); p.ldy = ldy;
   p.tilesX = cdiv(p.OW, sf::T1W); p.tilesY = cdiv(p.OH, sf::T1H);
   p.no_xcd = UPA_OPT(opts, no_xcd);
   const long ntiles = (long)p.tilesX * p.tilesY * n;
   const int wgs = UPA_OPT(opts, stemf_wgs) > 0 ? UPA_OPT(opts, stemf_wgs) : 512;
-  const int nw = UPA_OPT(opts, stemf_waves) == 4 ? 4 : 8;
-  const dim3 grid((unsigned)(ntiles < wgs ? ntiles : wgs));
+  v.family = c0 == 32 ? STEM_FUSED32 : STEM_FUSED16;
+  v.nt = c0 / 16; v.ks = k0; v.s = s0; v.silu = 1; v.staging = STEM_STAGE_DMA;
+  // fused16, k0 = 6: 4 waves - the 8-wave form of the 108-deep im2col row needs more than the 128 registers two 8-wave workgroups per CU allow (spills)
+  v.waves = c0 == 32 ? 8 : ((k0 == 6 || UPA_OPT(opts, stemf_waves) == 4) ? 4 : 8);
+  v.wgs = ntiles < wgs ? ntiles : wgs;
+  return UPA_OK;
+}
+
+/* Dispatch query of upa_stem_conv_fused_s (the other fused entry points: k0 = 3, s0 = 2, c0 = 16 where they take no such argument). */
+extern "C" long long upa_stem_fused_variant(int n, int h, int w, int k0, int s0, int c0, int ldy, const upa_opts* opts, int x_align) {
+  UPA_CHECK_ARG(s0 == 1 || s0 == 2, "stem_conv_fused: first conv stride 1 | 2");
+  StemFusedParams p;
+  StemSel v;
+  const int rc = stem_fused_select(n, h, w, k0, s0, c0, ldy, opts, x_align & 15, p, v);
+  return rc == UPA_OK ? stem_variant_bits(v) : (long long)rc;
+}
+
+static int stem_conv_fused_impl(const void* x, int n, int h, int w, int k0, int c0, const float* w0, const float* b0, const void* w1,
+                                const float* b1, void* y, int ldy, const upa_opts* opts, void* stream, int s0 = 2) {
+  UPA_CHECK_ARG(x && w0 && w1 && y, "stem_conv_fused: null pointer");
+  UPA_CHECK_ARG(b0 && b1, "stem_conv_fused: null bias (the folded BatchNorm bias of either conv)");
+  UPA_CHECK_ARG((uintptr_t)y % 16 == 0, "stem_conv_fused: output view must be 16-byte aligned");
+  StemFusedParams p;
+  StemSel v;
+  if (const int rc = stem_fused_select(n, h, w, k0, s0, c0, ldy, opts, (int)((uintptr_t)x & 15), p, v); rc != UPA_OK) return rc;
+  p.x = x; p.w0 = w0; p.b0 = b0; p.w1 = (const char*)w1; p.b1 = b1; p.y = (char*)y;
+  const dim3 grid((unsigned)v.wgs);
   hipStream_t st = (hipStream_t)stream;
-  if (c0 == 32 && s0 == 1) {  // (patch 8 KB + stem tile 46 KB: two to three 8-wave workgroups per CU)
+  if (v.family == STEM_FUSED32 && s0 == 1) {  // (patch 8 KB + stem tile 46 KB: two to three 8-wave workgroups per CU)
     (void)upa_full_lds<stem_conv_fused32_kernel<1>>();
     hipLaunchKernelGGL(stem_conv_fused32_kernel<1>, grid, dim3(512), (size_t)sf32::GeoS<1>::patch_bytes(8) + sf32::STILE32, st, p);
     UPA_LAUNCH_CHECK();
     return UPA_OK;
   }
-  if (c0 == 32) {  // two 8-wave workgroups per CU (71 KB of LDS each)
+  if (v.family == STEM_FUSED32) {  // two 8-wave workgroups per CU (71 KB of LDS each)
     (void)upa_full_lds<stem_conv_fused32_kernel<2>>();
     hipLaunchKernelGGL(stem_conv_fused32_kernel<2>, grid, dim3(512), (size_t)sf32::GeoS<2>::patch_bytes(8) + sf32::STILE32, st, p);
     UPA_LAUNCH_CHECK();
     return UPA_OK;
   }
-  if (k0 == 6) {  // 4 waves: the 8-wave form of the 108-deep im2col row needs more than the 128 registers two 8-wave workgroups per CU allow (spills)
+  if (k0 == 6) {
     (void)upa_full_lds<stem_conv_fused_kernel<4, 6>>();
     hipLaunchKernelGGL((stem_conv_fused_kernel<4, 6>), grid, dim3(256), (size_t)2 * sf::Geo<6>::patch_bytes(4) + sf::STILE, st, p);
-  } else if (nw == 4) {
+  } else if (v.waves == 4) {
     (void)upa_full_lds<stem_conv_fused_kernel<4, 3>>();
     hipLaunchKernelGGL((stem_conv_fused_kernel<4, 3>), grid, dim3(256), (size_t)2 * sf::Geo<3>::patch_bytes(4) + sf::STILE, st, p);
   } else {

@@ -374,7 +374,7 @@ class BaseModel(nn.Module):
             isinstance(a.act, nn.SiLU) and isinstance(b.act, nn.SiLU) and not a.training
         n, c, h, w = x.shape
         s0 = int(ca.stride[0])
-        return bool(ok and c == 3 and x.is_contiguous() and w % 8 == 0 and h % (2 * s0) == 0 and w % (2 * s0) == 0)
+        return bool(ok and c == 3 and x.is_contiguous() and x.data_ptr() % 16 == 0 and w % 8 == 0 and h % (2 * s0) == 0 and w % (2 * s0) == 0)
 
     def _fused_stem(self, x):
         a, b = self.model[0], self.model[1]
