@@ -685,6 +685,29 @@ int upa_segment_match_bits(const uint32_t* det_bits, const int32_t* det_area, in
                            const int32_t* ngt, int max_gt, const float* iou_thresholds, int n_thr, unsigned char* tp_m, float* iou_out,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- image classification head (csrc/classify.hip) -----------------------------------------------------------------------------
+ * Classify.forward in eval (nn/modules/head.py:1523-1531): linear(drop(pool(conv(x)).flatten(1))) then softmax(1).  Three launches:
+ * upa_classify_pool, upa_linear (exact f32 in both modes), upa_softmax_topk.
+ *
+ * The head's Conv(c1, c_, 1) + SiLU + AdaptiveAvgPool2d(1) as ONE launch (head.py:1518-1519, :1527; conv.py:188-197 with BN folded):
+ *   pooled[i, c] = (1 / (h w)) * sum_p act(sum_k x[i, p, k] W[c, k] + bias[c])
+ * x: NHWC view (n, h, w, cin), pixel stride ldx, f32 | bf16; w_packed = upa_pack_conv_weight(k = 1, dtype) of the folded (cout, cin)
+ * weights; bias f32[cout]; pooled: (n, cout) f32 rows of stride ldp in BOTH modes (the activation in f32, the (n, h, w, cout) map never
+ * written).  Fixed summation order, no atomics: two calls are bit-identical, a graph replay equals the eager call.
+ * UPA_EINVAL: a null pointer, n, h, w, cin, cout <= 0, ldx < cin, ldp < cout, x / cin / ldx off the 16-byte rule (n <= 65535).
+ * UPA_EUNSUPPORTED: act outside NONE | SILU, dtype outside F32 | BF16.  A refused call launches nothing and leaves pooled untouched.
+ * `opts` is accepted and ignored (one kernel, no dispatch choice). */
+int upa_classify_pool(const void* x, int n, int h, int w, int cin, int ldx, const void* w_packed, const float* bias, float* pooled,
+                      int cout, int ldp, int act, int dtype, const upa_opts* opts, void* stream);
+/* probs[r, :nc] = softmax(logits[r, :nc]) in f32 (exp(z - max z) / sum, head.py:1530) and, when topk_idx != NULL, topk_idx[r, :k] = the
+ * indices of the k largest LOGITS of row r, descending, ties to the lower index (-0 == +0): what `preds.argsort(1, descending=True)
+ * [:, :k]` of models/yolo/classify/val.py:107-108 keeps, as a pure function of the input bits (ranking the rounded probabilities
+ * would not be).  Row strides ldl, ldpr >= nc (elements outside a row's nc are neither read nor written); topk_idx is (rows, k) int32.
+ * A logit of -inf gets probability 0.  A row whose maximum is -inf, or that holds a NaN, is OUTSIDE the contract (its probabilities
+ * are NaN and its indices unspecified).  UPA_EINVAL: null logits / probs, rows or nc <= 0, ldl or ldpr < nc.  UPA_EUNSUPPORTED: k
+ * outside [1, min(nc, 16)] or nc > 65536.  A refused call launches nothing. */
+int upa_softmax_topk(const float* logits, int rows, int nc, int ldl, float* probs, int ldpr, int k, int32_t* topk_idx, void* stream);
+
 /* ---- HIP graph helpers (capture a launch sequence once, replay per batch) -------------------------------------
  * upa_graph_begin / _end bracket a stream capture of upa_* launches; upa_graph_launch replays the instantiated graph.
  * Two rules for graphs that run concurrently with other graphs (several steps in flight on separate streams), both found

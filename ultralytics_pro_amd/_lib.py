@@ -224,6 +224,8 @@ PROTOTYPES = {
     "upa_segment_match": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp,
                                _vp, _sz, _vp]),
     "upa_segment_match_bits": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "upa_classify_pool": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _op, _vp]),
+    "upa_softmax_topk": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "upa_graph_begin": (_i, [_vp]),
     "upa_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "upa_graph_launch": (_i, [_vp, _vp]),

@@ -250,3 +250,62 @@ class SegmentationValidator(DetectionValidator):
         stats.update(self._class_metrics(stats["tp"], stats["conf"], stats["pred_cls"], tcls))
         stats["seg"] = self._class_metrics(stats["tp_m"], stats["conf"], stats["pred_cls"], tcls)
         return stats
+
+
+class ClassificationValidator:
+    """Validation of a `Classify` model: top-1 / top-5 accuracy (models/yolo/classify/val.py:96-140).  Per batch the indices of the
+    min(nc, 5) largest logits of every image - ranked on the device by `upa_softmax_topk` inside the head's forward, what the
+    reference's `preds.argsort(1, descending=True)[:, :n5]` keeps - are copied to the host as int32 next to the targets;
+    `get_stats` is `ClassifyMetrics.process` on those lists and `finalize_metrics` the confusion matrix.  One process: the
+    multi-rank gather (`gather_stats`) is not provided."""
+
+    def __init__(self, model=None):
+        self.model = model
+        self.metrics = M.ClassifyMetrics()
+        self.names = getattr(model, "names", None)
+        self.reset()
+
+    def reset(self):
+        self.pred, self.targets = [], []
+
+    def init_metrics(self, model):
+        self.names = model.names
+        self.nc = len(model.names)
+        self.reset()
+
+    @staticmethod
+    def postprocess(preds):
+        return preds[0] if isinstance(preds, (list, tuple)) else preds
+
+    def update_metrics(self, preds, batch):
+        """preds: the model's eval output ((probs, logits) or probs) of THIS forward; batch["cls"]: the (N,) target classes."""
+        probs = self.postprocess(preds)
+        top = getattr(probs, "_upa_top5", None)
+        if top is None:
+            raise L.UpaError("ClassificationValidator: the predictions carry no device top-k (pass the Classify head's own output)")
+        n5 = min(int(probs.shape[1]), 5)
+        if tuple(top.shape) != (int(probs.shape[0]), n5):
+            raise L.UpaError(f"ClassificationValidator: top-k of shape {tuple(top.shape)} for predictions {tuple(probs.shape)}")
+        self.pred.append(top.to(torch.int32).cpu())  # a stream-ordered copy: synchronises with the forward that wrote it
+        self.targets.append(torch.as_tensor(batch["cls"]).view(-1).to(torch.int32).cpu())
+
+    def __call__(self, batches):
+        """Run the model over an iterable of {"img": float NCHW in [0, 1], "cls": (N,)} batches; returns `get_stats()`."""
+        if self.model is None:
+            raise L.UpaError("ClassificationValidator: no model")
+        self.init_metrics(self.model)
+        dev = next(self.model.parameters()).device
+        dt = getattr(self.model, "compute_dtype", torch.float32)
+        with torch.no_grad():
+            for batch in batches:
+                self.update_metrics(self.model(batch["img"].to(dev).to(dt)), batch)
+        self.finalize_metrics()
+        return self.get_stats()
+
+    def finalize_metrics(self):
+        nc = len(self.names) if self.names is not None else int(max(int(t.max()) for t in self.pred + self.targets)) + 1
+        self.metrics.confusion_matrix = M.process_cls_preds(self.pred, self.targets, nc)
+
+    def get_stats(self):
+        self.metrics.process(self.targets, self.pred)
+        return self.metrics.results_dict

@@ -10,9 +10,9 @@ import torch.nn as nn
 from ... import _lib as L
 from ...engine import runtime as R
 from .block import DFL, Proto
-from .conv import Conv, DWConv, _HipConvMixin, hip_conv2d, version_key
+from .conv import Conv, DWConv, PackedConv, _HipConvMixin, hip_conv2d, version_key
 
-__all__ = ("Detect", "Segment")
+__all__ = ("Detect", "Segment", "Classify")
 
 
 def _magic_exact(xmax: int, d: int) -> bool:
@@ -612,4 +612,87 @@ class Segment(Detect):
 
     def train(self, mode: bool = True):
         self.__dict__.pop("_seg", None)
+        return super().train(mode)
+
+
+class Classify(nn.Module):
+    """YOLO classification head (head.py:1481-1531): Conv(c1, 1280, 1) -> AdaptiveAvgPool2d(1) -> Dropout(0) -> Linear(1280, c2) ->
+    softmax(1).  Eval forward returns the reference's `(probs, logits)`, (B, c2) float32 each (`probs` alone with `export`).
+
+    Three launches: `upa_classify_pool` (conv + SiLU + pool: the (B, 1280, H, W) activation is never written; pooled rows are float32 in
+    both modes), `upa_linear` (exact float32 on the pooled rows in BOTH modes - 1280 is past `upa_linear_bf16`'s depth and 16-bit
+    products would only add error to 82 MFLOP) and `upa_softmax_topk`, which also leaves the indices of the min(c2, 5) largest logits
+    of every row in `self.top5` (and on the returned probabilities as `_upa_top5`) for `ClassificationValidator`.  Rows are stored
+    with c2 rounded up to 4 columns (16-byte rows for the GEMM's stores); the returned tensors are views of the first c2.
+
+    `pool` and `drop` are the reference's children (no parameters; they keep the module list and state_dict layout) and never run.
+    Inference only: train mode, a list input, k != 1, s != 1 and g != 1 raise."""
+
+    export = False
+
+    def __init__(self, c1: int, c2: int, k: int = 1, s: int = 1, p: int | None = None, g: int = 1):
+        super().__init__()
+        if k != 1 or s != 1 or g != 1:
+            raise L.UpaError(f"Classify: the HIP head is the 1x1 stride-1 groups-1 form (got k={k}, s={s}, g={g})")
+        c_ = 1280  # efficientnet_b0 size
+        self.conv = Conv(c1, c_, k, s, p, g)
+        self.pool = nn.AdaptiveAvgPool2d(1)
+        self.drop = nn.Dropout(p=0.0, inplace=True)
+        self.linear = nn.Linear(c_, c2)
+        self.top5 = None
+
+    def _packed_linear(self, device) -> PackedConv:
+        """float32 GEMM weights of `linear`, zero rows appended up to a multiple of 4 outputs; cached, validated by `version_key`."""
+        cache = self.__dict__.setdefault("_pk_cache", {})
+        lin = self.linear
+        ver = version_key(lin.weight, lin.bias)
+        hit = cache.get(str(device))
+        if hit is not None and hit[0] == ver:
+            return hit[1]
+        nc, c_ = lin.weight.shape
+        ncp = (nc + 3) // 4 * 4
+        w = torch.zeros(ncp, c_, 1, 1)
+        w[:nc, :, 0, 0] = lin.weight.detach().float().cpu()
+        b = torch.zeros(ncp)
+        if lin.bias is not None:
+            b[:nc] = lin.bias.detach().float().cpu()
+        pk = PackedConv(w, b, 1, device, torch.float32, False)
+        cache[str(device)] = (ver, pk)
+        return pk
+
+    def forward(self, x):
+        if isinstance(x, list):
+            raise L.UpaError("Classify: a list input (channel concat) is not on the HIP path")
+        if self.training:
+            raise L.UpaError("training-mode Classify is not on the HIP path (classification training is out of scope)")
+        L.require_gpu(x, "Classify")
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            raise L.UpaError(f"Classify: unsupported activation dtype {x.dtype}")
+        x = R.to_nhwc(x, x.dtype, key=(id(self), "x"))
+        vx = R.view_of(x)
+        cv = self.conv
+        if cv.training:
+            raise L.UpaError("Classify: its Conv is in train mode")
+        pk = cv._packed(cv.conv, getattr(cv, "bn", None), x.device, x.dtype, False)
+        lib, stream, dev = L.lib(), L.current_stream(x.device), x.device
+        n, nc = vx.n, self.linear.out_features
+        pooled = R.alloc_plain((n, pk.cout), torch.float32, dev, key=(id(self), "pooled"))
+        L.check(lib.upa_classify_pool(vx.ptr, vx.n, vx.h, vx.w, vx.c, vx.ld, pk.w.data_ptr(), pk.bias.data_ptr(), pooled.data_ptr(), pk.cout,
+                                      pk.cout, cv._act_code(), vx.dtype, R.opts_ptr(), stream), "classify_pool")
+        pl = self._packed_linear(dev)
+        ncp = pl.cout
+        logits = R.alloc_plain((n, ncp), torch.float32, dev, key=(id(self), "logits"))
+        L.check(lib.upa_linear(pooled.data_ptr(), n, pk.cout, pk.cout, pl.w.data_ptr(), pl.bias.data_ptr(), logits.data_ptr(), ncp, ncp,
+                               None, 0, L.ACT_NONE, stream), "linear")
+        probs = R.alloc_plain((n, ncp), torch.float32, dev, key=(id(self), "probs"))
+        k5 = min(nc, 5)
+        top = R.alloc_plain((n, k5), torch.int32, dev, key=(id(self), "top5"))
+        L.check(lib.upa_softmax_topk(logits.data_ptr(), n, nc, ncp, probs.data_ptr(), ncp, k5, top.data_ptr(), stream), "softmax_topk")
+        self.top5 = top
+        y = probs[:, :nc]
+        y._upa_top5 = top
+        return y if self.export else (y, logits[:, :nc])
+
+    def train(self, mode: bool = True):
+        self.__dict__.pop("_pk_cache", None)
         return super().train(mode)

@@ -19,7 +19,7 @@ import yaml
 
 from .. import _lib as L
 from ..engine import runtime as R
-from .modules import (C2f, C2PSA, C3, C3k2, SPPF, BoT3, Bottleneck, Concat, Conv, Detect, Segment)
+from .modules import (C2f, C2PSA, C3, C3k2, SPPF, BoT3, Bottleneck, Classify, Concat, Conv, Detect, Segment)
 from .modules.conv import VirtualUpsample
 from .modules.resample import MaxPool2d, Upsample, ZeroPad2d
 
@@ -29,7 +29,7 @@ _NN_STANDINS = {"Upsample": Upsample, "MaxPool2d": MaxPool2d, "ZeroPad2d": ZeroP
 
 
 def _registry():
-    reg = {m.__name__: m for m in (Conv, C2f, C3, SPPF, BoT3, Bottleneck, Concat, Detect, Segment, C3k2, C2PSA)}
+    reg = {m.__name__: m for m in (Conv, C2f, C3, SPPF, BoT3, Bottleneck, Concat, Detect, Segment, C3k2, C2PSA, Classify)}
     try:
         from .modules.rtdetr import RTDETRDecoder
         reg["RTDETRDecoder"] = RTDETRDecoder
@@ -38,7 +38,8 @@ def _registry():
     return reg
 
 
-BASE_MODULES = {"Conv", "C2f", "C3", "SPPF", "BoT3", "Bottleneck", "C3k2", "C2PSA"}  # subset of base_modules, tasks.py:2446-2710
+# Classify is a base module: its row [nc] becomes [c1, nc] (c2 == nc is left unscaled, tasks.py:2848-2851)
+BASE_MODULES = {"Conv", "C2f", "C3", "SPPF", "BoT3", "Bottleneck", "C3k2", "C2PSA", "Classify"}  # subset of base_modules, tasks.py:2446-2710
 REPEAT_MODULES = {"C2f", "C3", "C3k2", "C2PSA"}  # subset of repeat_modules (BoT3 is not one: SURVEY §8a row 15)
 
 
@@ -49,15 +50,18 @@ def make_divisible(x, divisor):
 
 def yaml_model_load(path):
     """Load a model YAML; 'yolov8n.yaml' resolves to yolov8.yaml with scale 'n', 'yolov8n-seg.yaml' to yolov8-seg.yaml
-    (tasks.py:3147-3185)."""
+    and 'yolov8n-cls.yaml' to yolov8-cls.yaml (tasks.py:3147-3185)."""
     path = Path(path)
     stem, scale = path.stem, ""
     m = re.match(r"^(yolo(?:v)?\d+)([nslmx])$", stem)
     seg = re.match(r"^(yolo(?:v)?\d+)([ntslmx])-seg$", stem)
+    cls = re.match(r"^(yolo(?:v)?\d+)([nslmx])-cls$", stem)
     if m:
         stem, scale = m.group(1), m.group(2)
     elif seg:
         stem, scale = seg.group(1) + "-seg", seg.group(2)
+    elif cls:
+        stem, scale = cls.group(1) + "-cls", cls.group(2)
     cands = [path] if path.is_file() else sorted(CFG_DIR.rglob(stem + ".yaml"))
     if not cands:
         raise FileNotFoundError(f"model YAML '{path}' not found under {CFG_DIR}")
@@ -539,3 +543,40 @@ class SegmentationModel(DetectionModel):
 
 
 RTDETRDetectionModel = DetectionModel  # eval path differs only in the head module (tasks.py:1608)
+
+
+class ClassificationModel(BaseModel):
+    """YOLO classification model (tasks.py:1516-1605): backbone rows + a `Classify` head; eval forward returns `(probs, logits)`.
+    The input is a float NCHW batch in [0, 1] (the reference's `classify_transforms` preprocessing is not part of this package).
+    BatchNorm keeps torch's defaults (eps 1e-5), as in the reference: its `_from_yaml` does not run `initialize_weights`.
+    The layer loop, `fuse()`, `set_compute_dtype` and `compile` are BaseModel's; no Detect preparation runs for a Classify tail."""
+
+    def __init__(self, cfg="yolov8n-cls.yaml", ch=3, nc=None, verbose=False):
+        super().__init__()
+        self.yaml = cfg if isinstance(cfg, dict) else yaml_model_load(cfg)
+        ch = self.yaml["channels"] = self.yaml.get("channels", ch)
+        if nc and nc != self.yaml["nc"]:
+            self.yaml["nc"] = nc
+        elif not nc and not self.yaml.get("nc", None):
+            raise ValueError("nc not specified. Must specify nc in model.yaml or function arguments.")
+        self.model, self.save = parse_model(deepcopy(self.yaml), ch=ch, verbose=verbose)
+        if not isinstance(self.model[-1], Classify):
+            raise L.UpaError(f"ClassificationModel needs a Classify head, {cfg} ends in {type(self.model[-1]).__name__}")
+        self.stride = torch.Tensor([1])  # no stride constraints
+        self.names = {i: f"{i}" for i in range(self.yaml["nc"])}
+        self.compute_dtype = torch.float32
+        self.eval()
+
+    @staticmethod
+    def reshape_outputs(model, nc):
+        """Give the model's `Classify` head `nc` outputs (tasks.py:1575-1586; the torchvision-backbone branches are not provided)."""
+        name, m = list((model.model if hasattr(model, "model") else model).named_children())[-1]
+        if not isinstance(m, Classify):
+            raise L.UpaError(f"reshape_outputs: only a Classify head is supported, the last module is {type(m).__name__}")
+        if m.linear.out_features != nc:
+            m.linear = torch.nn.Linear(m.linear.in_features, nc)
+            m.__dict__.pop("_pk_cache", None)
+            if hasattr(model, "names"):
+                model.names = {i: f"{i}" for i in range(nc)}
+            if hasattr(model, "_graphs"):
+                model._graphs = {}

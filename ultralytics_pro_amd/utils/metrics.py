@@ -248,3 +248,45 @@ def mean_results(p, r, ap):
     if not len(ap):
         return 0.0, 0.0, 0.0, 0.0
     return float(p.mean()), float(r.mean()), float(ap[:, 0].mean()), float(ap.mean())
+
+
+# ---- classification (utils/metrics.py:1450-1501, :353-362) -----------------------------------------------------------------------------
+
+class ClassifyMetrics:
+    """top-1 / top-5 accuracy with the reference's keys.  `process(targets, pred)` takes the validator's lists: per batch the (N,) int32
+    targets and the (N, min(nc, 5)) int32 indices of the largest logits, best first (host tensors; integer comparisons only)."""
+
+    keys = ["metrics/accuracy_top1", "metrics/accuracy_top5"]
+
+    def __init__(self) -> None:
+        self.top1 = 0
+        self.top5 = 0
+        self.speed = {"preprocess": 0.0, "inference": 0.0, "loss": 0.0, "postprocess": 0.0}
+        self.task = "classify"
+        self.confusion_matrix = None
+
+    def process(self, targets, pred):
+        pred, targets = torch.cat(list(pred)), torch.cat(list(targets))
+        correct = (targets[:, None] == pred).float()
+        acc = torch.stack((correct[:, 0], correct.max(1).values), dim=1)  # (top1, top5) accuracy
+        self.top1, self.top5 = acc.mean(0).tolist()
+
+    @property
+    def fitness(self) -> float:
+        return (self.top1 + self.top5) / 2
+
+    @property
+    def results_dict(self) -> dict:
+        return dict(zip([*self.keys, "fitness"], [self.top1, self.top5, self.fitness]))
+
+    def summary(self, normalize: bool = True, decimals: int = 5):
+        return [{"top1_acc": round(self.top1, decimals), "top5_acc": round(self.top5, decimals)}]
+
+
+def process_cls_preds(preds, targets, nc: int) -> np.ndarray:
+    """The classification confusion matrix (ConfusionMatrix.process_cls_preds, utils/metrics.py:353-362): matrix[predicted top-1,
+    target] counts over all batches, (nc, nc) int64, on the host."""
+    p, t = torch.cat(list(preds))[:, 0].cpu().numpy(), torch.cat(list(targets)).cpu().numpy()
+    matrix = np.zeros((nc, nc), dtype=np.int64)
+    np.add.at(matrix, (p, t), 1)
+    return matrix

@@ -125,6 +125,12 @@ HEAD_RECIPE = {
     "yolov8n-seg": (5.0, -4.4, 5.0),
     "yolov11n-seg": (0.1, -6.8, 0.1),
 }
+# Classification families: gain of the Classify head's `model.N.linear.weight` draw (head.py:1521) on top of sqrt(3 / fan_in).  With the
+# plain draw the logits of 1000 classes are nearly flat (spread ~0.3) and no top-5 is decidable; these gains spread them over several
+# units - ranks 1-6 of every golden image at least 1e-2 apart, the largest probability below 0.999 (tests/test_classify_oracle.py
+# asserts both on the reference's own outputs).  Keyed on the family name: no other family's draw changes.
+# (yolov11n-cls pools ~10x larger features than yolov8n-cls, hence the smaller gains; logit standard deviation 3 - 9 per image.)
+CLS_LINEAR_GAIN = {"yolov8n-cls": 30.0, "smooth:yolov8n-cls": 20.0, "yolov11n-cls": 1.5, "smooth:yolov11n-cls": 2.0}
 RTDETR_SCORE_BIAS = -6.5
 RTDETR_SCORE_GAIN = 1.5
 
@@ -214,6 +220,8 @@ def procedural_tensor(key: str, ref: torch.Tensor, kind: str, seed: int = 0, res
             gain = RTDETR_SCORE_GAIN
         if "sampling_offsets" in key:
             gain = 0.5
+        if family in CLS_LINEAR_GAIN and len(parts) >= 3 and parts[-2] == "linear" and kind == "linear":
+            gain = CLS_LINEAR_GAIN[family]
         w = uniform(key, shape, -a * gain, a * gain, seed)
         if smooth and kind == "conv":  # weights a bf16 model stores exactly (round-to-nearest-even of the same draws)
             w = w.to(torch.bfloat16).to(torch.float32)
@@ -237,7 +245,17 @@ def model_family(model: torch.nn.Module) -> str:
     from pathlib import Path
 
     y = getattr(model, "yaml", None) or {}
-    return Path(str(y.get("yaml_file", "default"))).stem
+    fam = Path(str(y.get("yaml_file", "default"))).stem
+    if fam == "default":  # a model built from a dict, or a bare head: a Classify tail takes the classification recipe
+        last = model
+        while True:
+            kids = list(last.children())
+            if type(last).__name__ == "Classify" or not kids:
+                break
+            last = kids[-1]
+        if type(last).__name__ == "Classify":
+            fam = "yolov8n-cls"
+    return fam
 
 
 @torch.no_grad()
