@@ -708,6 +708,45 @@ int upa_classify_pool(const void* x, int n, int h, int w, int cin, int ldx, cons
  * outside [1, min(nc, 16)] or nc > 65536.  A refused call launches nothing. */
 int upa_softmax_topk(const float* logits, int rows, int nc, int ldl, float* probs, int ldpr, int k, int32_t* topk_idx, void* stream);
 
+/* ---- image classification training (csrc/classify_train.hip) --------------------------------------------------------------------
+ * The tail of the train-mode classification step, what torch autograd does behind Classify.forward in train mode (nn/modules/head.py:
+ * 1523-1529: linear(drop(pool(conv(x)).flatten(1))), raw logits) and v8ClassificationLoss (utils/loss.py:873-880).  The head's Conv
+ * trains through the entries of the "training step" section; the linear FORWARD is upa_linear.  Every sum below has one fixed order
+ * that depends on the shapes alone and there are no atomics: two calls, and a graph replay, are bit-identical.  A refused call launches
+ * nothing.
+ *
+ * nn.AdaptiveAvgPool2d(1) + flatten(1) (head.py:1519, :1527): pooled[b, ch] = (sum_p x[b, p, ch]) / (h w), summed and divided in f32.
+ * x: NHWC view (n, h, w, c), pixel stride ldx >= c, f32 | bf16; pooled: (n, c) f32 rows of stride ldp >= c.  Any h * w <= 2^24 (eight
+ * pixel slices per workgroup loop over the map), n <= 65535.  16-byte packets when c, ldx and x allow them, an element-wise path
+ * otherwise.  UPA_EINVAL: null pointer, a dimension <= 0, ldx < c, ldp < c, a misaligned pointer; UPA_EUNSUPPORTED: another dtype. */
+int upa_global_avgpool_fwd(const void* x, int n, int h, int w, int c, int ldx, float* pooled, int ldp, int dtype, void* stream);
+/* Its backward: dy[b, y, x, ch] (+)= dpooled[b, ch] / (h w), the quotient (and, with `accumulate`, the f32 sum with the stored value)
+ * rounded to the view's dtype once.  dpooled: (n, c) f32 rows of stride ldp; dy: NHWC view (n, h, w, c) of pixel stride lddy.
+ * `accumulate` as upa_upsample2x_bwd.  Limits and refusals as the forward. */
+int upa_global_avgpool_bwd(const float* dpooled, int ldp, int n, int h, int w, int c, void* dy, int lddy, int accumulate, int dtype,
+                           void* stream);
+/* v8ClassificationLoss = F.cross_entropy(preds, batch["cls"], reduction="mean") (utils/loss.py:873-880) and its gradient in one call:
+ *   *loss = (1 / rows) sum_r (logsumexp(z_r) - z_r[t_r])     (max-subtracted; unscaled)
+ *   dlogits[r, j] = ((softmax(z_r)[j] - (j == t_r)) / rows) * scale,  scale = *loss_scale (device memory, the GradScaler's; NULL = 1)
+ * logits: (rows, nc) f32 rows of stride ldl; targets: (rows) int32; dlogits: (rows, nc) f32 rows of stride ldd, whose pad columns
+ * nc .. ldd - 1 are written as zero.  Any nc >= 1 (the classes are striped over a workgroup per row).  The row losses go to
+ * `workspace` (upa_cross_entropy_workspace_bytes(rows) bytes) and are added in index order by a second launch.  A target outside
+ * [0, nc) indexes nothing: its row's gradient and loss (hence *loss) are NaN.  No ignore_index, no label smoothing (the reference's call
+ * uses neither).  UPA_EINVAL: null pointer (loss_scale excepted), rows < 1, nc < 1, ldl < nc, ldd < nc, a short workspace. */
+size_t upa_cross_entropy_workspace_bytes(int rows);
+int upa_cross_entropy_fwd_bwd(const float* logits, int rows, int nc, int ldl, const int32_t* targets, const float* loss_scale, float* loss,
+                              float* dlogits, int ldd, void* workspace, size_t workspace_bytes, void* stream);
+/* nn.Linear backward on the plain (n, k) f32 weight (head.py:1521, :1527), exact f32 FMA chains in index order:
+ *   dw[j, i] (+)= sum_r dy[r, j] x[r, i]     db[j] (+)= sum_r dy[r, j]     (r ascending; `accumulate` adds the stored value last)
+ *   dx[r, i]  =  sum_j dy[r, j] w[j, i]      (j ascending; dx may be NULL: not computed)
+ * x: (m, k) rows of stride ldx; dy: (m, n) rows of stride lddy; w, dw: dense (n, k); db: (n) or NULL; dx: (m, k) rows of stride lddx.
+ * Supported form: k, ldx and lddx multiples of 4 with x and dx 16-byte aligned (four k per thread); w, dw, db and dy need float
+ * alignment only (they are views of flat parameter / gradient buffers); ANY n >= 1 and lddy >= n.
+ * UPA_EUNSUPPORTED: k, ldx or lddx not a multiple of 4.  UPA_EINVAL: null x / dy / w / dw, m, k or n < 1, a stride below its row,
+ * a misaligned pointer. */
+int upa_linear_bwd(const float* x, int m, int k, int ldx, const float* dy, int n, int lddy, const float* w, float* dw, float* db, float* dx,
+                   int lddx, int accumulate, void* stream);
+
 /* ---- HIP graph helpers (capture a launch sequence once, replay per batch) -------------------------------------
  * upa_graph_begin / _end bracket a stream capture of upa_* launches; upa_graph_launch replays the instantiated graph.
  * Two rules for graphs that run concurrently with other graphs (several steps in flight on separate streams), both found

@@ -1,0 +1,129 @@
+"""Standalone step time of classification training: yolov8n-cls, batch 32 at 224 x 224, bf16 and f32, eager and compiled (one
+hipGraph per step), and - in a run of its own, under the profiler - the share of the four kernels of csrc/classify_train.hip in the
+step.  Separate from bench.py, whose headline is the detection workload; no earlier number exists for this one and nothing is gated
+on it.
+
+    python -m tools.bench_classify_train                       # times; one JSON line, also written to profiles/classify_train_bench.json
+    python -m tools.bench_classify_train --profile             # + kernel shares: re-runs itself under `rocprofv3 --kernel-trace --stats`
+    python -m tools.bench_classify_train --steps-only bf16     # what the profiled child runs: compiled bf16 steps, nothing printed
+
+Timing: every mode is warmed (the first steps allocate the static buffers and load code objects; compile() needs one eager step),
+then `--repeats` windows of `--steps` steps each are timed with device events on the trainer's stream; the median window is reported
+with the spread (min, max) next to it.  The labels go up inside the timed window, as in real training."""
+
+from __future__ import annotations
+
+import argparse
+import csv
+import json
+import subprocess
+import sys
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+from ultralytics_pro_amd.engine.trainer import ClassificationTrainer  # noqa: E402
+from ultralytics_pro_amd.nn.tasks import ClassificationModel  # noqa: E402
+from ultralytics_pro_amd.utils import procedural as P  # noqa: E402
+
+NEW_KERNELS = ("avgpool_fwd_kernel", "avgpool_bwd_kernel", "cross_entropy_rows_kernel", "cross_entropy_mean_kernel", "linear_wgrad_kernel",
+               "linear_dgrad_kernel")
+
+
+def make(a, dtype, dev):
+    m = ClassificationModel(a.model + ".yaml", nc=a.nc)
+    P.apply_procedural_weights(m, family=a.model)
+    tr = ClassificationTrainer(m, dtype=dtype, device=dev)
+    x = P.synthetic_images(a.batch, h=a.imgsz, w=a.imgsz).to(dev)
+    cls = (P.uniform("bench:cls", (a.batch,), 0.0, 1.0) * a.nc).long().clamp_(0, a.nc - 1)
+    return tr, x, {"cls": cls}
+
+
+def windows(tr, x, lab, a):
+    for _ in range(a.warmup):
+        tr.step(x, lab)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(a.repeats):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(a.steps):
+            loss = tr.step(x, lab)
+        t1.record()
+        torch.cuda.synchronize()
+        ms.append(t0.elapsed_time(t1) / a.steps)
+    ms.sort()
+    return dict(ms_per_step=round(ms[len(ms) // 2], 4), min=round(ms[0], 4), max=round(ms[-1], 4), last_loss=round(float(loss[0]), 5))
+
+
+def kernel_shares(a):
+    """Run `--steps-only bf16` under the profiler (a run of its own) and add up the kernel-stats rows."""
+    out = ROOT / "profiles" / "classify_train_trace"
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", str(out), "--", sys.executable, "-m",
+           "tools.bench_classify_train", "--steps-only", "bf16", "--batch", str(a.batch), "--imgsz", str(a.imgsz), "--nc", str(a.nc),
+           "--steps", str(a.steps), "--warmup", str(a.warmup)]
+    subprocess.run(cmd, check=True, cwd=str(ROOT), timeout=600)
+    rows = []
+    for f in out.rglob("*kernel_stats.csv"):
+        with open(f) as fh:
+            rows += list(csv.DictReader(fh))
+    if not rows:
+        raise RuntimeError(f"no kernel_stats.csv under {out}")
+    total = sum(float(r["TotalDurationNs"]) for r in rows)
+    new = {k: 0.0 for k in NEW_KERNELS}
+    for r in rows:
+        for k in NEW_KERNELS:
+            if k in r["Name"]:
+                new[k] += float(r["TotalDurationNs"])
+    return {"kernel_time_share_of_new_kernels": round(sum(new.values()) / total, 5),
+            "per_kernel_share": {k: round(v / total, 5) for k, v in new.items()}, "kernels_in_trace": len(rows)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="yolov8n-cls")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--imgsz", type=int, default=224)
+    ap.add_argument("--nc", type=int, default=1000)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--profile", action="store_true", help="also collect the new kernels' share of the step (rocprofv3, a run of its own)")
+    ap.add_argument("--steps-only", default=None, choices=["bf16", "f32"], help="run compiled steps and exit (the profiled child)")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_classify_train needs an MI355X: there is no CPU measurement path")
+    dev = torch.device("cuda:0")
+    if a.steps_only:
+        tr, x, lab = make(a, torch.bfloat16 if a.steps_only == "bf16" else torch.float32, dev)
+        tr.compile(x, lab, warm_steps=2)
+        for _ in range(a.warmup + a.steps):
+            tr.step(x, lab)
+        torch.cuda.synchronize()
+        return
+    res = {"metric": f"training step of {a.model} nc {a.nc} bs {a.batch} {a.imgsz}x{a.imgsz}, ms per step (median of {a.repeats} windows of "
+                     f"{a.steps} steps; forward + loss + backward + clip + SGD + EMA)", "batch": a.batch, "steps": a.steps,
+           "warmup": a.warmup, "repeats": a.repeats}
+    for name, dtype in (("bf16", torch.bfloat16), ("f32", torch.float32)):
+        tr, x, lab = make(a, dtype, dev)
+        res[f"{name}_eager"] = windows(tr, x, lab, a)
+        tr.compile(x, lab, warm_steps=0)
+        res[f"{name}_compiled"] = windows(tr, x, lab, a)
+        res[f"{name}_compiled"]["images_per_s"] = round(a.batch / res[f"{name}_compiled"]["ms_per_step"] * 1e3, 1)
+        del tr
+    if a.profile:
+        try:
+            res.update(kernel_shares(a))
+        except (subprocess.SubprocessError, OSError, RuntimeError, KeyError) as e:  # the times above stand; say what is missing
+            res["kernel_shares"] = f"not measured: {type(e).__name__}: {e}"
+    line = json.dumps(res)
+    (ROOT / "profiles").mkdir(exist_ok=True)
+    (ROOT / "profiles" / "classify_train_bench.json").write_text(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()

@@ -226,6 +226,11 @@ PROTOTYPES = {
     "upa_segment_match_bits": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "upa_classify_pool": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _op, _vp]),
     "upa_softmax_topk": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "upa_global_avgpool_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "upa_global_avgpool_bwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
+    "upa_cross_entropy_workspace_bytes": (_sz, [_i]),
+    "upa_cross_entropy_fwd_bwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "upa_linear_bwd": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "upa_graph_begin": (_i, [_vp]),
     "upa_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "upa_graph_launch": (_i, [_vp, _vp]),

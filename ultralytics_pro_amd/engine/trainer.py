@@ -14,6 +14,10 @@ in one flat f32 buffer (grouped: biases | decayed weights | norm weights, traine
 fused launches; `model.parameters()` are views into it, the state_dict stays the reference's.
 Only the yolov8 module set is differentiable here (Conv, C2f, Bottleneck, SPPF, nn.Upsample, Concat, Detect); other
 modules raise.
+
+`ClassificationTrainer` is the same step with another tail (`_tail_op`): `ClassifyT` = the train-mode Classify head, global average
+pool, exact-f32 linear, fused cross-entropy (v8ClassificationLoss, utils/loss.py:873-880) and their backward (include/upa.h, "image
+classification training").
 """
 
 from __future__ import annotations
@@ -542,9 +546,9 @@ class DetectionTrainer:
         self._pack_table, self._pack_n = None, 0
         for m in self.model.model:
             name = f"model.{m.i}"
-            if isinstance(m, H.Detect):
-                op = DetectT(ctx, m, name, self)
-                kind = "detect"
+            tail = self._tail_op(m, name)
+            if tail is not None:
+                op, kind = tail
             elif isinstance(m, B.C2f):
                 op, kind = C2fT(ctx, m, name), "c2f"
             elif isinstance(m, B.SPPF):
@@ -562,6 +566,13 @@ class DetectionTrainer:
             self.nodes.append(_Node(m.i, m.f, kind, op))
         self.detect = self.nodes[-1].op
         self._plan_concats()
+
+    def _tail_op(self, m, name):
+        """(op, kind) of the module that ends the graph and owns the loss (`forward(x)`, `loss_backward(labels, batch_size)`), None for
+        every other module.  The hook a trainer of another task overrides (`ClassificationTrainer`)."""
+        if isinstance(m, H.Detect):
+            return DetectT(self.ctx, m, name, self), "detect"
+        return None
 
     def _plan_concats(self):
         """nn.Concat without copies: a layer whose output feeds exactly one Concat writes it straight into its channel slice of the
@@ -613,6 +624,7 @@ class DetectionTrainer:
             cv.pack_phase_weights()
         if self._pack_table is None:
             rows = [d for cv in self.convs for d in cv.pack_descs()]
+            rows += [d for nd in self.nodes if hasattr(nd.op, "extra_pack_descs") for d in nd.op.extra_pack_descs()]
             t = np.zeros(len(rows), dtype=np.dtype([("w", "<u8"), ("out", "<u8"), ("cout", "<i4"), ("cin", "<i4"), ("k", "<i4"),
                                                     ("dtype", "<i4"), ("tf", "<i4"), ("reserved", "<i4")]))
             for i, r in enumerate(rows):
@@ -669,7 +681,7 @@ class DetectionTrainer:
                         if self._cat_slot.get(j, (None,))[0] != nd.i:  # not written in place by its producer
                             copy_into(ctx, t, y[:, c0:c0 + t.shape[1]])
                         c0 += t.shape[1]
-                else:  # detect
+                else:  # the tail (Detect; Classify in ClassificationTrainer)
                     y = nd.op.forward(xin)
                 nd.y = y
                 nd.g = None
@@ -1214,3 +1226,182 @@ def pack_targets(labels, batch_size, imgsz_h, imgsz_w, min_rows=MAX_GT, nc=None)
             gt[j, :k, 1:] = xyxy[ix]
         ngt[j] = k
     return gt, ngt
+
+
+class ClassifyT(_Seq):
+    """Train-mode Classify (head.py:1523-1529 returns the raw logits) + v8ClassificationLoss (utils/loss.py:873-880) + its gradient:
+    ConvT (in output-channel slices, `_conv_parts`) -> upa_global_avgpool_fwd -> upa_linear, then upa_cross_entropy_fwd_bwd -> upa_linear_bwd -> upa_global_avgpool_bwd ->
+    ConvT.backward.  The pooled rows, the logits and their gradients are float32 in both trainer modes and the linear layer is exact
+    float32 (as the inference head keeps it, `Classify` docstring); only the (B, 1280, h, w) activation and its gradient carry the
+    trainer's dtype.  `Dropout(p = 0)` is the identity and never runs."""
+
+    def __init__(self, ctx, m: H.Classify, name, trainer):
+        super().__init__(ctx)
+        self.m, self.tr = m, trainer
+        self.nc, self.c_ = m.linear.out_features, m.linear.in_features
+        self.ncp = (self.nc + 3) // 4 * 4  # logits rows are 16-byte multiples (upa_linear's stores); pad columns carry zero weights
+        self.parts = self._conv_parts(ctx, m.conv, name + ".conv")
+        dev = ctx.device
+        nb = L.lib().upa_conv_packed_weight_bytes(self.nc, self.c_, 1, L.UPA_F32)
+        self.wl = torch.empty(nb, dtype=torch.uint8, device=dev)            # upa_linear's packed float32 weight, rebuilt every step
+        self.bias_pad = torch.zeros(self.ncp, dtype=torch.float32, device=dev)
+
+    MAX_BN_CHANNELS = 1024  # the channel reductions of csrc/train.hip take c <= 256 * (16 / element size); the context's scratch is sized for it
+
+    @classmethod
+    def _conv_parts(cls, ctx, cv, name):
+        """The head's Conv(c1, 1280, 1) as [(first channel, last channel, ConvT)] over equal output-channel slices of at most 1024
+        channels: BatchNorm is per channel, so a Conv is exactly the concatenation of its output-channel slices, and 1280 channels are
+        past what the per-channel reduction kernels take in one call.  A slice sees the layer's parameters, gradients and running
+        statistics through views of the flat buffers (rows a..b of the OIHW weight are contiguous)."""
+        from types import SimpleNamespace as NS
+        conv, bn = cv.conv, cv.bn
+        cout = conv.out_channels
+        nparts = next((k for k in range(-(-cout // cls.MAX_BN_CHANNELS), cout + 1)
+                       if cout % k == 0 and (cout // k) % 16 == 0 and cout // k <= cls.MAX_BN_CHANNELS), None)
+        if nparts is None:
+            raise L.UpaError(f"{name}: {cout} output channels do not split into equal 16-channel-aligned slices of <= {cls.MAX_BN_CHANNELS}")
+        if nparts == 1:
+            return [(0, cout, ConvT(ctx, conv, bn, cv._act_code(), name))]
+
+        def sl(p, a, b):  # rows a..b of a parameter with its gradient view; buffers have no gradient
+            v = p.data[a:b]
+            if getattr(p, "grad", None) is not None:
+                v.grad = p.grad[a:b]
+            return v
+
+        step, parts = cout // nparts, []
+        for j in range(nparts):
+            a, b = j * step, (j + 1) * step
+            c = NS(weight=sl(conv.weight, a, b), bias=None, groups=conv.groups, dilation=conv.dilation, kernel_size=conv.kernel_size,
+                   stride=conv.stride, padding=conv.padding, out_channels=b - a, in_channels=conv.in_channels)
+            n = NS(weight=sl(bn.weight, a, b), bias=sl(bn.bias, a, b), running_mean=sl(bn.running_mean, a, b),
+                   running_var=sl(bn.running_var, a, b), eps=bn.eps, momentum=bn.momentum)
+            parts.append((a, b, ConvT(ctx, c, n, cv._act_code(), f"{name}[{a}:{b}]")))
+        return parts
+
+    def convs(self):
+        return [p for _, _, p in self.parts]
+
+    def extra_pack_descs(self):
+        """The linear layer's row of the trainer's batched pack table: its master weight is an (nc, 1280, 1, 1) 1x1 kernel."""
+        return [(self.m.linear.weight.data_ptr(), self.wl.data_ptr(), self.nc, self.c_, 1, L.UPA_F32, 0)]
+
+    def forward(self, x):
+        c, lib = self.ctx, L.lib()
+        dev, st = c.device, _s(c.device)
+        n, _, h, w = x.shape
+        self.y = _new(n, self.c_, h, w, c.dtype, dev, (id(self), "y"))
+        for a, b, part in self.parts:
+            part.forward(x, out=self.y[:, a:b])
+        vy = R.view_of(self.y)
+        self.pooled = R.alloc_plain((n, self.c_), torch.float32, dev, (id(self), "pooled"))
+        L.check(lib.upa_global_avgpool_fwd(vy.ptr, vy.n, vy.h, vy.w, vy.c, vy.ld, self.pooled.data_ptr(), self.c_, vy.dtype, st),
+                "global_avgpool_fwd")
+        lin = self.m.linear
+        bias = None
+        if lin.bias is not None:  # the bias row padded to ncp (the flat parameter buffer has other parameters behind it)
+            L.check(lib.upa_copy_rows(lin.bias.data_ptr(), 1, self.nc, self.nc, self.bias_pad.data_ptr(), self.ncp, st), "copy_rows")
+            bias = self.bias_pad.data_ptr()
+        self.logits = R.alloc_plain((n, self.ncp), torch.float32, dev, (id(self), "logits"))
+        L.check(lib.upa_linear(self.pooled.data_ptr(), n, self.c_, self.c_, self.wl.data_ptr(), bias, self.logits.data_ptr(), self.ncp,
+                               self.ncp, None, 0, L.ACT_NONE, st), "linear")
+        return self.logits[:, :self.nc]
+
+    def loss_backward(self, labels, batch_size):
+        """F.cross_entropy(logits, cls, reduction="mean") and the whole backward of the head; returns the (1,) unscaled loss."""
+        c, tr, lib = self.ctx, self.tr, L.lib()
+        dev, st = c.device, _s(c.device)
+        if labels is not None:  # None: already uploaded into the static buffer (graph replay)
+            tr._upload_labels(labels, batch_size)
+        n = batch_size
+        nws = lib.upa_cross_entropy_workspace_bytes(n)
+        ws = tr.pool.get(("ce_ws", n), (nws,), torch.uint8, dev)
+        items = tr.pool.get(("loss_items",), (1,), torch.float32, dev)
+        dlogits = R.alloc_plain((n, self.ncp), torch.float32, dev, (id(self), "dlogits"))
+        L.check(lib.upa_cross_entropy_fwd_bwd(self.logits.data_ptr(), n, self.nc, self.ncp, tr.cls_d.data_ptr(), tr.scaler.ptr(),
+                                              items.data_ptr(), dlogits.data_ptr(), self.ncp, ws.data_ptr(), nws, st), "cross_entropy")
+        lin = self.m.linear
+        dpooled = R.alloc_plain((n, self.c_), torch.float32, dev, (id(self), "dpooled"))
+        L.check(lib.upa_linear_bwd(self.pooled.data_ptr(), n, self.c_, self.c_, dlogits.data_ptr(), self.nc, self.ncp,
+                                   lin.weight.data_ptr(), lin.weight.grad.data_ptr(),
+                                   None if lin.bias is None else lin.bias.grad.data_ptr(), dpooled.data_ptr(), self.c_, 1, st),
+                "linear_bwd")
+        vy = R.view_of(self.y)
+        dy = _new(vy.n, vy.c, vy.h, vy.w, c.dtype, dev, (id(self), "dy"))
+        vdy = R.view_of(dy)
+        L.check(lib.upa_global_avgpool_bwd(dpooled.data_ptr(), self.c_, vdy.n, vdy.h, vdy.w, vdy.c, vdy.ptr, vdy.ld, 0, vdy.dtype, st),
+                "global_avgpool_bwd")
+        f = self.m.f
+        src = tr.nodes[f] if f != -1 else tr.nodes[self.m.i - 1]
+        dx, acc = tr._grad_of(src)
+        for j, (a, b, part) in enumerate(self.parts):
+            part.backward(dy[:, a:b], dx, acc or j > 0)
+        return items
+
+
+def pack_cls_targets(labels, batch_size, nc):
+    """`batch["cls"]` of the reference's classification batch - (B,) integer class ids (models/yolo/classify/train.py
+    preprocess_batch) - as a host int32 tensor.  A label outside [0, nc) is refused here (torch's cross_entropy fails on the host with
+    an index error; the kernel would make the row NaN)."""
+    cls = labels["cls"] if isinstance(labels, dict) else labels
+    cls = torch.as_tensor(cls).detach().view(-1).cpu()
+    if cls.dtype.is_floating_point or cls.dtype == torch.bool:
+        raise L.UpaError(f"classification labels must be integer class ids, got {cls.dtype}")
+    if cls.numel() != batch_size:
+        raise L.UpaError(f"{cls.numel()} labels for a batch of {batch_size} images")
+    cls = cls.long()
+    bad = (cls < 0) | (cls >= nc)
+    if bool(bad.any()):
+        raise L.UpaError(f"label class {int(cls[bad][0])} is outside [0, {nc}) of the model's classes")
+    return cls.to(torch.int32)
+
+
+class ClassificationTrainer(DetectionTrainer):
+    """One-process-per-GPU trainer for a ClassificationModel (reference: models/yolo/classify/train.py on engine/trainer.py's loop; the
+    loss is v8ClassificationLoss, utils/loss.py:873-880).  The graph walk, `step`, `compile` / replay, `set_schedule`, `optimizer_step`,
+    GradScaler, EMA, `sync_ema_buffers` and `all_reduce_gradients` are DetectionTrainer's; the tail of the graph is `ClassifyT` and the
+    labels are the batch's `cls` vector.  The loss is a mean over the rank's batch, so the SUM all-reduce of the per-rank gradients is
+    what the reference's `loss * world_size` under DDP's average gives.  `step()` returns the (1,) unscaled loss.
+    Only the yolov8-cls module set trains (Conv, C2f, Classify); the optimizer is the SGD-Nesterov groups of the detection step."""
+
+    def __init__(self, model, dtype=torch.bfloat16, hyp=None, device=None, world_size=1, ema=True, wgrad_streams: int = 1,
+                 amp_scaler: bool = False):
+        tail = model.model[-1] if hasattr(model, "model") and len(model.model) else None
+        if not isinstance(tail, H.Classify):
+            raise L.UpaError(f"ClassificationTrainer needs a model that ends in a Classify head, got {type(tail).__name__}")
+        for m in model.modules():
+            if isinstance(m, (B.C3k2, B.C2PSA)):
+                raise L.UpaError(f"{type(m).__name__} (YOLO11) has no training path on HIP yet")
+            if isinstance(m, nn.Dropout) and m.p > 0:
+                raise L.UpaError(f"Dropout(p={m.p:g}) has no training path on HIP (the reference trains with dropout=0.0; no device RNG)")
+        self.cls_d = None
+        super().__init__(model, dtype=dtype, hyp=hyp, device=device, world_size=world_size, ema=ema, wgrad_streams=wgrad_streams,
+                         amp_scaler=amp_scaler)
+
+    def _tail_op(self, m, name):
+        if isinstance(m, H.Classify):
+            return ClassifyT(self.ctx, m, name, self), "classify"
+        if isinstance(m, H.Detect):
+            raise L.UpaError(f"{type(m).__name__} (layer {m.i}) is not a classification tail: use DetectionTrainer")
+        return None
+
+    def _upload_labels(self, labels, batch_size):
+        cls = pack_cls_targets(labels, batch_size, self.detect.nc)
+        if self.cls_d is None or self.cls_d.shape[0] != batch_size:
+            if self._graphs is not None or self._capturing:
+                raise L.UpaError(f"a batch of {batch_size} images but the compiled step holds {int(self.cls_d.shape[0])}")
+            self.cls_d = torch.zeros(batch_size, dtype=torch.int32, device=self.device)
+        # through a ring of pinned staging buffers, each guarded by the event of its last copy, as the detection labels go
+        ring = self.__dict__.setdefault("_label_ring", [None] * 4)
+        self._label_slot = (self.__dict__.get("_label_slot", -1) + 1) % len(ring)
+        ent = ring[self._label_slot]
+        if ent is None or ent[0].shape[0] != batch_size:
+            ent = [torch.zeros(batch_size, dtype=torch.int32).pin_memory(), None]
+            ring[self._label_slot] = ent
+        if ent[1] is not None:
+            ent[1].synchronize()
+        ent[0].copy_(cls)
+        self.cls_d.copy_(ent[0], non_blocking=True)
+        ent[1] = torch.cuda.Event()
+        ent[1].record(torch.cuda.current_stream(self.device))

@@ -626,7 +626,10 @@ class Classify(nn.Module):
     with c2 rounded up to 4 columns (16-byte rows for the GEMM's stores); the returned tensors are views of the first c2.
 
     `pool` and `drop` are the reference's children (no parameters; they keep the module list and state_dict layout) and never run.
-    Inference only: train mode, a list input, k != 1, s != 1 and g != 1 raise."""
+    This module's forward is the inference path: train mode, a list input, k != 1, s != 1 and g != 1 raise.  Training lives in the
+    trainer's op, as for every other layer: `engine.trainer.ClassificationTrainer` (`ClassifyT`: train-mode Conv, pool, linear, fused
+    cross-entropy and their backward).  After its optimizer steps - raw-pointer writes that move no `_version` - `eval()` sees the new
+    weights: both packed caches are keyed on `version_key`, which carries the process-wide weights generation the trainer bumps."""
 
     export = False
 
@@ -642,7 +645,8 @@ class Classify(nn.Module):
         self.top5 = None
 
     def _packed_linear(self, device) -> PackedConv:
-        """float32 GEMM weights of `linear`, zero rows appended up to a multiple of 4 outputs; cached, validated by `version_key`."""
+        """float32 GEMM weights of `linear`, zero rows appended up to a multiple of 4 outputs; cached, validated by `version_key`
+        (storage, `_version` and the weights generation `bump_weights_generation()` moves after the trainer's raw-pointer updates)."""
         cache = self.__dict__.setdefault("_pk_cache", {})
         lin = self.linear
         ver = version_key(lin.weight, lin.bias)
@@ -664,7 +668,8 @@ class Classify(nn.Module):
         if isinstance(x, list):
             raise L.UpaError("Classify: a list input (channel concat) is not on the HIP path")
         if self.training:
-            raise L.UpaError("training-mode Classify is not on the HIP path (classification training is out of scope)")
+            raise L.UpaError("training-mode Classify.forward is not on the HIP path: train a classification model with "
+                             "engine.trainer.ClassificationTrainer (its ClassifyT op holds the train-mode head)")
         L.require_gpu(x, "Classify")
         if x.dtype not in (torch.float32, torch.bfloat16):
             raise L.UpaError(f"Classify: unsupported activation dtype {x.dtype}")
