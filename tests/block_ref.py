@@ -371,3 +371,40 @@ def reference(case_index, family):
     d = case_data(case, family)
     with torch.no_grad():
         return d, case_reference(case, d)
+
+
+def emu_stage(order_fn, order, pre=None):
+    """`stage`'s float32 stand-in: exact products of bf16 operands, f32 accumulation in the groups order_fn(order, cin, k, g) names (a group
+    is summed on its own, then added: an MFMA k-step) with the bias first or last as it says, f32 SiLU and residual add, one bf16 (or f32)
+    store.  pre: a list that receives every stage's f32 value before its store."""
+    g = torch.Generator().manual_seed(77)
+
+    def run(x, e_in, w, bias, k, stride, act, residual=None, e_res=None, out_dtype=BF16, pad=None, store=None):
+        x32, w32 = x.float(), w.float()
+        assert torch.equal(x32.to(BF16).float(), x32) and torch.equal(w32.to(BF16).float(), w32)  # products are exact in f32
+        pad = k // 2 if pad is None else pad
+        n, cin, h = x32.shape[:3]
+        cout = w32.shape[0]
+        cols = F.unfold(x32, k, padding=pad, stride=stride)
+        w2 = w32.reshape(cout, -1)
+        groups, bias_first = order_fn(order, cin, k, g)
+        b = bias.float().view(1, cout, 1)
+        acc = b.expand(n, cout, cols.shape[2]).clone() if bias_first else torch.zeros(n, cout, cols.shape[2])
+        for grp in groups:
+            part = None
+            for i in grp:
+                pr = w2[:, i].view(1, cout, 1) * cols[:, i].unsqueeze(1)
+                part = pr if part is None else part + pr
+            acc = acc + part
+        if not bias_first:
+            acc = acc + b
+        if act == ACT_SILU:
+            acc = acc / (1.0 + torch.exp(-acc))
+        acc = acc.view(n, cout, (h + 2 * pad - k) // stride + 1, -1)
+        assert acc.dtype == torch.float32
+        if residual is not None:
+            acc = acc + residual.float()
+        if pre is not None:
+            pre.append(acc)
+        return (acc.to(BF16) if out_dtype == BF16 else acc).double(), None
+    return run

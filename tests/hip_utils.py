@@ -3,14 +3,11 @@
 import numpy as np
 import torch
 
+from tests.kernel_check import unit_input  # noqa: F401
 from ultralytics_pro_amd.engine import runtime as R
 from ultralytics_pro_amd.utils import procedural as P
 
 DEV = torch.device("cuda:0")
-
-
-def unit_input(name, shape, lo=-1.0, hi=1.0):
-    return P.uniform(f"unit:{name}", shape, lo, hi)
 
 
 def bn_fix(m):

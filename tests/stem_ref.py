@@ -23,7 +23,7 @@ import torch.nn.functional as F
 
 from tests import block_ref as B
 from tests import conv_ref as CR
-from tests.block_ref import rn_bf16, stage, store_bf16
+from tests.block_ref import _bf, rn_bf16, stage, store_bf16
 from tests.conv_ref import ACT_NONE, ACT_SILU, F64, conv_bound, conv_ref
 
 BF16 = torch.bfloat16
@@ -107,18 +107,10 @@ def fused_pair(x, w0, b0, k0, s0, p0, w1, b1, stage_fn=stage, store=None, trace=
 # ---------------------------------------------------------------------------------------------------------------------
 # input families
 # ---------------------------------------------------------------------------------------------------------------------
-def _bf(t):
-    return t.to(BF16).float()
-
-
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
 def single_data(case):
     """x (float32 NCHW holding what the input type stores, or uint8 NHWC BGR frames), w OIHW f32 (NOT bf16-exact: the MFMA family must
     round it), bias f32.  uniform: everything in [-1, 1]; saturated: conv_ref's (pre-activations to +-120); u8: random bytes."""
-    g = _gen(case["seed"])
+    g = torch.Generator().manual_seed(case["seed"])
     n, cin, h, w, cout, k = case["n"], case["cin"], case["h"], case["w"], case["cout"], case["k"]
     fam = "saturated" if case["family"] == "saturated" else "uniform"
     x, wt, bias, _ = CR.conv_family(fam, n, cin, h, w, cout, k, torch.float32, case["seed"])
@@ -143,7 +135,7 @@ def fused_data(case, family):
     in [0, 3 / K], biases in [0, 0.5] - never zero, so that the stem map is SiLU(b0) > 0 where nothing is lit and a stem pixel outside the
     map that is not ZERO shows as whole taps of the second conv).  uniform: everything in [-1, 1], w0 not bf16-exact (the kernel rounds it).
     saturated: conv_ref's, on both convs.  w1 is bf16-exact throughout (its packing is host code with its own test)."""
-    g = _gen(case["seed"] + {"positive": 0, "impulse": 1, "uniform": 2, "saturated": 3}[family] * 100000)
+    g = torch.Generator().manual_seed(case["seed"] + {"positive": 0, "impulse": 1, "uniform": 2, "saturated": 3}[family] * 100000)
     n, h, w, k0, c0 = case["n"], case["h"], case["w"], case["k0"], case["c0"]
     if family in ("positive", "impulse"):
         x = B.family_input(family, g, n, 3, h, w, case["seams_x"], case["seams_y"])

@@ -106,42 +106,6 @@ def _order(name, cin, k, g):
 ORDERS = ("ch16", "ch32", "taps_outer", "perm")
 
 
-def _emu_stage(order, pre=None):
-    """`stage`'s stand-in: exact products, f32 accumulation in `order`, f32 SiLU and residual add, one bf16 (or f32) store.  pre: a list that
-    receives every stage's f32 value before its store."""
-    g = _g(77)
-
-    def run(x, e_in, w, bias, k, stride, act, residual=None, e_res=None, out_dtype=BF16):
-        x32, w32 = x.float(), w.float()
-        assert torch.equal(x32.to(BF16).float(), x32) and torch.equal(w32.to(BF16).float(), w32)  # products are exact in f32
-        n, cin = x32.shape[:2]
-        cout = w32.shape[0]
-        cols = F.unfold(x32, k, padding=k // 2, stride=stride)
-        w2 = w32.reshape(cout, -1)
-        groups, bias_first = _order(order, cin, k, g)
-        b = bias.float().view(1, cout, 1)
-        acc = b.expand(n, cout, cols.shape[2]).clone() if bias_first else torch.zeros(n, cout, cols.shape[2])
-        for grp in groups:
-            part = None
-            for i in grp:
-                pr = w2[:, i].view(1, cout, 1) * cols[:, i].unsqueeze(1)
-                part = pr if part is None else part + pr
-            acc = acc + part
-        if not bias_first:
-            acc = acc + b
-        if act == ACT_SILU:
-            acc = acc / (1.0 + torch.exp(-acc))
-        oh = (x.shape[2] + stride - 1) // stride
-        acc = acc.view(n, cout, oh, -1)
-        assert acc.dtype == torch.float32
-        if residual is not None:
-            acc = acc + residual.float()
-        if pre is not None:
-            pre.append(acc)
-        return (acc.to(BF16) if out_dtype == BF16 else acc).double(), None
-    return run
-
-
 def _small_chains():
     """Every chain of block_ref on a small instance: name -> (run(stage_fn) -> list of (value, bound or None))."""
     g = _g(5)
@@ -169,7 +133,7 @@ def test_f32_emulation_in_four_orders_stays_inside_the_bound(chain):
     with torch.no_grad():
         ref = run(B.stage)
         pre = {o: [] for o in ORDERS}
-        outs = {o: run(_emu_stage(o, pre[o])) for o in ORDERS}
+        outs = {o: run(B.emu_stage(_order, o, pre[o])) for o in ORDERS}
     for o, got in outs.items():
         for (t, e), (y, _) in zip(ref, got):
             d = (y - t).abs()

@@ -3,16 +3,14 @@ upa_bottleneck_pair family, upa_detect_level_stream) against the float64 chain r
 the reference's bound everywhere and BIT-EQUAL to the reference's bf16 value wherever that bound is 0 (most elements of the `positive`
 family).  No term of the bound is tied to the largest output, and none was read off a GPU run.
 
-Conventions of tests/test_hip_conv_views.py: the output is a channel slice of a wider NaN-filled buffer with spare channels on both sides
-and a spare image behind it, the input a channel slice with NaN beside it, the virtually upsampled slice of a concat buffer is NaN (never
-read), every kernel runs twice into freshly poisoned buffers and the two results are bit-identical, everything outside the output slice is
-still NaN afterwards.  The form under test is asserted to have been dispatched (`_fused` / `_form32up` / `_form64` / `forward_down` / the
-return code of the C entry point) under the `upa_opts` switches that select it.
+Buffers, sentinels, the two bit-identical runs, the per-element bounds and the fault latch: the conventions of tests/kernel_check.py
+(E = 8, a spare
+image behind the output; the virtually upsampled slice of a concat buffer is NaN: never read).  The form under test is asserted to have been
+dispatched (`_fused` / `_form32up` / `_form64` / `forward_down` / the C entry point's return code) under the `upa_opts` that select it.
 
 BLOCK_STATS=1 prints, per case, the share of outputs held bit-exact and the worst |kernel - ref| / bound over the other elements."""
 
 import contextlib
-import functools
 import ctypes as C
 import os
 
@@ -21,6 +19,7 @@ import pytest
 import torch
 
 from tests import block_ref as B
+from tests import kernel_check as KC
 
 pytestmark = pytest.mark.gpu
 
@@ -31,18 +30,12 @@ PARAMS = [pytest.param(i, fam, id=f"{c['id']}-{fam}") for i, c in enumerate(B.CA
 
 def _dev_slice(x_nchw, lead_nan=0):
     """CPU NCHW float32 (bf16-exact) -> a device NHWC channel slice [E, E + c) of a NaN-filled buffer; its first `lead_nan` channels NaN too."""
-    from tests.hip_utils import DEV
-    n, c, h, w = x_nchw.shape
-    host = torch.full((n, h, w, c + 2 * E), NAN, dtype=torch.bfloat16)
-    xb = x_nchw.permute(0, 2, 3, 1).to(torch.bfloat16)
-    assert torch.equal(xb.float(), x_nchw.permute(0, 2, 3, 1).float()), "input not representable"
-    host[..., E + lead_nan:E + c] = xb[..., lead_nan:]
-    return host.to(DEV).permute(0, 3, 1, 2)[:, E:E + c]
+    buf = KC.slice_buf(x_nchw.permute(0, 2, 3, 1), torch.bfloat16, E, lead_fill=lead_nan)
+    return buf.permute(0, 3, 1, 2)[:, E:E + x_nchw.shape[1]]
 
 
-def _out_buf(n, c, h, w):
-    from tests.hip_utils import DEV
-    buf = torch.full((n + 1, h, w, c + 2 * E), NAN, dtype=torch.bfloat16, device=DEV)
+def _out_view(n, c, h, w):
+    buf = KC.out_buf((n, h, w), c + 2 * E, torch.bfloat16, 1)
     return buf, buf.permute(0, 3, 1, 2)[:n, E:E + c]
 
 
@@ -50,29 +43,6 @@ def _opts(case):
     """The case's `upa_opts` switches on top of the session's options (no switch: the options in force, untouched)."""
     from ultralytics_pro_amd.engine import runtime as R
     return R.use_opts(**case["opts"]) if case["opts"] else contextlib.nullcontext()
-
-
-_FAULTED = []
-
-
-def _stop_after_fault(fn):
-    """A failed assertion is a finding about one case; anything else (a HIP error, a refused launch) may have left the device in a bad
-    state: no later case of this module launches anything then."""
-    @functools.wraps(fn)
-    def run(*a, **k):
-        assert not _FAULTED, f"not run: {_FAULTED[0]} ended with an error that was no assertion"
-        try:
-            return fn(*a, **k)
-        except AssertionError:
-            raise
-        except BaseException as exc:
-            _FAULTED.append(f"{fn.__name__}{a}{k}: {type(exc).__name__}")
-            raise
-    return run
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16)
 
 
 def _load(conv, wb):
@@ -123,7 +93,7 @@ def _run_block(case, d):
                 md = pm.Conv(32, 64, 3, 2).eval()
                 _load(md, d["wts"]["down"])
                 md = md.to(DEV)
-                buf, out = _out_buf(n, 64, (h + 1) // 2, (w + 1) // 2)
+                buf, out = _out_view(n, 64, (h + 1) // 2, (w + 1) // 2)
                 y = m.forward_down(xd, md, out=out)
                 assert y is not None, "upa_c2f16_down_fused was not dispatched"
             else:
@@ -131,7 +101,7 @@ def _run_block(case, d):
                     assert m._form64()
                 elif case["c1"] >= 128:
                     assert m._form32up()
-                buf, out = _out_buf(n, case["c2"], h, w)
+                buf, out = _out_view(n, case["c2"], h, w)
                 y = m._fused(xd, out, up)
                 assert y is not None, "the fused form was not dispatched"
                 assert not mat and (up is None or not up.done), "the fused block must read the half-resolution tensor itself"
@@ -141,7 +111,7 @@ def _run_block(case, d):
             (wa, ba), (wb, bb) = d["wts"]
             p1, p2 = PackedConv(wa, ba, 3, DEV, torch.bfloat16, False), PackedConv(wb, bb, 3, DEV, torch.bfloat16, False)
             xd = _dev_slice(d["x"])
-            buf, out = _out_buf(n, c, h, w)
+            buf, out = _out_view(n, c, h, w)
             vx, vy = R.view_of(xd), R.view_of(out)
             if form == "pair":
                 rc = L.lib().upa_bottleneck_pair(vx.ptr, vx.n, vx.h, vx.w, vx.c, vx.ld, p1.w.data_ptr(), p1.bias.data_ptr(), p2.w.data_ptr(),
@@ -157,28 +127,11 @@ def _run_block(case, d):
             m = _c2f_module(dict(case, c1=64, c2=64, nb=1, c=32), d["wts"])
             cat = _dev_slice(torch.cat([d["x"], torch.zeros(n, 32, h, w)], 1), lead_nan=0)  # [y0 | y1 | room for b] as C2f lays it out
             cat[:, 64:].fill_(NAN)  # the fused launch never writes or reads b
-            buf, out = _out_buf(n, 64, h, w)
+            buf, out = _out_view(n, 64, h, w)
             assert m._pair_cv2(cat, out) is not None, "upa_bottleneck_pair_cv2 was not dispatched"
             c_out = 64
     torch.cuda.synchronize()
     return buf.cpu(), c_out
-
-
-def _check(got, ref, e, what, stats):
-    """got: kernel values (float64, bf16-exact), ref / e: the reference's stored values and bound."""
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    assert bool(torch.isfinite(got).all()), f"{what}: non-finite output"
-    dd = (got - ref).abs()
-    zero = e == 0
-    nz = ~zero
-    share = float(dd[nz].div(e[nz]).max()) if bool(nz.any()) else 0.0
-    stats.append((what, float(zero.float().mean()), share))
-    bad0 = zero & (dd != 0)
-    assert not bool(bad0.any()), (f"{what}: {int(bad0.sum())} of {int(zero.sum())} decided elements are not the reference's bits "
-                                  f"(first at {tuple(int(v) for v in bad0.nonzero()[0])}: got {float(got[bad0][0])!r}, ref {float(ref[bad0][0])!r})")
-    bad = dd > e
-    assert not bool(bad.any()), (f"{what}: {int(bad.sum())} elements outside their bound (worst |d| / bound = {share:.3g}, first at "
-                                 f"{tuple(int(v) for v in bad.nonzero()[0])})")
 
 
 def _report(stats, case, fam):
@@ -188,23 +141,15 @@ def _report(stats, case, fam):
 
 
 @pytest.mark.parametrize("ci,fam", [p for p in PARAMS if B.CASES[p.values[0]]["form"] != "detect"])
-@_stop_after_fault
+@KC.stop_after_fault
 def test_block_kernel_vs_f64_chain(ci, fam):
     case = B.CASES[ci]
     d, (ref, e) = B.reference(ci, fam)
     n = case["n"]
-    runs = []
-    for _ in range(2):
-        buf, c_out = _run_block(case, d)
-        runs.append(buf)
-    a, b = runs
-    assert torch.equal(_bits(a), _bits(b)), "two runs differ"
-    af = a.float()
-    assert bool(torch.isnan(af[n]).all()), "wrote past the last image"
-    assert bool(torch.isnan(af[..., :E]).all()) and bool(torch.isnan(af[..., E + c_out:]).all()), "wrote outside its channel slice"
-    got = af[:n, :, :, E:E + c_out].permute(0, 3, 1, 2).to(torch.float64)
-    stats = []
-    _check(got, ref, e, "out", stats)
+    buf, c_out = KC.twice(lambda: _run_block(case, d))
+    got = KC.payload(buf, n, c_out, "out", offset=E).permute(0, 3, 1, 2).to(torch.float64)
+    share = KC.check_bound(got, ref, e, "out", exact_where_zero=True)
+    stats = [("out", float((e == 0).float().mean()), share)]
     _report(stats, case, fam)
 
 
@@ -240,15 +185,14 @@ def _run_detect(case, d):
 
 
 @pytest.mark.parametrize("ci,fam", [p for p in PARAMS if B.CASES[p.values[0]]["form"] == "detect"])
-@_stop_after_fault
+@KC.stop_after_fault
 def test_detect_level_stream_vs_f64_chain(ci, fam):
     case = B.CASES[ci]
     d, (bl, be, cl, ce, _) = B.reference(ci, fam)
     n, h, w, nc = case["n"], case["h"], case["w"], case["nc"]
     keys_only = case["opts"]["keys_only"]
     dec = B.detect_decode(bl, be, cl, ce, 8.0)
-    (y, keys, a0), (y2, keys2, _) = _run_detect(case, d), _run_detect(case, d)
-    assert torch.equal(y.view(torch.int32), y2.view(torch.int32)) and torch.equal(keys, keys2), "two runs differ"
+    y, keys, a0 = KC.twice(lambda: _run_detect(case, d))
     hw = h * w
     lvl = slice(a0, a0 + hw)
     assert bool(torch.isnan(y[n]).all()) and bool(torch.isnan(y[:, :, :a0]).all()) and bool(torch.isnan(y[:, :, a0 + hw:]).all()), "wrote outside the level"
@@ -257,11 +201,7 @@ def test_detect_level_stream_vs_f64_chain(ci, fam):
     got = y[:n, :, lvl].to(torch.float64)
 
     def inside(g, r, e, what):
-        assert bool(torch.isfinite(g).all()), f"{what}: non-finite"
-        dd = (g - r).abs()
-        stats.append((what, float((e == 0).float().mean()), float((dd / e).max())))
-        bad = dd > e
-        assert not bool(bad.any()), f"{what}: {int(bad.sum())} outside the bound, worst |d| / bound = {float((dd / e).max()):.3g}"
+        stats.append((what, float((e == 0).float().mean()), KC.check_bound(g, r, e, what)))
     inside(got[:, :4], dec["box"], dec["e_box"], "box")
     kbits = keys[:n, lvl].numpy().view(np.uint64)
     kscore = torch.from_numpy((~(kbits >> np.uint64(32)) & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.float32))

@@ -14,6 +14,7 @@ import torch
 from tests import classify_oracle as C
 from tests import classify_ref as CF
 from tests import conv_ref as CR
+from tests import kernel_check as KC
 from ultralytics_pro_amd.utils import procedural as P
 
 pytestmark = pytest.mark.gpu
@@ -137,6 +138,7 @@ def _run_pool(x, wt, b, act, dt, runs=1):
 
 
 @pytest.mark.parametrize("idx", range(len(POOL_CASES)), ids=[_pool_id(c) for c in POOL_CASES])
+@KC.stop_after_fault
 def test_classify_pool_vs_float64(idx):
     case = POOL_CASES[idx]
     h, w, cin, cout, n, dt, act, fam = case
@@ -188,6 +190,7 @@ SOFTMAX_CASES = ([(fam, rows, nc, min(nc, 5)) for fam, rows, nc in
 
 
 @pytest.mark.parametrize("family,rows,nc,k", SOFTMAX_CASES, ids=[f"{f}-r{r}-nc{n}-k{k}" for f, r, n, k in SOFTMAX_CASES])
+@KC.stop_after_fault
 def test_softmax_topk_vs_float64(family, rows, nc, k):
     from ultralytics_pro_amd import _lib as L
     z = _softmax_input(family, rows, nc, k)
@@ -225,6 +228,7 @@ def test_softmax_topk_vs_float64(family, rows, nc, k):
 
 
 # ---- 3. refusals ------------------------------------------------------------------------------------------------------------------------
+@KC.stop_after_fault
 def test_refusals_launch_nothing():
     from ultralytics_pro_amd import _lib as L
     lib, st = L.lib(), _stream()
@@ -283,6 +287,7 @@ def _rules(p, z, top, p_ref, z_ref, what):
 
 
 @pytest.mark.parametrize("case", C.head_cases(), ids=[c[0] for c in C.head_cases()])
+@KC.stop_after_fault
 def test_classify_module_f32(case, golden_dir):
     from ultralytics_pro_amd.nn.modules import Classify
     g = np.load(golden_dir / "ops_classify.npz")
@@ -332,6 +337,7 @@ def _product(name, smooth, dtype=torch.float32):
 
 
 @pytest.mark.parametrize("name", MODELS)
+@KC.stop_after_fault
 def test_model_f32_vs_golden_and_oracle(name, golden_dir):
     g = np.load(golden_dir / f"e2e_{name}.npz")
     m = _product(name, False)
@@ -356,6 +362,7 @@ def test_model_f32_vs_golden_and_oracle(name, golden_dir):
 
 @pytest.mark.parametrize("dispatch", ["session", "serial", "throughput"])
 @pytest.mark.parametrize("name", MODELS)
+@KC.stop_after_fault
 def test_model_bf16_smooth(name, dispatch):
     po, zo = _oracle(name, True, 2)
     m = _product(name, True, torch.bfloat16)
@@ -375,6 +382,7 @@ def test_model_bf16_smooth(name, dispatch):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 @pytest.mark.parametrize("name", MODELS)
+@KC.stop_after_fault
 def test_model_graph_replay_equals_eager(name, dtype):
     m = _product(name, dtype == torch.bfloat16, dtype)
     x = _images(2).to(DEV).to(dtype)
@@ -393,6 +401,7 @@ def test_model_graph_replay_equals_eager(name, dtype):
 
 
 # ---- 6. ClassificationValidator -----------------------------------------------------------------------------------------------------------
+@KC.stop_after_fault
 def test_classification_validator_exact_fractions():
     """8 images in batches of 3 / 3 / 2; targets from the checker's own ranking: its rank-1 class for images 0, 3, 6, its rank-3 class
     for 1, 4, a class outside its top-5 (rank 8) for 2, 5, 7 -> top1 = 3 / 8, top5 = 5 / 8 exactly."""

@@ -18,6 +18,7 @@ import torch
 from tests import classify_oracle as C
 from tests import classify_train_oracle as T
 from tests import classify_train_ref as CR
+from tests import kernel_check as KC
 from ultralytics_pro_amd.utils import procedural as P
 
 pytestmark = pytest.mark.gpu
@@ -27,27 +28,8 @@ NAN = float("nan")
 UPA_EINVAL, UPA_EUNSUPPORTED = -1, -2
 
 
-def _env():
-    from tests.hip_utils import DEV
-    from ultralytics_pro_amd import _lib as L
-    return DEV, L, L.lib(), L.current_stream(DEV)
-
-
-def _bits(t):
-    t = t.contiguous().cpu()
-    return t.view({2: torch.int16, 4: torch.int32}[t.element_size()])
-
-
-def _same(a, b):
-    return torch.equal(_bits(a), _bits(b))
-
-
-def _check(got, ref, bound, what):
-    err = (got.double() - ref).abs()
-    ratio = float((err / bound.clamp_min(1e-300)).max()) if err.numel() else 0.0
-    print(f"{what}: worst error / bound = {ratio:.3f}")
-    assert bool(torch.isfinite(got).all()), f"{what}: non-finite output"
-    assert bool((err <= bound).all()), f"{what}: worst error / bound = {ratio:.3f}"
+def _held(got, ref, bound, what):
+    print(f"{what}: worst error / bound = {KC.check_bound(got, ref, bound, what):.3f}")
 
 
 def _code(dtype):
@@ -61,11 +43,12 @@ POOL_CASES = [(1, 1, 1, 16, 16), (4, 2, 2, 1280, 1280), (2, 7, 7, 1280, 1280), (
 
 @pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
 @pytest.mark.parametrize("case", POOL_CASES, ids=["x".join(map(str, c)) for c in POOL_CASES])
+@KC.stop_after_fault
 def test_global_avgpool_fwd_bwd(case, dtype):
     """Forward: a slice chain of ceil(hw / 8) additions, 7 joining additions, one divide: ops = ceil(hw / 8) + 8, magnitude
     sum |x| / hw.  Backward: one divide (+ one addition under accumulate) of magnitude |dpooled| / hw (+ |stored|), rounded to the
     view's dtype once (bf16: + half a bf16 ulp)."""
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     n, h, w, c, ld = case
     x = P.uniform(f"clstrain:pool:{case}", (n, c, h, w), -1.0, 1.0).to(dtype).float()
     xb = torch.full((n, h, w, ld), 7.0, dtype=dtype)
@@ -76,11 +59,11 @@ def test_global_avgpool_fwd_bwd(case, dtype):
     for o in outs:
         assert lib.upa_global_avgpool_fwd(xd.data_ptr(), n, h, w, c, ld, o.data_ptr(), ldp, _code(dtype), st) == 0, lib.upa_last_error()
     torch.cuda.synchronize()
-    assert _same(outs[0], outs[1]), "two runs differ"
+    assert KC.same_bits(outs[0], outs[1]), "two runs differ"
     got = outs[0].cpu()
     assert bool(torch.isnan(got[:, c:]).all()) and bool(torch.isnan(got[n:]).all()), "wrote outside the pooled rows"
     ref, mag, ops = CR.avg_pool_ref(x)
-    _check(got[:n, :c], ref, CR.bound(ops, mag), f"avgpool_fwd {case} {dtype}")
+    _held(got[:n, :c], ref, CR.bound(ops, mag), f"avgpool_fwd {case} {dtype}")
     # backward, plain and accumulating
     dp = P.uniform(f"clstrain:dpool:{case}", (n, c), -1.0, 1.0)
     dpb = torch.full((n, ldp), NAN, dtype=F32)
@@ -97,11 +80,11 @@ def test_global_avgpool_fwd_bwd(case, dtype):
             assert lib.upa_global_avgpool_bwd(dpd.data_ptr(), ldp, n, h, w, c, b.data_ptr(), ld, acc, _code(dtype), st) == 0, lib.upa_last_error()
             outs.append(b)
         torch.cuda.synchronize()
-        assert _same(outs[0], outs[1]), "two runs differ"
+        assert KC.same_bits(outs[0], outs[1]), "two runs differ"
         got = outs[0].cpu().float()
         assert bool(torch.isnan(got[..., c:]).all()), "wrote outside its channel slice"
         ref, mag, ops = CR.avg_pool_bwd_ref(dp, h, w, prev if acc else None)
-        _check(got[..., :c].permute(0, 3, 1, 2), ref, CR.bound(ops, mag, ref, dtype == BF16), f"avgpool_bwd {case} {dtype} acc={acc}")
+        _held(got[..., :c].permute(0, 3, 1, 2), ref, CR.bound(ops, mag, ref, dtype == BF16), f"avgpool_bwd {case} {dtype} acc={acc}")
 
 
 # ---- 2. cross-entropy ---------------------------------------------------------------------------------------------------------------
@@ -109,7 +92,7 @@ CE_CASES = [(1, 1, 4), (4, 10, 12), (3, 1000, 1000), (2, 1001, 1004), (65, 5, 8)
 
 
 def _ce_call(z, t, ld, scale=None):
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     rows, nc = z.shape
     zb = torch.full((rows, ld), NAN, dtype=F32)  # a pad column read as a logit would poison the row
     zb[:, :nc] = z
@@ -127,7 +110,7 @@ def _ce_call(z, t, ld, scale=None):
         assert rc == 0, lib.upa_last_error()
         outs.append((dz, loss))
     torch.cuda.synchronize()
-    assert _same(outs[0][0], outs[1][0]) and _same(outs[0][1], outs[1][1]), "two runs differ"
+    assert KC.same_bits(outs[0][0], outs[1][0]) and KC.same_bits(outs[0][1], outs[1][1]), "two runs differ"
     dz, loss = outs[0][0].cpu(), outs[0][1].cpu()
     assert bool(torch.isnan(dz[rows:]).all()) and bool(torch.isnan(loss[[0, 2]]).all()), "wrote outside its outputs"
     assert bool((dz[:rows, nc:] == 0).all()), "pad columns of dlogits are not zero"
@@ -143,6 +126,7 @@ def _targets(rows, nc, key):
 
 @pytest.mark.parametrize("amp", [1.0, 80.0], ids=["pm1", "pm80"])
 @pytest.mark.parametrize("case", CE_CASES, ids=["x".join(map(str, c)) for c in CE_CASES])
+@KC.stop_after_fault
 def test_cross_entropy_fwd_bwd(case, amp):
     """Bounds as derived in classify_train_ref.cross_entropy_ref: with D = max |z - max z| of a row and depth = ceil(nc / 256) + 9,
     gradient ops = 2 (D + 2) + depth + 3 on the magnitude (softmax + onehot) scale / rows; loss ops = D + depth + 6 + ceil(rows / 64)
@@ -154,20 +138,21 @@ def test_cross_entropy_fwd_bwd(case, amp):
     t = _targets(rows, nc, case)
     dz, loss = _ce_call(z, t, ld)
     rl, rdz, mag_dz, ops_dz, mag_l, ops_l = CR.cross_entropy_ref(z, t)
-    _check(dz, rdz, CR.bound(ops_dz[:, None], mag_dz) + CR.UNDERFLOW, f"cross_entropy dz {case} +-{amp:g}")
-    _check(loss.reshape(1), rl.reshape(1), CR.bound(ops_l, mag_l).reshape(1), f"cross_entropy loss {case} +-{amp:g}")
+    _held(dz, rdz, CR.bound(ops_dz[:, None], mag_dz) + CR.UNDERFLOW, f"cross_entropy dz {case} +-{amp:g}")
+    _held(loss.reshape(1), rl.reshape(1), CR.bound(ops_l, mag_l).reshape(1), f"cross_entropy loss {case} +-{amp:g}")
     if nc == 1:
         assert float(loss) == 0.0 and bool((dz == 0).all())
     dz2, loss2 = _ce_call(z, t, ld, scale=1024.0)
-    assert _same(dz2, dz * 1024.0) and _same(loss2.reshape(1), loss.reshape(1))
+    assert KC.same_bits(dz2, dz * 1024.0) and KC.same_bits(loss2.reshape(1), loss.reshape(1))
 
 
+@KC.stop_after_fault
 def test_cross_entropy_target_outside_the_classes_is_nan_and_in_bounds():
     rows, nc, ld = 3, 10, 12
     z = P.uniform("clstrain:z:bad", (rows, nc), -1.0, 1.0)
     for bad in (nc, -1, 2 ** 31 - 1):
         t = torch.tensor([1, bad, 2])
-        DEV, L, lib, st = _env()
+        DEV, L, lib, st = KC.env()
         zd, td = torch.nn.functional.pad(z, (0, ld - nc)).to(DEV), t.to(torch.int32).to(DEV)
         dz = torch.full((rows + 1, ld), 5.0, dtype=F32, device=DEV)
         loss = torch.full((3,), 5.0, dtype=F32, device=DEV)
@@ -186,10 +171,11 @@ LIN_CASES = [(1, 1280, 10), (4, 1280, 10), (2, 1280, 1000), (5, 64, 3), (33, 96,
 
 
 @pytest.mark.parametrize("case", LIN_CASES, ids=["x".join(map(str, c)) for c in LIN_CASES])
+@KC.stop_after_fault
 def test_linear_bwd(case):
     """FMA chains in index order: dW and db take m roundings (+ 1 for the accumulate addition) of sum |dy x| resp. sum |dy| (+ |stored|),
     dx takes n roundings of sum |dy W|."""
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     m, k, n = case
     x = P.uniform(f"clstrain:lx:{case}", (m, k), -1.0, 1.0)
     dy = P.uniform(f"clstrain:ldy:{case}", (m, n), -1.0, 1.0)
@@ -220,23 +206,24 @@ def test_linear_bwd(case):
             outs.append((dw, db, dx))
         torch.cuda.synchronize()
         for a, b in zip(*outs):
-            assert _same(a, b), "two runs differ"
+            assert KC.same_bits(a, b), "two runs differ"
         assert bool(torch.isnan(dwbuf[0])), "wrote in front of dw"
         dw, db, dx = (t.cpu() for t in outs[0])
         assert bool(torch.isnan(dw[n:]).all()) and bool(torch.isnan(db[n:]).all()) and bool(torch.isnan(dx[m:]).all())
         assert bool(torch.isnan(dx[:, k:]).all())
         rdw, rdb, rdx, mw, mb, mx, ops_w, ops_x = CR.linear_bwd_ref(x, dy, w, dw0 if acc else None, db0 if acc else None)
         what = f"linear_bwd {case} acc={acc}"
-        _check(dw[:n], rdw, CR.bound(ops_w, mw), what + " dW")
-        _check(db[:n], rdb, CR.bound(ops_w, mb), what + " db")
+        _held(dw[:n], rdw, CR.bound(ops_w, mw), what + " dW")
+        _held(db[:n], rdb, CR.bound(ops_w, mb), what + " db")
         if with_dx:
-            _check(dx[:m, :k], rdx, CR.bound(ops_x, mx), what + " dx")
+            _held(dx[:m, :k], rdx, CR.bound(ops_x, mx), what + " dx")
         else:
             assert bool(torch.isnan(dx).all()), "dx = NULL but dx was written"
 
 
+@KC.stop_after_fault
 def test_refusals_launch_nothing():
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     buf = torch.full((4096,), -7.0, dtype=F32, device=DEV)
     tg = torch.zeros(8, dtype=torch.int32, device=DEV)
     p, t = buf.data_ptr(), tg.data_ptr()
@@ -282,6 +269,7 @@ GOLDEN_RUNS = [("a", F32), ("b", F32), ("a", BF16)]
 
 
 @pytest.mark.parametrize("case,dtype", GOLDEN_RUNS, ids=["a-f32", "b-f32", "a-bf16"])
+@KC.stop_after_fault
 def test_training_step_matches_reference_golden(case, dtype, golden_dir):
     """Whole steps of yolov8n-cls on the HIP path against the imported reference's record, with the tolerances
     test_training_step_yolov8n_matches_reference_golden uses for the same quantities (f32: loss 2e-3, gradient norm 3e-3, per-parameter
@@ -342,6 +330,7 @@ def test_training_step_matches_reference_golden(case, dtype, golden_dir):
             np.testing.assert_allclose(got, G[f"{case}_state_l2_{step}"], rtol=1e-3, atol=1e-4)
 
 
+@KC.stop_after_fault
 def test_compiled_step_equals_eager_and_two_trainers_agree():
     """compile(): the hipGraph replay follows the eager step bit for bit - loss and the flat parameter buffer over three steps - and so
     do two eager trainers from the same start (every sum of the step has a fixed order)."""
@@ -358,10 +347,11 @@ def test_compiled_step_equals_eager_and_two_trainers_agree():
         runs.append((torch.cat(losses), tr.P.cpu().clone(), tr.E.cpu().clone(), tr.updates))
     for other in runs[1:]:
         assert other[3] == runs[0][3] == 4
-        assert _same(other[0], runs[0][0]) and _same(other[1], runs[0][1]) and _same(other[2], runs[0][2])
+        assert KC.same_bits(other[0], runs[0][0]) and KC.same_bits(other[1], runs[0][1]) and KC.same_bits(other[2], runs[0][2])
     assert bool(torch.isfinite(runs[0][0]).all())
 
 
+@KC.stop_after_fault
 def test_eight_steps_on_one_batch_lower_the_loss():
     """Eight f32 steps on golden (a)'s first batch.  With the reference's hyper-parameters (lr 0.01, Nesterov momentum 0.9, clip 10)
     momentum makes the CPU oracle's loss non-monotone on this batch (tests/test_classify_train_ref.py pins that: 10.03, 4.51, 4.00,
@@ -373,6 +363,7 @@ def test_eight_steps_on_one_batch_lower_the_loss():
     assert losses[-1] < losses[0], losses
 
 
+@KC.stop_after_fault
 def test_grad_scaler_leaves_the_unscaled_norm():
     """amp_scaler=True: the loss kernel multiplies its gradient by 2**16 (exact), the reported norm and loss are the unscaled ones
     (the existing scaler test's tolerance: 1e-3 relative on the norm, 1e-6 on the loss)."""
@@ -389,6 +380,7 @@ def test_grad_scaler_leaves_the_unscaled_norm():
     np.testing.assert_allclose(t1.P.cpu().numpy(), t0.P.cpu().numpy(), rtol=1e-5, atol=1e-6)
 
 
+@KC.stop_after_fault
 def test_eval_after_training_sees_the_new_weights():
     """After two steps `model.eval()` logits equal the CPU oracle's eval logits computed from the trainer's current weights within the
     f32 e2e tolerance of test_hip_classify.py (1e-3): the packed caches of Conv and of Classify's linear must follow the optimizer's
@@ -416,6 +408,7 @@ def test_eval_after_training_sees_the_new_weights():
     assert d <= 1e-3 and moved > 10 * 1e-3
 
 
+@KC.stop_after_fault
 def test_refusals():
     from tests.hip_utils import DEV
     from ultralytics_pro_amd._lib import UpaError

@@ -47,6 +47,7 @@ import ctypes as C
 import pytest
 import torch
 
+from tests import kernel_check as KC
 from tests import loss_ref as LR
 
 pytestmark = pytest.mark.gpu
@@ -55,12 +56,6 @@ UPA_OK, UPA_EINVAL = 0, -1
 K = 64
 SENTINEL = -77.0
 U23 = 2.0 ** -23
-
-
-def _env():
-    from tests.hip_utils import DEV
-    from ultralytics_pro_amd import _lib as L
-    return DEV, L, L.lib(), L.current_stream(DEV)
 
 
 class _Maps:
@@ -98,7 +93,7 @@ class _Maps:
 
 def _call(i, maps, grad_scale=1.0, dev_scale=None, scaled=False, **kw):
     """One call of upa_detection_loss(_scaled); keyword arguments override what the input says.  Returns (rc, items (3,) device)."""
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     nl = kw.get("n_levels", len(i.hw))
     n = max(nl, len(i.hw))
     VP, IA, FA = C.c_void_p * n, C.c_int * n, C.c_float * n
@@ -125,7 +120,7 @@ def _call(i, maps, grad_scale=1.0, dev_scale=None, scaled=False, **kw):
 
 
 def _run(name, **kw):
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     i = LR.inputs(name)
     maps = _Maps(i.feats, LR.CASE[name].layout, DEV)
     rc, items = _call(i, maps, **kw)
@@ -144,7 +139,7 @@ def _tensors(items, grads):
     return out
 
 
-def _check(name, items, grads, factor=1.0):
+def _check_case(name, items, grads, factor=1.0):
     """items and factor * gradients against loss_ref within K * max(E32, 2^-23 max |ref|); prints the ratio of every tensor."""
     r = LR.reference(name)
     o_items, o_grads, _, _ = LR.oracle32(name)
@@ -180,10 +175,11 @@ def _check(name, items, grads, factor=1.0):
 
 
 @pytest.mark.parametrize("name", [c.name for c in LR.CASES])
+@KC.stop_after_fault
 def test_loss_and_gradient_match_the_float64_reference(name):
     """Every case of the table in tests/loss_ref.py: items and gradients of upa_detection_loss against loss_ref."""
     items, grads = _run(name)
-    _check(name, items, grads)
+    _check_case(name, items, grads)
     if name.startswith("empty"):
         for g in grads:
             assert bool((g[:, :64] == 0.0).all()), "box / DFL gradient of a batch without boxes"
@@ -191,15 +187,17 @@ def test_loss_and_gradient_match_the_float64_reference(name):
 
 
 @pytest.mark.parametrize("host,dev", [(1.0 / 3.0, None), (1.0, 65536.0), (1.0 / 3.0, 65536.0)], ids=["host", "device", "both"])
+@KC.stop_after_fault
 def test_gradient_scales_multiply_the_gradients_only(host, dev):
     """upa_detection_loss_scaled: the gradients are host scale * device scale times the unscaled reference, the items are those of
     the unscaled call bit for bit."""
     items0, _ = _run("base")
     items, grads = _run("base", grad_scale=host, dev_scale=dev, scaled=True)
-    _check("base", items, grads, factor=_f32(host) * (dev or 1.0))
+    _check_case("base", items, grads, factor=_f32(host) * (dev or 1.0))
     assert torch.equal(items.view(torch.int32), items0.view(torch.int32))
 
 
+@KC.stop_after_fault
 def test_device_scale_of_zero_gives_zero_gradients():
     items0, _ = _run("base")
     items, grads = _run("base", dev_scale=0.0)
@@ -207,6 +205,7 @@ def test_device_scale_of_zero_gives_zero_gradients():
     assert torch.equal(items.view(torch.int32), items0.view(torch.int32))
 
 
+@KC.stop_after_fault
 def test_two_calls_give_the_same_bits():
     """The gradients of two calls are bit-identical; the items agree to 1e-6 relative (their sums are float64 atomics)."""
     a, ga = _run("base")
@@ -216,11 +215,12 @@ def test_two_calls_give_the_same_bits():
     assert float(((a - b).abs() / b.abs()).max()) <= 1e-6
 
 
+@KC.stop_after_fault
 def test_refusals_leave_every_output_untouched():
     """Shapes and arguments that must be refused on the host with UPA_EINVAL: fewer anchors than the top-k takes (a 3 x 3 level), more
     than the LDS metric row holds (202 x 202), max_gt of 0 and 1025, reg_max 8, four levels, a workspace one byte short.  The
     sentinel-filled gradient buffers and loss_items are untouched afterwards: nothing was launched."""
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     assert LR.refusals_precede_launches(), "this build would launch before it refuses: the 3 x 3 shape must not reach the GPU"
     base = LR.inputs("base")
 

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from tests import postprocess_ref as PR
+from tests import kernel_check as KC
 
 pytestmark = pytest.mark.gpu
 
@@ -58,6 +59,7 @@ def _assert_nms(got, s, what):
 
 
 @pytest.mark.parametrize("name", NAMES)
+@KC.stop_after_fault
 def test_nms_scene_bit_exact(name):
     """Rows, counts, keep indices and the fixed-shape tail of every scene; single-label scenes again through the best-class-key entry
     (`upa_nms_batched_hot`: the sort kernel compacts the candidates itself), bit for bit the plain path."""
@@ -70,6 +72,7 @@ def test_nms_scene_bit_exact(name):
         _assert_nms(_nms(s, hot=True), s, "hot")
 
 
+@KC.stop_after_fault
 def test_hot_entry_reads_the_keys_not_the_scores():
     """With the keys attached, single-label NMS takes score and class from them: the class rows may hold anything (keys-only Detect)."""
     for name in ("chain200_from60-sl", "tie_classes_nc17-sl", "stage1025-sl", "classes_filter-sl"):
@@ -80,6 +83,7 @@ def test_hot_entry_reads_the_keys_not_the_scores():
 
 
 @pytest.mark.parametrize("staging", [{"nms_stages": 1}, {"nms_stages": 2}, {"nms_first_prefix": 256}], ids=["all_keys", "radix_select", "prefix_256"])
+@KC.stop_after_fault
 def test_nms_staging_does_not_change_results(staging):
     from ultralytics_pro_amd import _lib as L
     from ultralytics_pro_amd.engine import runtime as R
@@ -90,6 +94,7 @@ def test_nms_staging_does_not_change_results(staging):
             _assert_nms(_nms(s), s, staging)
 
 
+@KC.stop_after_fault
 def test_nms_wrapper_and_max_det_cap():
     """The list-returning wrapper on a ragged batch, and max_det above the kept-list capacity (1024) refused."""
     from ultralytics_pro_amd import _lib as L
@@ -124,6 +129,7 @@ def _match(m):
 
 
 @pytest.mark.parametrize("max_det", [300, 600])
+@KC.stop_after_fault
 def test_match_predictions_bit_exact(max_det):
     """Contests over one label (also split across the rounds of 256 detections), IoU on a threshold and one ulp below, class mismatch,
     ragged B = 3 with ngt = 0 and counts = 0, counts / ngt above the buffers (clamped), zero rows at and past counts[b]."""
@@ -133,6 +139,7 @@ def test_match_predictions_bit_exact(max_det):
         assert bad[0].size == 0, (m.name, "first differing row", bad[0][0], bad[1][0], got[bad[0][0], bad[1][0]], ref[bad[0][0], bad[1][0]])
 
 
+@KC.stop_after_fault
 def test_match_predictions_refusals():
     from ultralytics_pro_amd import _lib as L
     from ultralytics_pro_amd.utils import metrics as pmet
@@ -165,6 +172,7 @@ def _boxes(rng, n):
 
 
 @pytest.mark.parametrize("nm", [(15, 17), (16, 16), (1, 257), (257, 1), (0, 5)], ids=lambda v: f"{v[0]}x{v[1]}")
+@KC.stop_after_fault
 def test_box_iou_bit_exact(nm):
     """N M = 255, 256, 257 (the 256-thread block edge) and an empty side: bit-equal to the f32 restatement of utils/metrics.py:54-74, and as
     close to float64 as that restatement itself is on these inputs (the bound is measured, not chosen)."""
@@ -194,6 +202,7 @@ def test_box_iou_bit_exact(nm):
 
 @pytest.mark.parametrize("stride", [6, 38])
 @pytest.mark.parametrize("padding", [True, False])
+@KC.stop_after_fault
 def test_scale_boxes_bit_exact(stride, padding):
     """Row strides 6 (detections) and 38 (detections + 32 mask coefficients), with and without the padding step, boxes that clip at all
     four borders, more rows than one block: columns 0-3 bit-equal to the f32 restatement of utils/ops.py:102-178, the others untouched."""

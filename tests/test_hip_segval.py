@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from tests import segval_ref as V
+from tests import kernel_check as KC
 from ultralytics_pro_amd.utils import procedural as P
 
 pytestmark = pytest.mark.gpu
@@ -39,20 +40,11 @@ def _u32(t):
     return t.cpu().numpy().view(np.uint32)
 
 
-def _twice(fn):
-    a = fn()
-    b = fn()
-    torch.cuda.synchronize()
-    for x, y in zip(a, b):
-        assert torch.equal(x.view(torch.uint8) if x.dtype != torch.uint8 else x, y.view(torch.uint8) if y.dtype != torch.uint8 else y), \
-            "two runs differ"
-    return a
-
-
 # ---- 1. packing -------------------------------------------------------------------------------------------------------------------
 
 
 @pytest.mark.parametrize("hw", [(8, 8), (20, 28), (160, 160)])
+@KC.stop_after_fault
 def test_pack_mask_bits(hw):
     from ultralytics_pro_amd.utils import metrics as M
     dev = _dev()
@@ -83,7 +75,7 @@ def test_pack_mask_bits(hw):
             return bits.clone(), area.clone()
         # sentinels: the allocator hands the freed block back, so fill one of the same size first
         torch.full((b, max_gt, words), -1, dtype=torch.int32, device=dev)
-        bits, area = _twice(once)
+        bits, area = KC.twice(once)
         assert np.array_equal(_u32(bits), want_bits), (hw, src.dtype, overlap)
         assert np.array_equal(area.cpu().numpy(), want_area)
 
@@ -108,6 +100,7 @@ def test_pack_mask_bits(hw):
         assert not (_u32(bits)[..., -1] >> (npix % 32)).any()  # padding bits
 
 
+@KC.stop_after_fault
 def test_pack_masks_resizes_like_the_reference():
     """SegmentationValidator.pack_masks on 320 x 320 label masks (overlap form and planes) for a 160 x 160 proto map equals
     F.interpolate(bilinear, align_corners = False) > 0.5 on the CPU (segment/val.py:138-141)."""
@@ -177,6 +170,7 @@ CASES = [(torch.float32, 32, (8, 8), 0), (torch.float32, 8, (20, 28), 0), (torch
 
 
 @pytest.mark.parametrize("dtype,nm,hw,ldp", CASES, ids=[f"{str(c[0])[6:]}-nm{c[1]}-{c[2][0]}x{c[2][1]}" + ("-slice" if c[3] else "") for c in CASES])
+@KC.stop_after_fault
 def test_mask_bits_equal_process_mask(dtype, nm, hw, ldp):
     from ultralytics_pro_amd.utils import metrics as M
     from ultralytics_pro_amd.utils import ops
@@ -217,7 +211,7 @@ def test_mask_bits_equal_process_mask(dtype, nm, hw, ldp):
         M.match_masks_batched(protos, rows, cnt, (H, W), gt_cls, gt_bits, gt_area, ngt, out=tp, pred_bits=pb, pred_area=pa)
         return pb, pa, tp
 
-    pb, pa, tp = _twice(once)
+    pb, pa, tp = KC.twice(once)
     assert int(total.item()) == total_rows
     refm = ref.cpu().numpy().astype(bool).reshape(total_rows, -1)
     assert refm.any() and not refm.all()
@@ -269,7 +263,7 @@ def _run_bits(cases, G, hw, max_det, max_gt, garbage=False):
         tp = M.match_mask_bits_batched(*args, iou_out=iou)
         return iou, tp
 
-    iou, tp = _twice(once)
+    iou, tp = KC.twice(once)
     return iou.cpu().numpy(), tp.cpu().numpy(), cnt, ngt
 
 
@@ -284,6 +278,7 @@ def _check_bits(cases, G, iou, tp, cnt, ngt):
 
 
 @pytest.mark.parametrize("garbage", [False, True], ids=["clean", "padding-bits-set"])
+@KC.stop_after_fault
 def test_iou_and_tp_equal_reference_ragged_batch(OPS, garbage):
     """The four (20, 28) cases as ONE batch: counts (0, 37, 37, 300) and label counts (5, 5, 70, 1) side by side, 560 pixels = a half
     last word.  Classes 7 (labels only) and 9 (predictions only) are in the cases."""
@@ -295,6 +290,7 @@ def test_iou_and_tp_equal_reference_ragged_batch(OPS, garbage):
 
 
 @pytest.mark.parametrize("name", ["n1_m1", "n5_m0", "n300_m64"])
+@KC.stop_after_fault
 def test_iou_and_tp_equal_reference_single(OPS, name):
     hw = tuple(int(v) for v in OPS[f"{name}_hw"])
     n, m = OPS[f"{name}_pred_bits"].shape[0], OPS[f"{name}_gt_bits"].shape[0]
@@ -302,6 +298,7 @@ def test_iou_and_tp_equal_reference_single(OPS, name):
     _check_bits([name], OPS, iou, tp, cnt, ngt)
 
 
+@KC.stop_after_fault
 def test_tp_on_the_references_own_masks(MAP):
     """Image 0 of the mask-mAP set, the reference's stored 160 x 160 masks: tp_m and the IoU matrix equal the reference's, through
     the public single-image form as well."""
@@ -326,6 +323,7 @@ def test_tp_on_the_references_own_masks(MAP):
 
 # ---- 4. public functions ------------------------------------------------------------------------------------------------------------
 
+@KC.stop_after_fault
 def test_mask_iou_public(OPS, MAP):
     from ultralytics_pro_amd._lib import UpaError
     from ultralytics_pro_amd.utils import metrics as M
@@ -335,7 +333,7 @@ def test_mask_iou_public(OPS, MAP):
         npix = int(hw[0] * hw[1])
         p, g = V.unpack_bits(OPS[f"{name}_pred_bits"], npix), V.unpack_bits(OPS[f"{name}_gt_bits"], npix)
         for cast in (lambda a: torch.from_numpy(a.astype(np.float32)), lambda a: torch.from_numpy(a.astype(np.uint8))):
-            out = _twice(lambda: (M.mask_iou(cast(g).to(dev), cast(p).to(dev)),))[0]
+            out = KC.twice(lambda: (M.mask_iou(cast(g).to(dev), cast(p).to(dev)),))[0]
             assert out.dtype == torch.float32 and np.array_equal(out.cpu().numpy(), OPS[f"{name}_iou"]), name
     k = MAP["pred_bits0"].shape[0]
     out = M.mask_iou(torch.from_numpy(V.unpack_bits(MAP["gt_bits0"], 25600)).float().to(dev),
@@ -353,6 +351,7 @@ def test_mask_iou_public(OPS, MAP):
 
 # ---- 5. refusals ------------------------------------------------------------------------------------------------------------------
 
+@KC.stop_after_fault
 def test_refusals_leave_every_buffer_untouched():
     from ultralytics_pro_amd import _lib as L
     dev = _dev()
@@ -423,6 +422,7 @@ def _seg_model(dev):
     return m.to(dev).eval()
 
 
+@KC.stop_after_fault
 def test_segmentation_validator_matches_reference_map(MAP):
     """SegmentationModel("yolov8n-seg.yaml") in f32 on the four synthetic images, as one batch and as two batches of two: box and
     mask means within the project's 5e-3 of the reference's (the gate of tests/test_metrics.py).  The product's detections differ
@@ -459,6 +459,7 @@ def test_segmentation_validator_matches_reference_map(MAP):
 
 # ---- 7. graph ---------------------------------------------------------------------------------------------------------------------
 
+@KC.stop_after_fault
 def test_update_step_graph_replay_equals_eager(MAP):
     from ultralytics_pro_amd.engine.validator import SegmentationValidator
     dev = _dev()

@@ -4,17 +4,14 @@ tests/stem_ref.py, element by element: inside the reference's bound everywhere, 
 bound is 0 (98 to 99 % of a fused case's outputs on `positive`).  All tolerances are conv_ref.conv_bound / block_ref.stage: none is tied
 to the largest output and none was read off a GPU run.
 
-Conventions of tests/test_hip_conv_views.py and tests/test_hip_blocks.py: the input is images [1, 1 + n) of an (n + 2)-image NaN-filled
-NCHW allocation (uint8 frames: 255-filled), so that a row read from the neighbouring image shows; the output is a channel slice at offset 8
-of a NaN-filled NHWC buffer with spare channels on both sides and a spare image behind it, all of which are still NaN afterwards; every case
-first asserts, through upa_stem_variant / upa_stem_fused_variant, the family, instantiation, staging form, waves and workgroup count the
-call dispatches to (and workgroups < tiles where the case is meant to walk several tiles per workgroup); every case runs twice into freshly
-poisoned buffers and the two results agree bit for bit.  After an error that is no assertion, no later case of the module launches.
+Buffers, sentinels, the two bit-identical runs, the per-element bounds and the fault latch: the conventions of tests/kernel_check.py.
+The input is images [1, 1 + n) of an (n + 2)-image NaN-filled (uint8: 255-filled) allocation, the output a channel slice at offset 8 with a spare image behind;
+every case first asserts, through upa_stem_variant / upa_stem_fused_variant, the family, instantiation, staging form, waves and workgroup
+count it dispatches to (and workgroups < tiles where it is meant to walk several tiles per workgroup).
 
 Each case prints its worst |kernel - ref| / bound; STEM_STATS=1 adds the share of outputs held bit-exact."""
 
 import ctypes as C
-import functools
 import os
 
 import pytest
@@ -22,6 +19,7 @@ import torch
 
 from tests import stem_ref as S
 from tests.conv_ref import ACT_NONE, ACT_RELU, ACT_SILU
+from tests import kernel_check as KC
 
 pytestmark = pytest.mark.gpu
 
@@ -30,24 +28,6 @@ NAN = float("nan")
 XCODE = {"f32": 0, "bf16": 1, "u8": 2}   # UPA_F32, UPA_BF16, UPA_U8_BGR_HWC
 TORCH = {"f32": torch.float32, "bf16": torch.bfloat16}
 EINVAL, EUNSUPPORTED = -1, -2
-
-_FAULTED = []
-
-
-def _stop_after_fault(fn):
-    """A failed assertion is a finding about one case; anything else (a HIP error, a refused launch) may have left the device in a bad
-    state: no later case of this module launches anything then."""
-    @functools.wraps(fn)
-    def run(*a, **k):
-        assert not _FAULTED, f"not run: {_FAULTED[0]} ended with an error that was no assertion"
-        try:
-            return fn(*a, **k)
-        except AssertionError:
-            raise
-        except BaseException as exc:
-            _FAULTED.append(f"{fn.__name__}{a}{k}: {type(exc).__name__}")
-            raise
-    return run
 
 
 def _opts(case_opts):
@@ -62,13 +42,7 @@ def _dev_input(x, fmt, misalign=False):
     """CPU payload -> (pointer to image 1 of an (n + 2)-image poisoned device allocation, the allocation).  misalign: the whole allocation
     starts 2 bytes into its buffer."""
     from tests.hip_utils import DEV
-    if fmt == "u8":
-        host = torch.full((x.shape[0] + 2,) + tuple(x.shape[1:]), 255, dtype=torch.uint8)
-        host[1:-1] = x
-    else:
-        host = torch.full((x.shape[0] + 2,) + tuple(x.shape[1:]), NAN, dtype=TORCH[fmt])
-        host[1:-1] = x.to(TORCH[fmt])
-        assert torch.equal(host[1:-1].float(), x.float()), "input not representable"
+    host = KC.slice_buf(x, torch.uint8 if fmt == "u8" else TORCH[fmt], 0, tail=0, fill=255 if fmt == "u8" else NAN, spare=1, front=1, dev="cpu")
     per = host[0].numel() * host.element_size()
     if misalign:
         assert fmt == "bf16"
@@ -83,43 +57,20 @@ def _dev_input(x, fmt, misalign=False):
     return ptr, dev
 
 
-def _out_buf(n, c, oh, ow, dtype):
-    from tests.hip_utils import DEV
+def _out(n, c, oh, ow, dtype):
+    """(the NaN-filled output buffer with a spare image, the pointer to its channel slice at E, its pitch)"""
     ld = E + c + E + (-c % 8)
-    buf = torch.full((n + 1, oh, ow, ld), NAN, dtype=dtype, device=DEV)
+    buf = KC.out_buf((n, oh, ow), ld, dtype, 1)
     return buf, buf.data_ptr() + E * buf.element_size(), ld
 
 
-def _payload(buf, n, c, what):
-    """The whole output buffer on the CPU -> the slice as float64 NCHW, after checking that nothing outside it was written."""
-    af = buf.float()
-    assert bool(torch.isnan(af[n]).all()), f"{what}: wrote past the last image"
-    assert bool(torch.isnan(af[..., :E]).all()) and bool(torch.isnan(af[..., E + c:]).all()), f"{what}: wrote outside its channel slice"
-    got = af[:n, :, :, E:E + c].permute(0, 3, 1, 2).to(torch.float64)
-    assert bool(torch.isfinite(got).all()), f"{what}: non-finite output"
-    return got
-
-
-def _same_bits(a, b):
-    return torch.equal(a.contiguous().view(torch.int16 if a.element_size() == 2 else torch.int32), b.contiguous().view(torch.int16 if b.element_size() == 2 else torch.int32))
-
-
-def _compare(got, ref, e, what):
-    """Inside the bound everywhere; where the bound is 0 that means the reference's bits.  Prints the worst share of the bound used."""
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    dd = (got - ref).abs()
-    zero = e == 0
-    nz = ~zero
-    share = float(dd[nz].div(e[nz]).max()) if bool(nz.any()) else 0.0
+def _held(buf, n, c, ref, e, what):
+    """Nothing outside the slice written; inside the bound everywhere, and where the bound is 0 the reference's bits."""
+    got = KC.payload(buf, n, c, what, offset=E).permute(0, 3, 1, 2).to(torch.float64)
+    share = KC.check_bound(got, ref, e, what, exact_where_zero=True)
     print(f"STEM {what}: worst |d| / bound = {share:.4f}", flush=True)
     if os.environ.get("STEM_STATS"):
-        print(f"STEM_STATS {what}|exact={float(zero.double().mean()):.4f}|worst_share={share:.4f}", flush=True)
-    bad0 = zero & (dd != 0)
-    assert not bool(bad0.any()), (f"{what}: {int(bad0.sum())} of {int(zero.sum())} decided elements are not the reference's bits "
-                                  f"(first at {tuple(int(v) for v in bad0.nonzero()[0])}: got {float(got[bad0][0])!r}, ref {float(ref[bad0][0])!r})")
-    bad = dd > e
-    assert not bool(bad.any()), (f"{what}: {int(bad.sum())} elements outside their bound (worst |d| / bound = {share:.3g}, first at "
-                                 f"{tuple(int(v) for v in bad.nonzero()[0])}: got {float(got[bad][0])!r}, ref {float(ref[bad][0])!r})")
+        print(f"STEM_STATS {what}|exact={float((e == 0).double().mean()):.4f}|worst_share={share:.4f}", flush=True)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -135,7 +86,7 @@ def _run_single(case, d, pk):
     oh, ow = (case["oh"] // 2, case["ow"] // 2) if pool else (case["oh"], case["ow"])
     xptr, keep = _dev_input(d["x"], case["fmt"], case["misalign"])
     odt = TORCH[case["out"]]
-    buf, yptr, ld = _out_buf(n, cout, oh, ow, odt)
+    buf, yptr, ld = _out(n, cout, oh, ow, odt)
     opts = _opts(case["opts"])
     args = (XCODE[case["fmt"]], n, case["cin"], case["h"], case["w"])
     tail = (cout, ld, case["k"], case["s"], case["pad"], case["act"], L.dtype_code(odt))
@@ -160,19 +111,17 @@ def _single_test(kind, index):
     case = (S.SINGLE_CASES if kind == "single" else S.POOL_CASES)[index]
     d, (ref, bound) = S.single_case_reference(kind, index)
     pk = PackedConv(d["w"], d["b"], case["k"], DEV, torch.float32, True)
-    a, b = _run_single(case, d, pk), _run_single(case, d, pk)
-    assert _same_bits(a, b), "two runs differ"
-    _compare(_payload(a, case["n"], case["cout"], case["id"]), ref, bound, case["id"])
+    _held(KC.twice(lambda: _run_single(case, d, pk)), case["n"], case["cout"], ref, bound, case["id"])
 
 
 @pytest.mark.parametrize("index", range(len(S.SINGLE_CASES)), ids=[c["id"] for c in S.SINGLE_CASES])
-@_stop_after_fault
+@KC.stop_after_fault
 def test_stem_kernel_vs_f64(index):
     _single_test("single", index)
 
 
 @pytest.mark.parametrize("index", range(len(S.POOL_CASES)), ids=[c["id"] for c in S.POOL_CASES])
-@_stop_after_fault
+@KC.stop_after_fault
 def test_stem_pool_kernel_vs_f64_chain(index):
     _single_test("pool", index)
 
@@ -190,7 +139,7 @@ def _run_fused(case, d, pa, pb):
     lib = L.lib()
     n, c = case["n"], 2 * case["c0"]
     xptr, keep = _dev_input(d["x"], "bf16")
-    buf, yptr, ld = _out_buf(n, c, case["oh"], case["ow"], torch.bfloat16)
+    buf, yptr, ld = _out(n, c, case["oh"], case["ow"], torch.bfloat16)
     opts = _opts(case["opts"])
     v = lib.upa_stem_fused_variant(*_fused_args(case), ld, C.byref(opts), xptr & 15)
     assert v >= 0, f"upa_stem_fused_variant refused: {v}"
@@ -206,7 +155,7 @@ def _run_fused(case, d, pa, pb):
 
 
 @pytest.mark.parametrize("index,family", [pytest.param(i, f, id=f"{c['id']}-{f}") for i, c in enumerate(S.FUSED_CASES) for f in c["families"]])
-@_stop_after_fault
+@KC.stop_after_fault
 def test_fused_stem_pair_vs_f64_chain(index, family):
     from tests.hip_utils import DEV
     from ultralytics_pro_amd.nn.modules.conv import PackedConv
@@ -214,9 +163,7 @@ def test_fused_stem_pair_vs_f64_chain(index, family):
     d, (ref, e) = S.fused_case_reference(index, family)
     pa = PackedConv(d["w0"], d["b0"], case["k0"], DEV, torch.bfloat16, True)
     pb = PackedConv(d["w1"], d["b1"], 3, DEV, torch.bfloat16, False)
-    a, b = _run_fused(case, d, pa, pb), _run_fused(case, d, pa, pb)
-    assert _same_bits(a, b), "two runs differ"
-    _compare(_payload(a, case["n"], 2 * case["c0"], case["id"]), ref, e, f"{case['id']}-{family}")
+    _held(KC.twice(lambda: _run_fused(case, d, pa, pb)), case["n"], 2 * case["c0"], ref, e, f"{case['id']}-{family}")
 
 
 def test_the_cases_name_every_instantiation_the_file_can_launch():
@@ -248,7 +195,7 @@ _SINGLE_REFUSALS = [
 
 
 @pytest.mark.parametrize("what,change,code", _SINGLE_REFUSALS, ids=[r[0].replace(" ", "_") for r in _SINGLE_REFUSALS])
-@_stop_after_fault
+@KC.stop_after_fault
 def test_stem_refuses_and_writes_nothing(what, change, code):
     from tests.hip_utils import DEV
     from ultralytics_pro_amd import _lib as L
@@ -283,7 +230,7 @@ _FUSED_REFUSALS = [
 
 
 @pytest.mark.parametrize("what,change", _FUSED_REFUSALS, ids=[r[0].replace(" ", "_") for r in _FUSED_REFUSALS])
-@_stop_after_fault
+@KC.stop_after_fault
 def test_fused_stem_refuses_and_writes_nothing(what, change):
     from tests.hip_utils import DEV
     from ultralytics_pro_amd import _lib as L
@@ -307,7 +254,7 @@ def test_fused_stem_refuses_and_writes_nothing(what, change):
     assert bool(torch.isnan(buf.float()).all()), f"{what}: a refused call wrote to its output"
 
 
-@_stop_after_fault
+@KC.stop_after_fault
 def test_fused_model_path_falls_back_to_the_two_layers_on_a_misaligned_input():
     """DetectionModel._stem_fusable looks at the input's address: a bf16 batch that starts 2 bytes into its allocation runs the two layers
     (the stem then stages through VGPRs) instead of raising from the refused fused call - the same result as the aligned batch gives."""

@@ -1,16 +1,11 @@
 """-m gpu: the training-step kernels of csrc/train.hip (and the entries of conv.hip / elementwise.hip the backward pass uses) called
 through the C ABI on channel slices of wider buffers and compared per element with the float64 restatements of tests/train_ref.py.
 
-Conventions (those of tests/test_hip_conv_views.py):
-  input     a channel slice starting at channel E of a wider buffer (E = 16 bytes of elements); the channels on both sides hold 7.0 -
-            NaN in the `poison` family;
-  output    a channel slice at offset E of a NaN-filled buffer with four spare pixel rows: afterwards everything outside the slice
-            must still be NaN and the payload finite; under accumulate = 1 the payload is pre-filled with known finite values;
-  pitches   every view of one call has its own pitch (c + 2 E, c + 3 E, c + 4 E ...);
-  vectors   per-channel float32 outputs sit at offset 4 of a NaN-filled array eight longer than c;
-  every call runs twice into two sets of buffers, which must agree bit for bit.
-Each bound is per element and built from the magnitude term train_ref returns next to the reference; the docstrings carry the
-derivations.  The `print`s give the worst error / bound of each group (pytest -s)."""
+Buffers, sentinels, the two bit-identical runs, the per-element bounds and the fault latch: the conventions of tests/kernel_check.py:
+every view of
+one call has its own pitch (c + 2 E, c + 3 E, ...), accumulating outputs are pre-filled with known finite values, per-channel float32
+outputs sit at offset 4 of a NaN-filled array eight longer than c.  Each bound is built from the magnitude term train_ref returns next to
+the reference; the docstrings carry the derivations.  The `print`s give the worst error / bound of each group (pytest -s)."""
 
 import ctypes as C
 import math
@@ -20,6 +15,7 @@ import torch
 
 from tests import conv_ref as CR
 from tests import train_ref as TR
+from tests import kernel_check as KC
 
 pytestmark = pytest.mark.gpu
 
@@ -32,12 +28,6 @@ MOM, EPS = 0.03, TR.BN_EPS
 NAN = float("nan")
 
 
-def _env():
-    from tests.hip_utils import DEV
-    from ultralytics_pro_amd import _lib as L
-    return DEV, L, L.lib(), L.current_stream(DEV)
-
-
 def _opts(**kw):
     from ultralytics_pro_amd import _lib as L
     return L.Opts(**kw)
@@ -45,15 +35,6 @@ def _opts(**kw):
 
 def _es(dtype):
     return torch.empty(0, dtype=dtype).element_size()
-
-
-def _bits(t):
-    t = t.contiguous()
-    return t.view({1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-
-def _same(a, b):
-    return torch.equal(_bits(a.cpu()), _bits(b.cpu()))
 
 
 def _rows(t):
@@ -69,15 +50,11 @@ class _In:
     """An input view: `mat` (rows, c) at channel offset E of a buffer c + groups * E wide."""
 
     def __init__(self, mat, dtype, groups=2, poison=False):
-        DEV = _env()[0]
         self.rows, self.c = mat.shape
         self.es = _es(dtype)
         E = self.E = 16 // self.es
         self.ld = self.c + groups * E
-        b = torch.full((self.rows, self.ld), NAN if poison else PAD, dtype=dtype)
-        b[:, E:E + self.c] = mat.to(dtype)
-        assert torch.equal(b[:, E:E + self.c].float(), mat.float()), "input not representable"
-        self.buf = b.to(DEV)
+        self.buf = KC.slice_buf(mat, dtype, E, tail=(groups - 1) * E, fill=NAN if poison else PAD)
         self.ptr = self.buf.data_ptr() + E * self.es
 
 
@@ -86,72 +63,42 @@ class _Out:
     (rows, c) for accumulating calls."""
 
     def __init__(self, rows, c, dtype, groups=3, prefill=None):
-        DEV = _env()[0]
         self.rows, self.c, self.dtype = rows, c, dtype
         self.es = _es(dtype)
         E = self.E = 16 // self.es
         self.ld = c + groups * E
-        b = torch.full((rows + SPARE, self.ld), NAN, dtype=dtype)
-        if prefill is not None:
-            b[:rows, E:E + c] = prefill.to(dtype)
-            assert torch.equal(b[:rows, E:E + c].float(), prefill.float()), "pre-fill not representable"
-        self.buf = b.to(DEV)
+        self.buf = (KC.out_buf((rows,), self.ld, dtype, SPARE) if prefill is None else
+                    KC.slice_buf(prefill, dtype, E, tail=(groups - 1) * E, spare=SPARE))
         self.ptr = self.buf.data_ptr() + E * self.es
 
     def untouched(self):
         return bool(torch.isnan(self.buf.float()).all())
 
     def payload(self, what):
-        a, E = self.buf.cpu().float(), self.E
-        assert bool(torch.isnan(a[self.rows:]).all()), f"{what}: wrote past the last pixel"
-        assert bool(torch.isnan(a[:, :E]).all()) and bool(torch.isnan(a[:, E + self.c:]).all()), f"{what}: wrote outside its channel slice"
-        out = a[:self.rows, E:E + self.c]
-        nbad = int((~torch.isfinite(out)).sum())
-        assert nbad == 0, f"{what}: {nbad} non-finite outputs"
-        return out.double()
+        return KC.payload(self.buf, self.rows, self.c, what, offset=self.E).double()
 
 
 class _Vec:
     """A float32 per-channel array at offset 4 of a NaN-filled array eight longer."""
 
     def __init__(self, c, prefill=None):
-        DEV = _env()[0]
         self.c = c
-        b = torch.full((c + 8,), NAN, dtype=F32)
-        if prefill is not None:
-            b[4:4 + c] = prefill.float()
-        self.buf = b.to(DEV)
+        self.buf = KC.out_buf((1,), c + 8, F32, 0)[0] if prefill is None else KC.slice_buf(prefill.float()[None], F32, 4)[0]
         self.ptr = self.buf.data_ptr() + 16
 
     def payload(self, what):
-        a = self.buf.cpu()
-        assert bool(torch.isnan(a[:4]).all()) and bool(torch.isnan(a[4 + self.c:]).all()), f"{what}: wrote outside its {self.c} channels"
-        assert bool(torch.isfinite(a[4:4 + self.c]).all()), f"{what}: non-finite"
-        return a[4:4 + self.c].double()
+        return KC.payload(self.buf[None], 1, self.c, what, offset=4)[0].double()
 
 
 def _dev(t, dtype=F32):
-    return t.to(dtype).contiguous().to(_env()[0])
+    return t.to(dtype).contiguous().to(KC.env()[0])
 
 
 def _pair(outs, what):
     """outs: two lists of _Out / _Vec from two runs of one call -> their payloads (first run), after asserting identical bits."""
     for a, b in zip(*outs):
-        assert _same(a.buf, b.buf), f"{what}: two runs differ"
+        assert KC.same_bits(a.buf, b.buf), f"{what}: two runs differ"
     return [a.payload(what) for a in outs[0]]
-
-
-def _ratio(got, ref, bound, what, report):
-    err = (got - ref).abs()
-    r = torch.where(err > 0, err / bound.clamp_min(1e-300), torch.zeros_like(err))
-    worst = float(r.max()) if r.numel() else 0.0
-    report.append((worst, what))
-    assert bool((err <= bound).all()), f"{what}: worst error / bound = {worst:.3f}"
-
-
-def _report(report, title):
-    worst, what = max(report)
-    print(f"{title}: {len(report)} comparisons, worst error / bound = {worst:.3f} ({what})")
 
 
 def _out_round(ref, arith, dtype):
@@ -162,7 +109,7 @@ def _out_round(ref, arith, dtype):
 
 
 def _reduce_ws(c):
-    DEV, L, lib, _ = _env()
+    DEV, L, lib, _ = KC.env()
     return torch.zeros(lib.upa_channel_reduce_workspace_bytes(c) // 8, dtype=F64, device=DEV)
 
 
@@ -170,7 +117,7 @@ def _reduce_ws(c):
 # a. channel reductions and the BatchNorm apply kernels
 # =====================================================================================================================
 def _bn_one(dtype, c, case, report):
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     npix, family, act, acc, with_res, running, seed = case
     code = L.dtype_code(dtype)
     what = f"{'bf16' if dtype == BF16 else 'f32'} c{c} npix{npix} {family} act{act} acc{acc} res{int(with_res)} run{int(running)}"
@@ -193,14 +140,14 @@ def _bn_one(dtype, c, case, report):
     dsum = 1.01 * 64 * U24 * A1 / npix
     b_mean = dsum + U24 * mean.abs() + 1e-300
     b_var = 1.01 * 65 * U24 * A2 / npix + 2 * mean.abs() * dsum + dsum * dsum + U24 * var.abs() + 1e-300
-    _ratio(got[0], mean, b_mean, what + " mean", report)
-    _ratio(got[1], var, b_var, what + " var", report)
+    KC.check_bound(got[0], mean, b_mean, what + " mean", report)
+    KC.check_bound(got[1], var, b_var, what + " var", report)
     assert float(got[1].min()) >= 0.0, what + ": negative variance"
     if running:
         m = TR.f32(MOM)
         unb = npix / (npix - 1) if npix > 1 else 1.0
-        _ratio(got[2], run[0], m * b_mean + 4 * U24 * ((1 - m) * rm0.double().abs() + m * mean.abs()), what + " running mean", report)
-        _ratio(got[3], run[1], m * unb * b_var + 5 * U24 * ((1 - m) * rv0.double().abs() + m * unb * var.abs()), what + " running var", report)
+        KC.check_bound(got[2], run[0], m * b_mean + 4 * U24 * ((1 - m) * rm0.double().abs() + m * mean.abs()), what + " running mean", report)
+        KC.check_bound(got[3], run[1], m * unb * b_var + 5 * U24 * ((1 - m) * rv0.double().abs() + m * unb * var.abs()), what + " running var", report)
     # ---- upa_channel_sum ----
     outs = []
     for _ in range(2):
@@ -208,7 +155,7 @@ def _bn_one(dtype, c, case, report):
         L.check(lib.upa_channel_sum(Z.ptr, npix, c, Z.ld, o[0].ptr, acc, ws.data_ptr(), code, st), what)
         outs.append(o)
     ref = z.double().sum(0) + (g0.double() if acc else 0.0)
-    _ratio(_pair(outs, what + " channel_sum")[0], ref, 1.01 * 64 * U24 * A1 + 2 * U24 * ref.abs() + 1e-300, what + " channel_sum", report)
+    KC.check_bound(_pair(outs, what + " channel_sum")[0], ref, 1.01 * 64 * U24 * A1 + 2 * U24 * ref.abs() + 1e-300, what + " channel_sum", report)
     # ---- upa_bn_act_fwd / upa_bn_act_bwd with the float32-rounded reference statistics ----
     m32, v32 = mean.float(), var.float()
     md, vd, gd, bd = _dev(m32), _dev(v32), _dev(gamma), _dev(beta)
@@ -219,7 +166,7 @@ def _bn_one(dtype, c, case, report):
                                    o[0].ld, RES.ptr if with_res else None, RES.ld if with_res else 0, code, st), what)
         outs.append(o)
     yr, My = TR.bn_act_fwd_ref(z, m32, v32, gamma, beta, EPS, act, res if with_res else None)
-    _ratio(_pair(outs, what + " fwd")[0], yr, _out_round(yr, 4 * TR.C1_FWD_CPU * U24 * My, dtype) + 1e-300, what + " y", report)
+    KC.check_bound(_pair(outs, what + " fwd")[0], yr, _out_round(yr, 4 * TR.C1_FWD_CPU * U24 * My, dtype) + 1e-300, what + " y", report)
     outs = []
     for _ in range(2):
         o = [_Out(npix, c, dtype, 5), _Vec(c, g0 if acc else None), _Vec(c, b0 if acc else None)]
@@ -232,13 +179,14 @@ def _bn_one(dtype, c, case, report):
     b_db = 1.01 * (64 + 2) * U24 * Sb + 16 * U24 * Tb
     rstd, xh, _ = TR._bn_u(z, m32, v32, gamma, beta, EPS)
     feed = (gamma.double() * rstd).abs() * (b_db + U24 * dbeta.abs() + xh.abs() * (b_dg + U24 * dgamma.abs())) / npix
-    _ratio(got[0], dz, _out_round(dz, 4 * TR.C1_BWD_CPU * U24 * (Mdz + T) + feed, dtype) + 1e-300, what + " dz", report)
+    KC.check_bound(got[0], dz, _out_round(dz, 4 * TR.C1_BWD_CPU * U24 * (Mdz + T) + feed, dtype) + 1e-300, what + " dz", report)
     rg, rb = dgamma + (g0.double() if acc else 0.0), dbeta + (b0.double() if acc else 0.0)
-    _ratio(got[1], rg, b_dg + U24 * dgamma.abs() + 2 * U24 * rg.abs() + 1e-300, what + " dgamma", report)
-    _ratio(got[2], rb, b_db + U24 * dbeta.abs() + 2 * U24 * rb.abs() + 1e-300, what + " dbeta", report)
+    KC.check_bound(got[1], rg, b_dg + U24 * dgamma.abs() + 2 * U24 * rg.abs() + 1e-300, what + " dgamma", report)
+    KC.check_bound(got[2], rb, b_db + U24 * dbeta.abs() + 2 * U24 * rb.abs() + 1e-300, what + " dbeta", report)
 
 
 @pytest.mark.parametrize("dtype,c", [(d, c) for d in (F32, BF16) for c in TR.BN_CHANNELS[d]], ids=lambda v: str(v).replace("torch.", ""))
+@KC.stop_after_fault
 def test_channel_reductions_and_bn_apply(dtype, c):
     """upa_bn_stats + upa_bn_finalize, upa_channel_sum, upa_bn_act_fwd, upa_bn_act_bwd on slices: channel-group counts that leave
     idle threads (12, 10, 36 / 34) and the launcher's largest (256), every pixel count of TR.BN_NPIX with every family (at 256 groups the two largest counts with two families), the options
@@ -264,14 +212,15 @@ def test_channel_reductions_and_bn_apply(dtype, c):
     report = []
     for case in TR.bn_cases(dtype, c):
         _bn_one(dtype, c, case, report)
-    _report(report, f"bn {dtype} c{c}")
+    KC.print_report(report, f"bn {dtype} c{c}", "comparisons")
 
 
+@KC.stop_after_fault
 def test_reductions_large_grid_switch():
     """npix = 1 500 001 > 1.5 M: reduce_grid's 1024-block form, c = 8 bf16 (24 MB), upa_bn_stats + upa_bn_finalize and upa_bn_act_bwd,
     uniform family and the impulse family (whose first-chunk pixel moves with the grid).  Same bounds as above.
     Measured on MI355X: 0.998 (dz, the bf16 output rounding)."""
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     npix, c, dtype = 1500001, 8, BF16
     assert TR.reduce_grid(npix) == 1024 and TR.reduce_grid(npix - 1) == 512
     code = L.dtype_code(dtype)
@@ -290,8 +239,8 @@ def test_reductions_large_grid_switch():
             outs.append(o)
         got = _pair(outs, what)
         dsum = 1.01 * 64 * U24 * A1 / npix
-        _ratio(got[0], mean, dsum + U24 * mean.abs() + 1e-300, what + " mean", report)
-        _ratio(got[1], var, 1.01 * 65 * U24 * A2 / npix + 2 * mean.abs() * dsum + dsum * dsum + U24 * var.abs() + 1e-300, what + " var", report)
+        KC.check_bound(got[0], mean, dsum + U24 * mean.abs() + 1e-300, what + " mean", report)
+        KC.check_bound(got[1], var, 1.01 * 65 * U24 * A2 / npix + 2 * mean.abs() * dsum + dsum * dsum + U24 * var.abs() + 1e-300, what + " var", report)
         m32, v32 = mean.float(), var.float()
         md, vd, gd, bd = _dev(m32), _dev(v32), _dev(gamma), _dev(beta)
         outs = []
@@ -305,17 +254,17 @@ def test_reductions_large_grid_switch():
         b_dg, b_db = 1.01 * 72 * U24 * Sg + 16 * U24 * Tg, 1.01 * 66 * U24 * Sb + 16 * U24 * Tb
         rstd, xh, _ = TR._bn_u(z, m32, v32, gamma, beta, EPS)
         feed = (gamma.double() * rstd).abs() * (b_db + U24 * dbeta.abs() + xh.abs() * (b_dg + U24 * dgamma.abs())) / npix
-        _ratio(got[0], dz, _out_round(dz, 4 * TR.C1_BWD_CPU * U24 * (Mdz + T) + feed, dtype) + 1e-300, what + " dz", report)
-        _ratio(got[1], dgamma, b_dg + 2 * U24 * dgamma.abs() + 1e-300, what + " dgamma", report)
-        _ratio(got[2], dbeta, b_db + 2 * U24 * dbeta.abs() + 1e-300, what + " dbeta", report)
-    _report(report, "large grid")
+        KC.check_bound(got[0], dz, _out_round(dz, 4 * TR.C1_BWD_CPU * U24 * (Mdz + T) + feed, dtype) + 1e-300, what + " dz", report)
+        KC.check_bound(got[1], dgamma, b_dg + 2 * U24 * dgamma.abs() + 1e-300, what + " dgamma", report)
+        KC.check_bound(got[2], dbeta, b_db + 2 * U24 * dbeta.abs() + 1e-300, what + " dbeta", report)
+    KC.print_report(report, "large grid", "comparisons")
 
 
 # =====================================================================================================================
 # b. the one-call forms
 # =====================================================================================================================
 def _pack(w, dtype):
-    DEV, L, lib, _ = _env()
+    DEV, L, lib, _ = KC.env()
     cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
     code = L.dtype_code(dtype)
     packed = torch.empty(lib.upa_conv_packed_weight_bytes(cout, cin, k, code), dtype=torch.uint8)
@@ -326,7 +275,7 @@ def _pack(w, dtype):
 
 def _pack_dev(w_dev, cout, cin, k, dtype, flip):
     """upa_pack_conv_weight_dev of a float32 OIHW device tensor; flip = 1: the transposed, flipped weights of the data gradient."""
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     code = L.dtype_code(dtype)
     nb = lib.upa_conv_packed_weight_bytes(cin, cout, k, code) if flip else lib.upa_conv_packed_weight_bytes(cout, cin, k, code)
     out = torch.empty(nb, dtype=torch.uint8, device=DEV)
@@ -336,13 +285,14 @@ def _pack_dev(w_dev, cout, cin, k, dtype, flip):
 
 @pytest.mark.parametrize("k", [1, 3])
 @pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "f32"])
+@KC.stop_after_fault
 def test_one_call_forms_equal_their_separate_calls(dtype, k):
     """upa_conv2d_bn_act_fwd and upa_conv_bn_act_bwd on 2 x (24 -> 40) x 9 x 13 slice views against the calls they stand for, bit for
     bit: forward against upa_conv2d_bias_act + upa_bn_stats + upa_bn_finalize + upa_bn_act_fwd (no_epi_stats = 1 on both sides) and
     against upa_conv2d_bn_stats + upa_bn_act_fwd (default options); backward against upa_bn_act_bwd + upa_conv2d_wgrad +
     upa_conv2d_bias_act with the flipped weights - on the caller's stream and with the weight gradient on a side stream (joined by a
     device synchronise before dw is read), accumulating into dx and not, and with w_packed_t = NULL (dx stays NaN)."""
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     n, cin, cout, h, w, p = 2, 24, 40, 9, 13, k // 2
     code = L.dtype_code(dtype)
     npix = n * h * w
@@ -377,7 +327,7 @@ def test_one_call_forms_equal_their_separate_calls(dtype, k):
         a, b = fwd(one, opts), fwd(sep, opts)
         torch.cuda.synchronize()
         for key in a:
-            assert _same(a[key].buf, b[key].buf), f"forward {sep}: {key} differs"
+            assert KC.same_bits(a[key].buf, b[key].buf), f"forward {sep}: {key} differs"
             a[key].payload(f"forward {key}")
     zv = a["z"]  # the stored z of the last run: the backward's input, read in place
     md, vd = a["m"], a["v"]
@@ -412,7 +362,7 @@ def test_one_call_forms_equal_their_separate_calls(dtype, k):
     for side_stream, acc_dx, with_dx in ((None, 0, True), (side, 1, True), (side, 0, False), (None, 1, True)):
         (a, _wa), (b, _wb) = bwd("one", side_stream, acc_dx, with_dx), bwd("separate", None, acc_dx, with_dx)
         for key in a:
-            assert _same(a[key].buf, b[key].buf), f"backward side={side_stream is not None} acc={acc_dx} dx={with_dx}: {key} differs"
+            assert KC.same_bits(a[key].buf, b[key].buf), f"backward side={side_stream is not None} acc={acc_dx} dx={with_dx}: {key} differs"
         for key in ("dz", "dg", "db", "dw"):
             a[key].payload(f"backward {key}")
         if with_dx:
@@ -439,7 +389,7 @@ def _fused_expected(cin, n, oh, ow):
 
 
 def _dgrad_case(cin, cout, hw, n, acc, dtype, report, seed):
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     h, w = hw
     oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     code = L.dtype_code(dtype)
@@ -463,7 +413,7 @@ def _dgrad_case(cin, cout, hw, n, acc, dtype, report, seed):
     def check(outs, route, K, extra=0.0):
         got = _nchw(_pair(outs, f"{what} {route}")[0], n, h, w)
         bound = CR.conv_bound(v, S, ref, K, NONE, dtype) + extra
-        _ratio(got, ref, bound, f"{what} {route}", report)
+        KC.check_bound(got, ref, bound, f"{what} {route}", report)
 
     # route 1: the interleaving epilogue of conv_big
     if dtype == BF16:
@@ -479,7 +429,7 @@ def _dgrad_case(cin, cout, hw, n, acc, dtype, report, seed):
             check(outs, "fused", 4 * cout)
         else:
             torch.cuda.synchronize()
-            assert all(_same(o[0].buf, _Out(n * h * w, cin, dtype, 3, dx0).buf) for o in outs), what + ": a refused call wrote to dx"
+            assert all(KC.same_bits(o[0].buf, _Out(n * h * w, cin, dtype, 3, dx0).buf) for o in outs), what + ": a refused call wrote to dx"
     # the refusal: conv_big = 1 (and float32 always)
     o = _Out(n * h * w, cin, dtype, 3)
     rc = lib.upa_conv2d_dgrad_s2(DZ.ptr, n, oh, ow, cout, DZ.ld, phase.data_ptr(), o.ptr, h, w, cin, o.ld, acc, code, C.byref(_opts(conv_big=1)), st)
@@ -499,7 +449,7 @@ def _dgrad_case(cin, cout, hw, n, acc, dtype, report, seed):
     # (accumulating: the phase value is stored once before the interleave pass adds and stores again)
     extra = (TR.half_ulp_bf16(v.abs() + CR.conv_bound(v, S, v, 4 * cout, NONE, dtype)) if dtype == BF16 else U24 * v.abs()) if acc else 0.0
     check([[r[0]] for r in outs], "phase + interleave", 4 * cout, extra)
-    assert _same(outs[0][1].buf, outs[1][1].buf)
+    assert KC.same_bits(outs[0][1].buf, outs[1][1].buf)
     outs[0][1].payload(what + " phase maps")
     # route 3: upa_dilate2x + the flipped 3 x 3 convolution
     outs = []
@@ -518,6 +468,7 @@ def _dgrad_case(cin, cout, hw, n, acc, dtype, report, seed):
 
 
 @pytest.mark.parametrize("cin,cout", TR.DGRAD_CHANNELS)
+@KC.stop_after_fault
 def test_stride2_data_gradient_routes_bf16(cin, cout):
     """The three routes to the data gradient of a 3 x 3 stride-2 convolution against TR.dgrad_ref, n = 2, dx maps 13 x 11, 16 x 16 and
     7 x 20 (odd sizes: phase pixels past the last row / column), accumulate 0 and 1, dz and dx as slices.
@@ -535,18 +486,20 @@ def test_stride2_data_gradient_routes_bf16(cin, cout):
     for i, hw in enumerate(TR.DGRAD_MAPS):
         for acc in (0, 1):
             _dgrad_case(cin, cout, hw, 2, acc, BF16, report, 1000 + cin + 10 * i + acc)
-    _report(report, f"dgrad s2 bf16 {cin}<-{cout}")
+    KC.print_report(report, f"dgrad s2 bf16 {cin}<-{cout}", "comparisons")
 
 
+@KC.stop_after_fault
 def test_stride2_data_gradient_routes_f32():
     """float32 has the two fallback routes only: the fused entry refuses, the phase and dilate routes meet the float32 bound."""
     report = []
     for cin, cout in ((12, 20), (24, 64)):
         for i, hw in enumerate(TR.DGRAD_MAPS):
             _dgrad_case(cin, cout, hw, 2, i % 2, F32, report, 1100 + cin + i)
-    _report(report, "dgrad s2 f32")
+    KC.print_report(report, "dgrad s2 f32", "comparisons")
 
 
+@KC.stop_after_fault
 def test_stride2_fused_128_columns():
     """64 <- 128 with enough pixels that big_prepare keeps 128-channel columns (2 x 92 x 92 phase pixels >= 128 per compute unit pair):
     the fused form on 4 cin = 256, a phase boundary on the column boundary, odd dx map 183 x 182, accumulate 1."""
@@ -556,13 +509,14 @@ def test_stride2_fused_128_columns():
         n = 4
     assert _fused_expected(64, n, (h - 1) // 2 + 1, (w - 1) // 2 + 1)
     _dgrad_case(64, 128, (h, w), n, 1, BF16, report, 1200)
-    _report(report, "dgrad s2 fused 64<-128")
+    KC.print_report(report, "dgrad s2 fused 64<-128", "comparisons")
 
 
 # =====================================================================================================================
 # d. upa_conv2d_wgrad: the float32 instantiations and the bf16 generic fallback
 # =====================================================================================================================
 @pytest.mark.parametrize("case", TR.WGRAD_CASES, ids=[c[6].split(":")[0].replace(" ", "_").replace(",", "") + f"_{c[1]}-{c[2]}" for c in TR.WGRAD_CASES])
+@KC.stop_after_fault
 def test_wgrad_generic_branches(case):
     """wgrad_kernel<T, MT, NT, KK> on 2 x 9 x 13 maps, ragged channel counts, x and dz slices, accumulate 0 and 1.  The branch each
     shape takes is read off upa_conv2d_wgrad's dispatch (wgrad_small: cin <= 32 or cout <= 32; the bf16 ring forms need k = 3, or
@@ -570,7 +524,7 @@ def test_wgrad_generic_branches(case):
     Bound: K u S + u |ref| with K = n oh ow the terms per element - one float32 rounding per MFMA accumulation step (bf16 products
     are exact, float32 ones are fused), the partial blocks only shorten the chains; u |ref| for the final add and store.
     Measured on MI355X: 0.003 - 0.028 (a worst-case chain bound; random signs stay far inside it)."""
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     dtype, cin, cout, k, s, p, branch = case
     n, h, w = TR.WGRAD_MAP
     code = L.dtype_code(dtype)
@@ -589,13 +543,14 @@ def test_wgrad_generic_branches(case):
             L.check(lib.upa_conv2d_wgrad(X.ptr, n, h, w, cin, X.ld, DZ.ptr, cout, DZ.ld, o[0].ptr, k, s, p, acc, code, wws.data_ptr(), nws, st), branch)
             outs.append(o)
         ref = dw.reshape(-1) + (dw0.double() if acc else 0.0)
-        _ratio(_pair(outs, branch)[0], ref, K * U24 * S.reshape(-1) + U24 * ref.abs() + 1e-300, f"{branch} acc{acc}", report)
-    _report(report, f"wgrad {branch}")
+        KC.check_bound(_pair(outs, branch)[0], ref, K * U24 * S.reshape(-1) + U24 * ref.abs() + 1e-300, f"{branch} acc{acc}", report)
+    KC.print_report(report, f"wgrad {branch}", "comparisons")
 
 
 @pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "f32"])
+@KC.stop_after_fault
 def test_wgrad_refuses_k5(dtype):
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     n, h, w = TR.WGRAD_MAP
     cin, cout = 40, 40
     x, dz, _ = TR.conv_grad_family(n, cin, cout, h, w, 5, 1, 2, dtype, 9)
@@ -612,20 +567,21 @@ def test_wgrad_refuses_k5(dtype):
 # e. pooling and upsampling backward
 # =====================================================================================================================
 def _pool_call(X, DY, o, n, h, w, c, k, s, p, acc, code, wsb, nws=None):
-    _, _, lib, st = _env()
+    _, _, lib, st = KC.env()
     return lib.upa_maxpool2d_bwd(X.ptr, DY.ptr, n, h, w, c, X.ld, DY.ld, k, s, p, o.ptr, o.ld, acc, code, wsb.data_ptr(),
                                  wsb.numel() if nws is None else nws, st)
 
 
 @pytest.mark.parametrize("ksp", TR.POOL_KSP, ids=lambda v: f"k{v[0]}s{v[1]}p{v[2]}")
 @pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@KC.stop_after_fault
 def test_maxpool_backward(dtype, ksp):
     """upa_maxpool2d_bwd against TR.maxpool_bwd_ref (torch's first-maximum rule, proved on the CPU): every (k, s, p) on maps from
     1 x 1 (smaller than the window: the unrolled bf16 k = 5 kernels clamp their addresses) to 9 x 11 and 8 x 16, c = E and 5 E,
     accumulate 0 and 1, the ties / flat / neginf families.  dy holds multiples of 1 / 128, so float32 adds without rounding:
     float32 results are exact; a bf16 result is the exact sum rounded once - half a bf16 ulp of the float64 sum plus k^2 2^-24 A.
     A map the window does not fit (k > h + 2 p) is refused.  Measured on MI355X: float32 exact, bf16 1.000 (exact ties of the one rounding)."""
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     k, s, p = ksp
     code = L.dtype_code(dtype)
     E = 16 // _es(dtype)
@@ -661,14 +617,15 @@ def test_maxpool_backward(dtype, ksp):
                         report.append((0.0, what))
                     else:
                         arith = k * k * U24 * (A + (_nchw(dx0.double().abs(), n, h, w) if acc else 0.0))
-                        _ratio(got, ref, _out_round(ref, arith, dtype) + 1e-300, f"{what} acc{acc}", report)
-    _report(report, f"maxpool bwd {dtype} {ksp}")
+                        KC.check_bound(got, ref, _out_round(ref, arith, dtype) + 1e-300, f"{what} acc{acc}", report)
+    KC.print_report(report, f"maxpool bwd {dtype} {ksp}", "comparisons")
 
 
 @pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@KC.stop_after_fault
 def test_upsample_backward(dtype):
     """upa_upsample2x_bwd on 1 x 1 and 5 x 7 maps, slices, accumulate 0 and 1; dy multiples of 1 / 128: float32 exact, bf16 rounded once."""
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     code = L.dtype_code(dtype)
     E = 16 // _es(dtype)
     report = []
@@ -692,14 +649,15 @@ def test_upsample_backward(dtype):
                     assert torch.equal(got, ref), what
                     report.append((0.0, what))
                 else:
-                    _ratio(got, ref, _out_round(ref, 5 * U24 * (A + ref.abs()), dtype) + 1e-300, what, report)
-    _report(report, f"upsample bwd {dtype}")
+                    KC.check_bound(got, ref, _out_round(ref, 5 * U24 * (A + ref.abs()), dtype) + 1e-300, what, report)
+    KC.print_report(report, f"upsample bwd {dtype}", "comparisons")
 
 
 # =====================================================================================================================
 # f. optimizer and the element-wise movers
 # =====================================================================================================================
 @pytest.mark.parametrize("n", [1, 255, 1025, 1048577])
+@KC.stop_after_fault
 def test_sumsq(n):
     """upa_sumsq against the exactly rounded sum (math.fsum of the exact float64 squares), accumulate 0 and 1, three runs bit-identical.
     Bound: the squares are exact in float64; a thread adds ceil(n / (256 grid)) of them in turn, eight tree levels fold a block, the
@@ -707,7 +665,7 @@ def test_sumsq(n):
     at most the total, so D 2^-53 sum g^2 with D the number of additions on the longest path - 1 + 8 for n = 255, 23 for n = 1 048 577
     (inside the 4 2^-53 sum g^2 log2(blocks) = 40 2^-53 sum g^2 the 1024-block case was specified with; one block has log2 = 0 but
     still folds eight levels).  n = 1 is exact.  Measured on MI355X: every case came out exactly rounded (error 0)."""
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     g = (torch.rand(n, generator=torch.Generator().manual_seed(n)) * 2 - 1) * 3
     gd = _dev(g)
     ws = torch.zeros(lib.upa_sumsq_workspace_bytes() // 8, dtype=F64, device=DEV)
@@ -724,7 +682,7 @@ def test_sumsq(n):
             out = out.to(DEV)
             L.check(lib.upa_sumsq(gd.data_ptr(), n, out.data_ptr() + 8, acc, ws.data_ptr(), st), "sumsq")
             runs.append(out.cpu())
-        assert all(_same(runs[0], r) for r in runs[1:]), "sumsq: runs differ"
+        assert all(KC.same_bits(runs[0], r) for r in runs[1:]), "sumsq: runs differ"
         assert math.isnan(runs[0][0]) and math.isnan(runs[0][2])
         want = ref + (0.5 if acc else 0.0)
         err = abs(float(runs[0][1]) - want)
@@ -748,13 +706,14 @@ def _sgd_bounds(M, prev, lr, mom, wd, d, first, skipped):
 
 
 @pytest.mark.parametrize("n", [1, 1000, 300001])
+@KC.stop_after_fault
 def test_sgd_nesterov_ema(n):
     """upa_sgd_nesterov_ema and upa_sgd_nesterov_ema_scaled against TR.sgd_ref over three steps (the reference keeps its own float32
     state; the bound of a step carries the bound of the state it started from, _sgd_bounds): a clipping step (1) and two that do not
     clip, weight_decay 5e-4 and 0, ema = NULL, the decay read from ema_d_dev while the scalar ema_d holds a wrong value, zero_grad 0
     and 1.  Scaled: grad_sumsq finite lands on the unscaled step's bound; inf and NaN leave p and the momentum buffer bit-identical,
     still move the EMA and still zero the gradient.  Measured on MI355X: 0.20 / 0.37 / 0.44 for n = 1 / 1000 / 300 001."""
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     gen = torch.Generator().manual_seed(n)
     p0 = torch.rand(n, generator=gen) * 2 - 1
     lr, mom, max_norm = 0.01, 0.9, 10.0
@@ -781,10 +740,10 @@ def test_sgd_nesterov_ema(n):
                 L.check(lib.upa_sgd_nesterov_ema_scaled(*args, sstate.data_ptr(), st), what)
             (pn, gn, bn, en), M = TR.sgd_ref(P, g, B, Em if with_ema else None, ss, max_norm, lr, mom, wd, step == 0, d, zero, scale)
             prev = _sgd_bounds(M, prev, lr, mom, wd, TR.f32(d), step == 0, False)
-            _ratio(Bd.cpu().double(), bn, prev[0] + U24 * bn.abs() + 1e-300, what + " momentum", report)
-            _ratio(Pd.cpu().double(), pn, prev[1] + U24 * pn.abs() + 1e-300, what + " p", report)
+            KC.check_bound(Bd.cpu().double(), bn, prev[0] + U24 * bn.abs() + 1e-300, what + " momentum", report)
+            KC.check_bound(Pd.cpu().double(), pn, prev[1] + U24 * pn.abs() + 1e-300, what + " p", report)
             if with_ema:
-                _ratio(Ed.cpu().double(), en, prev[2] + U24 * en.abs() + 1e-300, what + " ema", report)
+                KC.check_bound(Ed.cpu().double(), en, prev[2] + U24 * en.abs() + 1e-300, what + " ema", report)
                 Em = en.float()
             else:
                 assert torch.equal(Ed.cpu(), p0), what + ": ema = NULL, but the buffer moved"
@@ -797,17 +756,18 @@ def test_sgd_nesterov_ema(n):
                 pb, bb, eb = Pd.clone(), Bd.clone(), Ed.clone()
                 L.check(lib.upa_sgd_nesterov_ema_scaled(Pd.data_ptr(), Gd.data_ptr(), Bd.data_ptr(), Ed.data_ptr(), n, ssd.data_ptr(), max_norm,
                                                         lr, mom, wd, 0, 0.5, None, 1, sstate.data_ptr(), st), "overflow")
-                assert _same(Pd, pb) and _same(Bd, bb), f"grad_sumsq {bad}: p or the momentum buffer moved"
+                assert KC.same_bits(Pd, pb) and KC.same_bits(Bd, bb), f"grad_sumsq {bad}: p or the momentum buffer moved"
                 assert float(Gd.abs().max()) == 0.0
                 want = eb.cpu().double() * 0.5 + 0.5 * pb.cpu().double()
-                _ratio(Ed.cpu().double(), want, 4 * U24 * (eb.cpu().double().abs() + pb.cpu().double().abs()) + 1e-300, f"ema of a skipped step {bad}", report)
-    _report(report, f"sgd n{n}")
+                KC.check_bound(Ed.cpu().double(), want, 4 * U24 * (eb.cpu().double().abs() + pb.cpu().double().abs()) + 1e-300, f"ema of a skipped step {bad}", report)
+    KC.print_report(report, f"sgd n{n}", "comparisons")
 
 
+@KC.stop_after_fault
 def test_grad_scaler_update_sequence():
     """upa_grad_scaler_update over a scripted sequence, all four state floats against TR.scaler_ref after every step: clean steps up to
     growth_interval (4), an overflow at tracker = interval - 1, two overflows in a row (inf, then NaN), growth again."""
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     state = [65536.0, 0.0, 0.0, 0.0]
     sd = _dev(torch.tensor(state))
     seq = [1.0] * 4 + [2.0] * 3 + [math.inf] + [3.0] + [math.inf, math.nan] + [1.0] * 4
@@ -821,10 +781,11 @@ def test_grad_scaler_update_sequence():
 
 
 @pytest.mark.parametrize("n", [1, 1000, 300001])
+@KC.stop_after_fault
 def test_ema_update(n):
     """upa_ema_update: e d + (1 - d) v, d from the argument and from device memory (the scalar then holding a wrong value); three
     float32 roundings and (1 - d): 4 u (|e d| + |(1 - d) v|)."""
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     gen = torch.Generator().manual_seed(n)
     e, v = torch.rand(n, generator=gen) * 2 - 1, torch.rand(n, generator=gen) * 2 - 1
     report = []
@@ -834,16 +795,17 @@ def test_ema_update(n):
         L.check(lib.upa_ema_update(ed.data_ptr(), vd.data_ptr(), n, 0.9 if use_dev else d, dd.data_ptr() if use_dev else None, st), "ema")
         d32 = TR.f32(d)
         ref = e.double() * d32 + (1 - d32) * v.double()
-        _ratio(ed.cpu().double(), ref, 4 * U24 * ((e.double() * d32).abs() + ((1 - d32) * v.double()).abs()) + 1e-300, f"ema dev{int(use_dev)}", report)
+        KC.check_bound(ed.cpu().double(), ref, 4 * U24 * ((e.double() * d32).abs() + ((1 - d32) * v.double()).abs()) + 1e-300, f"ema dev{int(use_dev)}", report)
         assert torch.equal(vd.cpu(), v)
-    _report(report, f"ema n{n}")
+    KC.print_report(report, f"ema n{n}", "comparisons")
 
 
+@KC.stop_after_fault
 def test_cast_add_copy_views_and_layout_movers():
     """upa_cast_view (all four type pairs on slices; float32 -> bf16 must round to nearest even: compared with tensor.to(bfloat16) on
     values that include exact ties both ways), upa_add_view and upa_copy_view (exact on slices: the sums are chosen representable),
     upa_nchw_to_nhwc / upa_nhwc_to_nchw (a permutation, plus the same rounding into bf16)."""
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     rows, c = 37, 24
     gen = torch.Generator().manual_seed(3)
     src32 = torch.rand(rows, c, generator=gen) * 4 - 2
@@ -860,9 +822,9 @@ def test_cast_add_copy_views_and_layout_movers():
             L.check(lib.upa_cast_view(S.ptr, L.dtype_code(sdt), S.ld, o[0].ptr, L.dtype_code(ddt), o[0].ld, rows, c, st), "cast")
             outs.append(o)
         for a, b in zip(*outs):
-            assert _same(a.buf, b.buf)
+            assert KC.same_bits(a.buf, b.buf)
         got = outs[0][0].buf.cpu()[:rows, outs[0][0].E:outs[0][0].E + c]
-        assert torch.equal(_bits(got), _bits(src.to(ddt))), f"cast {sdt} -> {ddt}"
+        assert KC.same_bits(got, src.to(ddt)), f"cast {sdt} -> {ddt}"
         a = outs[0][0].buf.cpu().float()
         assert bool(torch.isnan(a[rows:]).all()) and bool(torch.isnan(a[:, :outs[0][0].E]).all()) and bool(torch.isnan(a[:, outs[0][0].E + c:]).all())
     for dtype in (F32, BF16):
@@ -884,7 +846,7 @@ def test_cast_add_copy_views_and_layout_movers():
             y = _Out(n * h * w, cpad, dtype, 3)
             L.check(lib.upa_nchw_to_nhwc(xd.data_ptr(), n, cc, h, w, y.ptr, y.ld, code, st), "nchw_to_nhwc")
             got = y.buf.cpu()[:n * h * w, y.E:y.E + cc]
-            assert torch.equal(_bits(got), _bits(_rows(x).to(dtype))), f"nchw_to_nhwc {dtype} c{cc}"
+            assert KC.same_bits(got, _rows(x).to(dtype)), f"nchw_to_nhwc {dtype} c{cc}"
             back = torch.full((n * cc * h * w + 8,), NAN, device=DEV)
             L.check(lib.upa_nhwc_to_nchw(y.ptr, n, h, w, cc, y.ld, back.data_ptr() + 16, code, st), "nhwc_to_nchw")
             bk = back.cpu()
@@ -897,11 +859,12 @@ def test_cast_add_copy_views_and_layout_movers():
 # g. refusals
 # =====================================================================================================================
 @pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "f32"])
+@KC.stop_after_fault
 def test_refusals_leave_every_output_untouched(dtype):
     """Every pitch argument of every entry that is not a multiple of 16 bytes, c not a multiple of E, c > 256 E, npix = 0, and
     upa_maxpool2d_bwd with k > h + 2 pad, pad > k / 2, k = 16 or a workspace one byte short, upa_cast_view with c = 0: UPA_EINVAL, and
     every output buffer is bit-identical to its pre-fill afterwards - nothing was launched."""
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     code = L.dtype_code(dtype)
     E = 16 // _es(dtype)
     n, h, w, c = 2, 4, 6, 2 * E
@@ -976,7 +939,7 @@ def test_refusals_leave_every_output_untouched(dtype):
     assert not wrong, f"not refused with UPA_EINVAL: {wrong}"
     torch.cuda.synchronize()
     for t, b in zip([t.buf for t in outs] + [ws, wsb], before):
-        assert _same(t, b), "a refused call wrote to one of its buffers"
+        assert KC.same_bits(t, b), "a refused call wrote to one of its buffers"
     # ... and the unvaried calls are valid ones
     for name, rc in (("bn_stats", stats()), ("channel_sum", csum()), ("bn_act_fwd", fwd()), ("bn_act_bwd", bwd()), ("dilate2x", dil()),
                      ("upsample2x_bwd", ups()), ("interleave2x", itl()), ("maxpool2d_bwd", pool()), ("cast_view", cast())):

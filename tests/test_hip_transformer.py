@@ -1,11 +1,9 @@
 """-m gpu: every `upa_mhsa` instantiation and the RT-DETR row / box / sampling kernels of csrc/transformer.hip, each called
 through the C ABI and compared with the float64 references of tests/transformer_ref.py.
 
-Conventions of this file: every output goes into a buffer pre-filled with NaN that has four spare rows after the last one
-and - where the call takes an output pitch - spare columns; the sentinels must still be NaN afterwards and the payload
-finite.  Every call runs twice into two such buffers and the two must agree bit for bit.  Input padding is 7.0, so a read
-past a row shows as a wrong number, not as a zero.  Tolerances are derived in the docstrings; the `print`s give the worst
-error / bound ratio of each case (pytest -s)."""
+Buffers, sentinels, the two bit-identical runs, the per-element bounds and the fault latch: the conventions of tests/kernel_check.py:
+outputs have four
+spare rows and, where the call takes a pitch, spare columns; input padding is 7.0.  Tolerances are derived in the docstrings."""
 
 import math
 
@@ -14,6 +12,7 @@ import torch
 
 from oracle import modules as om
 from tests import transformer_ref as TR
+from tests import kernel_check as KC
 
 pytestmark = pytest.mark.gpu
 
@@ -22,40 +21,9 @@ SPARE = 4
 PAD = 7.0
 
 
-def _env():
-    from tests.hip_utils import DEV
-    from ultralytics_pro_amd import _lib as L
-    return DEV, L, L.lib(), L.current_stream(DEV)
-
-
 def _rnd(t, dtype):
     """The values a buffer of `dtype` really stores, as float32."""
     return t.to(dtype).float()
-
-
-def _nan_buf(rows, pitch, dtype, dev):
-    return torch.full((rows + SPARE, pitch), float("nan"), dtype=dtype, device=dev)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
-
-
-def _payload(bufs, rows, cols, what):
-    """Both runs identical in every bit, sentinels untouched, payload finite -> payload of the first run (CPU float32)."""
-    a, b = (x.cpu() for x in bufs)
-    assert torch.equal(_bits(a), _bits(b)), f"{what}: two runs differ"
-    af = a.float()
-    assert bool(torch.isnan(af[rows:]).all()) and bool(torch.isnan(af[:, cols:]).all()), f"{what}: wrote outside its rows / columns"
-    out = af[:rows, :cols]
-    assert bool(torch.isfinite(out).all()), f"{what}: non-finite output"
-    return out
-
-
-def _worst(err, bound):
-    """max of err / bound (0 / 0 = 0) for the report, and the pass flag."""
-    ratio = torch.where(err > 0, err / bound.clamp_min(1e-300), torch.zeros_like(err))
-    return float(ratio.max()), bool((err <= bound).all())
 
 
 # =====================================================================================================================
@@ -76,7 +44,7 @@ def _mhsa_pitches(heads, D, dtype, mfma):
 
 def _mhsa_call(q, k, v, res, scale, dtype, mfma, what):
     """q, k, v, res: (n, L, heads, D) CPU float32 holding values `dtype` stores exactly.  Returns y as (n, L, heads, D)."""
-    DEV, L_, lib, st = _env()
+    DEV, L_, lib, st = KC.env()
     n, L, heads, D = q.shape
     hd, es = heads * D, torch.empty(0, dtype=dtype).element_size()
     ldqkv, ldy, ldr = _mhsa_pitches(heads, D, dtype, mfma)
@@ -89,12 +57,12 @@ def _mhsa_call(q, k, v, res, scale, dtype, mfma, what):
         rbuf = torch.full((n * L, ldr), PAD, dtype=dtype)
         rbuf[:, :hd] = res.reshape(n * L, hd).to(dtype)
         rbuf = rbuf.to(DEV)
-    ys = [_nan_buf(n * L, ldy, dtype, DEV) for _ in range(2)]
+    ys = [KC.out_buf((n * L,), ldy, dtype, SPARE, dev=DEV) for _ in range(2)]
     for y in ys:
         L_.check(lib.upa_mhsa(buf.data_ptr(), buf.data_ptr() + hd * es, buf.data_ptr() + 2 * hd * es, ldqkv, n, L, heads, D, float(scale),
                               rbuf.data_ptr() if rbuf is not None else None, ldr, y.data_ptr(), ldy, L_.dtype_code(dtype), st), what)
     torch.cuda.synchronize()
-    return _payload(ys, n * L, hd, what).reshape(n, L, heads, D)
+    return KC.payload_of_two(ys, n * L, hd, what).reshape(n, L, heads, D)
 
 
 def _mhsa_families(n, L, heads, D, scale, dtype, g, with_res):
@@ -151,31 +119,25 @@ def _mhsa_check(kind, n, L, heads, D, dtype, seed, report):
                     bound = f32b + 2.0 ** -8 * ref.abs()
                 else:
                     bound = (0.0 if name == "const_v" else 2.0 ** -7 * vmax) + 2.0 ** -8 * ref.abs()
-                ratio, ok = _worst((y - ref).abs(), bound)
-                report.append((ratio, what))
                 # measured on MI355X (worst error / bound): f32 0.80 on the late-maximum families at D = 64, L = 130 (64-term score sums
                 # of |s| ~ 130; a float32 CPU emulation of the four-partition online softmax gives the same 0.80), 0.32 on the uniform
                 # family; bf16 vector 0.996 (the output rounding itself: half an ulp at the foot of a binade); matrix-core 0.40
-                assert ok, f"{what}: worst error / bound = {ratio:.3f}"
+                KC.check_bound(y, ref, bound, what, report)
                 if name == "const_v" and res is None:  # a pix0 or h * D slip shows as another head's constant
                     assert float((y - v.double()).abs().max()) <= 2.0 ** -8 * float(v.max())
-
-
-def _print_report(report, title):
-    ratio, what = max(report)
-    print(f"{title}: {len(report)} calls, worst error / bound = {ratio:.3f} ({what})")
 
 
 @pytest.mark.parametrize("L", [1, 5, 63, 64, 65, 130])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 @pytest.mark.parametrize("D", [4, 8, 16, 32, 64])
+@KC.stop_after_fault
 def test_mhsa_vector_every_head_dim(D, dtype, L):
     """mhsa_kernel<float | bf16, D, 4> for every D: n = 2, heads = 3, q / k / v three column ranges of one padded buffer, y and
     the residual on pitches of their own.  L = 1 / 5 leave key partitions without keys, 63 / 64 / 65 straddle a 64-query block,
     130 takes three.  The residual pitch is 2 mod 4, which keeps bf16 d = 32 off the matrix-core kernel at L >= 16 too."""
     report = []
     _mhsa_check("f32" if dtype == torch.float32 else "bf16vec", 2, L, 3, D, dtype, 1000 * D + L, report)
-    _print_report(report, f"mhsa vector D={D} {dtype} L={L}")
+    KC.print_report(report, f"mhsa vector D={D} {dtype} L={L}")
 
 
 def _mfma_max_keys():
@@ -186,15 +148,17 @@ def _mfma_max_keys():
 
 @pytest.mark.parametrize("n,heads", [(1, 1), (2, 4)], ids=["n1h1", "n2h4"])
 @pytest.mark.parametrize("L", [16, 17, 31, 32, 33, 48, 143, 300])
+@KC.stop_after_fault
 def test_mhsa_mfma_tails_and_scale(L, n, heads):
     """mhsa_mfma_bf16_d32_kernel (bf16, d = 32, ldr % 4 == 0, L >= 16): the second 16-key tile of the last block empty (16, 48's
     second block), partial (17, 31, 33, 143, 300) or full (32); 9 (L = 143) and 19 (L = 300) query tiles that do not fill
     chunks x waves, so one wave's tile lies past L."""
     report = []
     _mhsa_check("mfma", n, L, heads, 32, torch.bfloat16, 7000 + L * 10 + heads, report)
-    _print_report(report, f"mhsa mfma L={L} n={n} heads={heads}")
+    KC.print_report(report, f"mhsa mfma L={L} n={n} heads={heads}")
 
 
+@KC.stop_after_fault
 def test_mhsa_mfma_largest_key_count():
     """The largest L the matrix-core launch admits (1248 keys: 156.5 KiB of LDS), n = heads = 1; the vector kernel would refuse
     it (128 L + 34816 bytes > 158 KiB), so a pass is the matrix-core kernel's."""
@@ -208,16 +172,15 @@ def test_mhsa_mfma_largest_key_count():
         y = _mhsa_call(q, k, v, res, scale, torch.bfloat16, True, what).double()
         ref = TR.attention_ref(q, k, v, scale, res)
         bound = (0.0 if name == "const_v" else 2.0 ** -7 * float(v.abs().max())) + 2.0 ** -8 * ref.abs()
-        ratio, ok = _worst((y - ref).abs(), bound)
-        report.append((ratio, what))
-        assert ok, f"{what}: worst error / bound = {ratio:.3f}"
-    _print_report(report, "mhsa mfma largest L")
+        KC.check_bound(y, ref, bound, what, report)
+    KC.print_report(report, "mhsa mfma largest L")
 
 
+@KC.stop_after_fault
 def test_mhsa_refuses_what_does_not_fit():
     """One key past what LDS holds, a head dim without an instantiation, a pitch that is no multiple of 16 bytes: UpaError with
     the library's message, nothing launched, the output untouched."""
-    DEV, L_, lib, st = _env()
+    DEV, L_, lib, st = KC.env()
 
     def attempt(dtype, L, D, ldqkv=None):
         heads, n = 1, 1
@@ -225,7 +188,7 @@ def test_mhsa_refuses_what_does_not_fit():
         ld, ldy, _ = _mhsa_pitches(heads, max(D, 16), dtype, True)
         ld = ld if ldqkv is None else ldqkv
         buf = torch.zeros(n * L + 1, max(ld, 3 * D) + 16, dtype=dtype, device=DEV)
-        y = _nan_buf(n * L, ldy, dtype, DEV)
+        y = KC.out_buf((n * L,), ldy, dtype, SPARE, dev=DEV)
         try:
             L_.check(lib.upa_mhsa(buf.data_ptr(), buf.data_ptr() + D * es, buf.data_ptr() + 2 * D * es, ld, n, L, heads, D, 1.0,
                                   None, 0, y.data_ptr(), ldy, L_.dtype_code(dtype), st), "mhsa")
@@ -256,13 +219,14 @@ def test_mhsa_refuses_what_does_not_fit():
 # =====================================================================================================================
 @pytest.mark.parametrize("M", [1, 3, 6, 301])
 @pytest.mark.parametrize("C", [1, 8, 100, 256, 1000])
+@KC.stop_after_fault
 def test_layer_norm_rows(C, M):
     """layer_norm_kernel (one wave per row, four rows per workgroup) at C below / across / not a multiple of the 64 lanes and at
     M % 4 != 0, on zero-mean, mean-30 and mean-1000 rows (sigma about 1) and on rows of one repeated value (sigma = 0: the output
     is beta).  Per row: |err| <= 8 * 2^-24 * (max|x + r| / sqrt(var + eps) + max|y_ref|) * max|gamma| - one rounding of x + r, of
     the mean and of the difference each move the normalised value by 2^-24 max|x + r| / sigma, the scale and shift round at
     2^-24 |y|; F.layer_norm in float32 stays within 1.64 of that unit, the factor 8 covers this kernel's reduction tree."""
-    DEV, L_, lib, st = _env()
+    DEV, L_, lib, st = KC.env()
     g = torch.Generator().manual_seed(31 * C + M)
     gamma = torch.rand(C, generator=g) * 1.5 + 0.25
     gamma[0] = -1.75
@@ -282,34 +246,33 @@ def test_layer_norm_rows(C, M):
             xd, rd = x.to(DEV), (r.to(DEV) if with_res else None)
             for eps in (1e-5, 1e-3):
                 what = f"layer_norm {family} C={C} M={M} res={with_res} eps={eps}"
-                ys = [_nan_buf(M, C, torch.float32, DEV) for _ in range(2)]
+                ys = [KC.out_buf((M,), C, torch.float32, SPARE, dev=DEV) for _ in range(2)]
                 for y in ys:
                     L_.check(lib.upa_layer_norm(xd.data_ptr(), rd.data_ptr() if with_res else None, M, C, gd.data_ptr(), bd.data_ptr(), eps,
                                                 y.data_ptr(), st), what)
                 torch.cuda.synchronize()
-                y = _payload(ys, M, C, what).double()
+                y = KC.payload_of_two(ys, M, C, what).double()
                 ref = TR.layer_norm_ref(x, r, gamma, beta, eps)
                 z = x.double() + (r.double() if with_res else 0)
                 var = z.var(-1, unbiased=False, keepdim=True)
                 bound = 8 * U24 * (z.abs().amax(-1, keepdim=True) / torch.sqrt(var + eps) + ref.abs().amax(-1, keepdim=True)) * float(gamma.abs().max())
-                ratio, ok = _worst((y - ref).abs(), bound.expand_as(ref))
-                report.append((ratio, what))
                 # measured on MI355X: 0.73 of the bound on the all-equal rows at C = 1000, M = 301, eps = 1e-5 (the rounded mean of 1000
                 # equal values times 1 / sqrt(eps); a float32 CPU emulation of the lane-strided sums and the xor butterfly gives the same
                 # figure), 0.29 on the mean-1000 family
-                assert ok, f"{what}: worst error / bound = {ratio:.3f}"
-    _print_report(report, f"layer_norm C={C} M={M}")
+                KC.check_bound(y, ref, bound.expand_as(ref), what, report)
+    KC.print_report(report, f"layer_norm C={C} M={M}")
 
 
 # =====================================================================================================================
 # upa_rows_add / upa_rows_scale / upa_rows_gather
 # =====================================================================================================================
 @pytest.mark.parametrize("M,C", [(1, 1), (7, 100), (300, 256), (8200, 256)], ids=["1x1", "7x100", "300x256", "8200x256"])
+@KC.stop_after_fault
 def test_row_utilities_exact(M, C):
     """rows_kernel in its three modes, bit for bit against torch on the CPU.  8200 x 256 elements are more than the 8192 x 256
     threads the grid is capped at: the grid-stride loop takes a second trip.  Gather: descending, the first and the last source
     row, repeats, and more output rows than source rows."""
-    DEV, L_, lib, st = _env()
+    DEV, L_, lib, st = KC.env()
     g = torch.Generator().manual_seed(M + C)
     a, b = torch.randn(M, C, generator=g), torch.randn(M, C, generator=g) * 3
     sc = torch.randn(M, generator=g)
@@ -323,15 +286,15 @@ def test_row_utilities_exact(M, C):
     srcd = src.to(DEV)
 
     def run(fn, rows, *args):
-        ys = [_nan_buf(rows, C, torch.float32, DEV) for _ in range(2)]
+        ys = [KC.out_buf((rows,), C, torch.float32, SPARE, dev=DEV) for _ in range(2)]
         for y in ys:
             L_.check(fn(*args, y.data_ptr(), rows, C, st), fn.__name__)
         torch.cuda.synchronize()
-        return _payload(ys, rows, C, fn.__name__)
+        return KC.payload_of_two(ys, rows, C, fn.__name__)
 
-    assert torch.equal(_bits(run(lib.upa_rows_add, M, ad.data_ptr(), bd.data_ptr())), _bits(a + b))
-    assert torch.equal(_bits(run(lib.upa_rows_scale, M, ad.data_ptr(), scd.data_ptr())), _bits(a * sc[:, None]))
-    assert torch.equal(_bits(run(lib.upa_rows_gather, m_out, srcd.data_ptr(), idxd.data_ptr())), _bits(src[idx.long()]))
+    assert torch.equal(KC.bits(run(lib.upa_rows_add, M, ad.data_ptr(), bd.data_ptr())), KC.bits(a + b))
+    assert torch.equal(KC.bits(run(lib.upa_rows_scale, M, ad.data_ptr(), scd.data_ptr())), KC.bits(a * sc[:, None]))
+    assert torch.equal(KC.bits(run(lib.upa_rows_gather, m_out, srcd.data_ptr(), idxd.data_ptr())), KC.bits(src[idx.long()]))
 
 
 # =====================================================================================================================
@@ -339,18 +302,16 @@ def test_row_utilities_exact(M, C):
 # =====================================================================================================================
 def _flat_call(fn, n_rows, cols, tail, what, *inputs):
     """fn(inputs..., y, *tail, stream) with the CPU tensors `inputs` uploaded and y a contiguous (n_rows, cols) output."""
-    DEV, L_, lib, st = _env()
+    DEV, L_, lib, st = KC.env()
     dev = [t.to(DEV) for t in inputs]
-    ys = [_nan_buf(n_rows, cols, torch.float32, DEV) for _ in range(2)]
+    ys = [KC.out_buf((n_rows,), cols, torch.float32, SPARE, dev=DEV) for _ in range(2)]
     for y in ys:
         L_.check(fn(*[t.data_ptr() for t in dev], y.data_ptr(), *tail, st), what)
     torch.cuda.synchronize()
-    a, b = (x.cpu() for x in ys)
-    assert torch.equal(_bits(a), _bits(b)), f"{what}: two runs differ"
-    assert bool(torch.isnan(a[n_rows:]).all()), f"{what}: wrote past its last row"
-    return a[:n_rows]
+    return KC.payload_of_two(ys, n_rows, cols, what, finite=False)   # (the +inf anchors of invalid tokens are values here)
 
 
+@KC.stop_after_fault
 def test_box_arithmetic_edges():
     """box_kernel's three modes and rtdetr_output_kernel at what the decoder tests never feed them: references at and beyond the
     inverse_sigmoid clamps (0, 1, eps = 1e-5) crossed with deltas up to +-30, the +inf anchors of invalid tokens, sigmoid
@@ -358,7 +319,7 @@ def test_box_arithmetic_edges():
     box_refine: |err| <= 4 * 2^-24 (outputs in [0, 1]) and exactly 0 / 1 where the float64 value rounds to them in float32.
     sigmoid / score columns: |err| <= 2 * 2^-24 (expf, the sum and the quotient round once each on a value <= 1).
     Measured on MI355X: box_refine 0.17 of its bound, sigmoid 0.16, score columns 0.74 (a sigmoid just under 1: one ulp there is 2^-24)."""
-    DEV, L_, lib, st = _env()
+    DEV, L_, lib, st = KC.env()
     # ---- box_refine: 40 (reference, delta) pairs, tiled to 70 boxes = 280 values: two workgroups, the second partial
     n_boxes = 70
     ref = torch.tensor(TR.BOX_REFS, dtype=torch.float32).repeat_interleave(len(TR.BOX_DELTAS)).repeat(7).view(n_boxes, 4)
@@ -386,7 +347,7 @@ def test_box_arithmetic_edges():
     d = torch.randn(nb, 4, generator=g) * 3
     y = _flat_call(lib.upa_box_add_anchors, nb, 4, (nb,), "box_add_anchors", d, tok, anchors)
     want = TR.box_add_anchors_ref(d, tok, anchors)
-    assert torch.equal(_bits(y), _bits(want))
+    assert torch.equal(KC.bits(y), KC.bits(want))
     bad = ~valid[tok.long()]
     assert bool((y[bad] == float("inf")).all()) and bool(torch.isfinite(y[~bad]).all())
     s = _flat_call(lib.upa_sigmoid, nb, 4, (nb * 4,), "sigmoid(anchored boxes)", y.contiguous())
@@ -416,7 +377,7 @@ def test_box_arithmetic_edges():
             y = _flat_call(lib.upa_rtdetr_output, M, 4 + nc, (M, nc), f"rtdetr_output nc={nc} M={M}", boxes, scores)
             assert not bool(torch.isnan(y).any())
             want = TR.rtdetr_output_ref(boxes, scores)
-            assert torch.equal(_bits(y[:, :4]), _bits(want[:, :4].float()))
+            assert torch.equal(KC.bits(y[:, :4]), KC.bits(want[:, :4].float()))
             e = float((y[:, 4:].double() - want[:, 4:]).abs().max())
             worst = max(worst, e)
             assert e <= 2 * U24, (nc, M, e)
@@ -470,6 +431,7 @@ def _msd_inputs(family, logit_family, shapes, bs, nq, heads, g):
 @pytest.mark.parametrize("n_levels", [1, 2, 3, 4])
 @pytest.mark.parametrize("vdtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 @pytest.mark.parametrize("d", [8, 32])
+@KC.stop_after_fault
 def test_msdeform_vs_f64_grid_sample(d, vdtype, n_levels):
     """msdeform_kernel<8 | 32, 4, float | bf16> against the oracle's grid_sample formulation in float64: 1 - 4 levels of odd maps,
     15 and 80 (b, q, head) items (a partial block either way), a value pitch wider than heads * d with 7.0 next to the data,
@@ -480,7 +442,7 @@ def test_msdeform_vs_f64_grid_sample(d, vdtype, n_levels):
     The +-3e9 offsets are what found the unclamped `(int)floorf(ix)` of the exact-f32 branch: the coordinate converts to INT_MAX,
     `x0 + 1` wraps, the compiled range test `x0 > -2 && x0 + 1 < W` holds for the wrapped value, and the corner load went to a wild
     address (an illegal memory access, not a wrong number); the branch now clamps the integer corner as the bf16 branch does."""
-    DEV, L_, lib, st = _env()
+    DEV, L_, lib, st = KC.env()
     shapes = MAPS[:n_levels]
     T = sum(h * w for h, w in shapes)
     shp = torch.tensor([v for s_ in shapes for v in s_], dtype=torch.int32)
@@ -500,12 +462,12 @@ def test_msdeform_vs_f64_grid_sample(d, vdtype, n_levels):
                 what = f"msdeform d={d} {vdtype} levels={n_levels} items={bs * nq * heads} {family} {lf}"
                 off, lg, ref = _msd_inputs(family, lf, shapes, bs, nq, heads, g)
                 offd, lgd, refd = off.to(DEV), lg.to(DEV), ref.to(DEV)
-                ys = [_nan_buf(bs * nq, C, torch.float32, DEV) for _ in range(2)]
+                ys = [KC.out_buf((bs * nq,), C, torch.float32, SPARE, dev=DEV) for _ in range(2)]
                 for y in ys:
                     L_.check(lib.upa_msdeform_attn_strided(vd.data_ptr(), L_.dtype_code(vdtype), ldv, shp.data_ptr(), n_levels, bs, heads, d,
                                                            offd.data_ptr(), lgd.data_ptr(), refd.data_ptr(), nq, 4, y.data_ptr(), st), what)
                 torch.cuda.synchronize()
-                y = _payload(ys, bs * nq, C, what).double()
+                y = KC.payload_of_two(ys, bs * nq, C, what).double()
                 want = TR.msdeform_ref(rows, shapes, bs, heads, d, off, lg, ref)
                 if family == "wild":
                     assert bool((want == 0).all()) and bool((y == 0).all()), f"{what}: a sample far outside the map contributed"
@@ -517,4 +479,4 @@ def test_msdeform_vs_f64_grid_sample(d, vdtype, n_levels):
                 # measured on MI355X: f32 values 0.72 of the bound at worst (d = 32, three levels, 15 items), 0.31-0.41 elsewhere;
                 # bf16 values 0.015
                 assert e <= tol, f"{what}: error {e:.3g} > {tol:.3g}"
-    _print_report(report, f"msdeform d={d} {vdtype} levels={n_levels}")
+    KC.print_report(report, f"msdeform d={d} {vdtype} levels={n_levels}")

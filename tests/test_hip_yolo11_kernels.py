@@ -2,10 +2,9 @@
 by element, with the float64 references and derived bounds of tests/yolo11_kernel_ref.py (pinned on the CPU by
 tests/test_yolo11_kernel_ref.py).
 
-Conventions: every input is a channel slice of a wider buffer whose other elements are NaN (a read outside the view poisons the
-result); every output is a channel slice of a wider buffer, with four spare pixel rows, filled with one NaN bit pattern as canary:
-after the call every element outside the slice must still hold exactly those bits and the payload must be finite.  Batch is 2 unless
-stated.  The `print`s give the worst error / bound of each test (pytest -s).
+Buffers, sentinels, the two bit-identical runs, the per-element bounds and the fault latch: the conventions of tests/kernel_check.py,
+with the
+output canary held to its very NaN bits.  Batch is 2 unless stated.
 
 Which instantiation a parametrisation reaches (from the dispatch conditions; neither entry point has a variant query):
   upa_dwconv2d       vec = c, ldx, ldy multiples of V (f32 4, bf16 8) and x, y, weight, bias 16-byte aligned -> dwconv3_kernel<T, V, S>,
@@ -34,6 +33,7 @@ import torch
 
 from tests import yolo11_kernel_ref as Y
 from tests.conv_ref import ACT_NONE, ACT_SILU
+from tests import kernel_check as KC
 
 pytestmark = pytest.mark.gpu
 
@@ -43,53 +43,25 @@ UPA_EINVAL, UPA_EUNSUPPORTED = -1, -2
 NAN = float("nan")
 
 
-def _env():
-    from tests.hip_utils import DEV
-    from ultralytics_pro_amd import _lib as L
-    return DEV, L, L.lib(), L.current_stream(DEV)
-
-
 def _es(dtype):
     return 2 if dtype == BF16 else 4
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
-
-
-def _worst(y, ref, bound):
-    err = (y - ref).abs()
-    ratio = torch.where(err > 0, err / bound.clamp_min(1e-300), torch.zeros_like(err))
-    return float(ratio.max())
 
 
 class _View:
     """`rows` x `c` values at channel `off` of a (rows + spare) x ld buffer of NaN."""
 
     def __init__(self, rows, c, ld, off, dtype, values=None):
-        DEV = _env()[0]
         self.rows, self.c, self.ld, self.off, self.dtype = rows, c, ld, off, dtype
-        buf = torch.full((rows + (0 if values is not None else SPARE), ld), NAN, dtype=dtype)
-        if values is not None:
-            buf[:rows, off:off + c] = values.to(dtype)
-            assert torch.equal(buf[:rows, off:off + c].float(), values.float()), "values not representable"
-        self.buf = buf.to(DEV)
+        self.buf = (KC.out_buf((rows,), ld, dtype, SPARE, dev="cpu").to(KC.env()[0]) if values is None else
+                    KC.slice_buf(values, dtype, off, tail=ld - off - c))
         self.ptr = self.buf.data_ptr() + off * _es(dtype)
 
     def untouched(self):
-        a = _bits(self.buf.cpu())
-        return bool((a == _bits(torch.full((1,), NAN, dtype=self.dtype))[0]).all())
+        return bool((KC.bits(self.buf) == KC.bits(torch.full((1,), NAN, dtype=self.dtype))[0]).all())
 
     def payload(self, what):
         """Canary intact in every bit outside the slice, payload finite -> (rows, c) float64."""
-        a = self.buf.cpu()
-        outside = torch.ones(a.shape, dtype=torch.bool)
-        outside[:self.rows, self.off:self.off + self.c] = False
-        canary = _bits(torch.full((1,), NAN, dtype=self.dtype))[0]
-        assert bool((_bits(a)[outside] == canary).all()), f"{what}: wrote outside its view"
-        out = a[:self.rows, self.off:self.off + self.c].double()
-        assert bool(torch.isfinite(out).all()), f"{what}: non-finite output"
-        return out
+        return KC.payload(self.buf, self.rows, self.c, what, offset=self.off, exact_fill=True).double()
 
 
 def _rows(t_nchw):
@@ -101,7 +73,7 @@ def _rows(t_nchw):
 # upa_dwconv2d
 # =====================================================================================================================
 def _dw_call(x, w9c, bias, stride, act, dtype, off=None, k=3, pad=1):
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     n, c, h, w = x.shape
     E = 16 // _es(dtype)
     off = E if off is None else off
@@ -123,19 +95,13 @@ def _dw_check(family, n, c, h, w, stride, act, dtype, seed, report, off=None):
     v, S, ref = Y.dw_ref(x, w9c, bias, stride, act)
     if family == "saturated" and v.numel() >= 400:
         assert float(v.max()) > 60 and float(v.min()) < -60, what
-    ratio = _worst(y, _rows(ref), _rows(Y.dw_bound(v, S, ref, act, dtype)))
-    report.append((ratio, what))
-    assert ratio <= 1.0, f"{what}: worst error / bound = {ratio:.3f}"
-
-
-def _print_report(report, title):
-    ratio, what = max(report)
-    print(f"{title}: {len(report)} calls, worst error / bound = {ratio:.3f} ({what})")
+    KC.check_bound(y, _rows(ref), _rows(Y.dw_bound(v, S, ref, act, dtype)), what, report)
 
 
 @pytest.mark.parametrize("act", [ACT_NONE, ACT_SILU], ids=["none", "silu"])
 @pytest.mark.parametrize("stride", [1, 2])
 @pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@KC.stop_after_fault
 def test_dwconv_every_instantiation(dtype, stride, act):
     """Three families x seven maps (1 x 1 to 5 x 4: every border combination, odd and even sizes for stride 2) x c 4 / 6 / 8 / 12 / 40,
     which reach V = 4 / 8 and V = 1 in both types (module docstring), and c = 8 views at channel offset 1, which must take V = 1."""
@@ -145,21 +111,23 @@ def test_dwconv_every_instantiation(dtype, stride, act):
             for c in Y.DW_CHANNELS:
                 _dw_check(family, 2, c, h, w, stride, act, dtype, 10 * c + fi, report)
             _dw_check(family, 2, 8, h, w, stride, act, dtype, 90 + fi, report, off=1)
-    _print_report(report, f"dwconv {dtype} s{stride} act{act}")
+    KC.print_report(report, f"dwconv {dtype} s{stride} act{act}")
 
 
 @pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@KC.stop_after_fault
 def test_dwconv_row_loop_second_trip_crosses_the_image_boundary(dtype):
     """n = 2, h = 33000, w = 1, c = 8: 66000 output rows on a grid of 65535, so blocks 0 .. 464 take a second trip, which lands in image
     1 while their first was in image 0 (b = row / oh is recomputed per trip)."""
     report = []
     for family in ("uniform", "impulse"):
         _dw_check(family, 2, 8, 33000, 1, 1, ACT_SILU, dtype, 120, report)
-    _print_report(report, f"dwconv rows {dtype}")
+    KC.print_report(report, f"dwconv rows {dtype}")
 
 
 @pytest.mark.parametrize("stride,vectors", [(1, 1), (2, 1), (2, 2)], ids=["s1_1vec", "s2_1vec", "s2_2vec"])
 @pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@KC.stop_after_fault
 def test_dwconv_item_loop_second_trip(dtype, stride, vectors):
     """n = 1, h = 1, w = 4096 * 256 + 300: with one vector of channels and stride 1 a row has 1048876 items on a grid of 4096 x 256, so
     300 threads take a second trip.  At stride 2 one vector of channels halves the items (524438: one trip, the case as the issue
@@ -170,12 +138,13 @@ def test_dwconv_item_loop_second_trip(dtype, stride, vectors):
     assert (items > 4096 * 256) == (stride == 1 or vectors == 2)
     report = []
     _dw_check("uniform", 1, V * vectors, 1, w, stride, ACT_NONE, dtype, 130 + stride, report)
-    _print_report(report, f"dwconv items {dtype} s{stride} x{vectors}")
+    KC.print_report(report, f"dwconv items {dtype} s{stride} x{vectors}")
 
 
 @pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@KC.stop_after_fault
 def test_dwconv_refusals_leave_the_output_untouched(dtype):
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     x, w9c, bias = Y.dw_family("uniform", 2, 8, 4, 4, dtype, 140)
     rc, yout, _ = _dw_call(x, w9c, bias, 1, ACT_SILU, dtype, k=5, pad=2)
     assert rc == UPA_EUNSUPPORTED and yout.untouched()
@@ -188,11 +157,11 @@ def test_dwconv_refusals_leave_the_output_untouched(dtype):
     wd, bd = w9c.to(DEV), bias.to(DEV)
     code = L.dtype_code(dtype)
     assert lib.upa_dwconv2d(xin.ptr, 2, 4, 4, 8, 7, wd.data_ptr(), bd.data_ptr(), yout.ptr, yout.ld, 3, 1, 1, ACT_SILU, code, st) == UPA_EINVAL
-    before = _bits(xin.buf.cpu()).clone()
+    before = KC.bits(xin.buf.cpu()).clone()
     assert lib.upa_dwconv2d(xin.ptr, 2, 4, 4, 8, xin.ld, wd.data_ptr(), bd.data_ptr(), xin.ptr + 3 * xin.ld * es, xin.ld, 3, 1, 1, ACT_SILU, code,
                             st) == UPA_EINVAL
     torch.cuda.synchronize()
-    assert yout.untouched() and torch.equal(_bits(xin.buf.cpu()), before)
+    assert yout.untouched() and torch.equal(KC.bits(xin.buf.cpu()), before)
     assert lib.upa_dwconv2d(xin.ptr, 2, 4, 4, 8, xin.ld, wd.data_ptr(), bd.data_ptr(), yout.ptr, yout.ld, 3, 1, 1, ACT_SILU, code, st) == 0
     torch.cuda.synchronize()
     yout.payload("the unvaried call")
@@ -222,7 +191,7 @@ def _psa_problem(family, h, w, heads, dtype):
 
 
 def _psa_call(qkv, pw, pb, h, w, heads, dtype, extra, off, key_dim=32, head_dim=64, ldqkv=None, code=None, y_in_x=False):
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     n, C = qkv.shape[0], heads * Y.HD
     xin = _View(n * h * w, heads * Y.CH, heads * Y.CH + extra, off, dtype, qkv.reshape(n * h * w, heads * Y.CH))
     yout = _View(n * h * w, C, C + 8, 4, dtype)
@@ -236,6 +205,7 @@ def _psa_call(qkv, pw, pb, h, w, heads, dtype, extra, off, key_dim=32, head_dim=
 
 @pytest.mark.parametrize("heads", Y.PSA_HEADS)
 @pytest.mark.parametrize("route", list(PSA_ROUTES))
+@KC.stop_after_fault
 def test_psa_every_route(route, heads):
     """Seven families x thirteen token counts around the 16-key partitions (15 / 16 / 17: partitions 1 - 3 empty or holding one key), the
     32-query tiles of the matrix-core kernel (31 / 32 / 33), the 64-key blocks (63 / 64 / 65, 127 / 129) and 200, on 1 x W and H x 1
@@ -249,12 +219,11 @@ def test_psa_every_route(route, heads):
             what = f"psa {route} {family} {h}x{w} heads {heads}"
             rc, _, yout = _psa_call(qkv, pw, pb, h, w, heads, dtype, extra, off)
             assert rc == 0, what
-            ratio = _worst(yout.payload(what), ref, bounds[kind])
-            report.append((ratio, what))
-            assert ratio <= 1.0, f"{what}: worst error / bound = {ratio:.3f}"
-    _print_report(report, f"psa {route} heads {heads}")
+            KC.check_bound(yout.payload(what), ref, bounds[kind], what, report)
+    KC.print_report(report, f"psa {route} heads {heads}")
 
 
+@KC.stop_after_fault
 def test_psa_refusals_leave_the_output_untouched():
     qkv, pw, pb = Y.psa_family("uniform", 2, 4, 4, 1, F32, 1)
     for kw, want in ((dict(key_dim=16, head_dim=32), UPA_EUNSUPPORTED), (dict(ldqkv=127), UPA_EINVAL), (dict(code=99), UPA_EUNSUPPORTED),
@@ -273,7 +242,7 @@ def test_psa_refusals_leave_the_output_untouched():
 # upa_conv_transpose2x2
 # =====================================================================================================================
 def _convt_call(x, wt, bias, dtype, cin=None, x_shift=0):
-    DEV, L, lib, st = _env()
+    DEV, L, lib, st = KC.env()
     n, cin_, h, w = x.shape
     cout = wt.shape[1]
     E, code = 16 // _es(dtype), L.dtype_code(dtype)
@@ -291,6 +260,7 @@ def _convt_call(x, wt, bias, dtype, cin=None, x_shift=0):
 
 
 @pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@KC.stop_after_fault
 def test_conv_transpose2x2_every_tile_shape(dtype):
     """cin with partial MFMA depth steps (f32 depth 4: 4 / 12 / 40; bf16 depth 32: 8 / 40 / 72), 4 cout = 16 / 80 / 160 (f32) and
     32 / 96 / 160 (bf16) columns: partial 64-column blocks of 16 and 32, a second and a third block; 2 / 126 / 128 / 130 pixels: one
@@ -306,13 +276,12 @@ def test_conv_transpose2x2_every_tile_shape(dtype):
                     rc, yout = _convt_call(x, wt, bias, dtype)
                     assert rc == 0, what
                     v, S, ref = Y.convt_ref(x, wt, bias)
-                    ratio = _worst(yout.payload(what), _rows(ref), _rows(Y.convt_bound(v, S, ref, cin, dtype)))
-                    report.append((ratio, what))
-                    assert ratio <= 1.0, f"{what}: worst error / bound = {ratio:.3f}"
-    _print_report(report, f"convt {dtype}")
+                    KC.check_bound(yout.payload(what), _rows(ref), _rows(Y.convt_bound(v, S, ref, cin, dtype)), what, report)
+    KC.print_report(report, f"convt {dtype}")
 
 
 @pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@KC.stop_after_fault
 def test_conv_transpose2x2_refusals_leave_the_output_untouched(dtype):
     E = 16 // _es(dtype)
     x, wt, bias = Y.convt_family("uniform", 2, 2 * E, 3, 3, E, dtype, 150)

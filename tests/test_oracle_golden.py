@@ -10,13 +10,10 @@ import torch
 from oracle import modules as om
 from oracle import nms as onms
 from oracle import tasks as ot
+from tests.kernel_check import unit_input
 from ultralytics_pro_amd.utils import procedural as P
 
 CONFIGS = ["yolov8n", "yolov8s", "yolov3-tiny", "yolov5-BoT3", "yolov3-rtdetr"]
-
-
-def unit_input(name, shape, lo=-1.0, hi=1.0):
-    return P.uniform(f"unit:{name}", shape, lo, hi)
 
 
 def bn_fix(m):

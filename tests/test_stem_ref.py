@@ -129,39 +129,6 @@ def _order(name, cin, k, g):
     return [[int(i)] for i in torch.randperm(cin * kk, generator=g)], False
 
 
-def _emu_stage(order, pre=None):
-    """`stage`'s stand-in: exact products of bf16 operands, f32 accumulation in `order`, f32 SiLU, one bf16 (or f32) store."""
-    g = _g(77)
-
-    def run(x, e_in, w, bias, k, stride, act, residual=None, e_res=None, out_dtype=BF16, pad=None, store=None):
-        x32, w32 = x.float(), w.float()
-        assert torch.equal(x32.to(BF16).float(), x32) and torch.equal(w32.to(BF16).float(), w32)  # products are exact in f32
-        pad = k // 2 if pad is None else pad
-        n, cin, h, wd = x32.shape
-        cout = w32.shape[0]
-        cols = F.unfold(x32, k, padding=pad, stride=stride)
-        w2 = w32.reshape(cout, -1)
-        groups, bias_first = _order(order, cin, k, g)
-        b = bias.float().view(1, cout, 1)
-        acc = b.expand(n, cout, cols.shape[2]).clone() if bias_first else torch.zeros(n, cout, cols.shape[2])
-        for grp in groups:
-            part = None
-            for i in grp:
-                pr = w2[:, i].view(1, cout, 1) * cols[:, i].unsqueeze(1)
-                part = pr if part is None else part + pr
-            acc = acc + part
-        if not bias_first:
-            acc = acc + b
-        if act == ACT_SILU:
-            acc = acc / (1.0 + torch.exp(-acc))
-        acc = acc.view(n, cout, (h + 2 * pad - k) // stride + 1, -1)
-        assert acc.dtype == torch.float32
-        if pre is not None:
-            pre.append(acc)
-        return (acc.to(BF16) if out_dtype == BF16 else acc).double(), None
-    return run
-
-
 @pytest.mark.parametrize("form", ["k3s2c16", "k6s2c16", "k3s1c32", "pool_p1", "pool_p0", "single_f32", "single_bf16"])
 def test_f32_emulation_in_four_orders_stays_inside_the_bound(form):
     g = _g(5)
@@ -192,7 +159,7 @@ def test_f32_emulation_in_four_orders_stays_inside_the_bound(form):
     with torch.no_grad():
         ref, e = run(B.stage)
         pre = {o: [] for o in ORDERS}
-        outs = {o: run(_emu_stage(o, pre[o]))[0] for o in ORDERS}
+        outs = {o: run(B.emu_stage(_order, o, pre[o]))[0] for o in ORDERS}
     for o, y in outs.items():
         d = (y - ref).abs()
         assert bool((d <= e).all()), (form, o, float((d - e).max()))

@@ -10,11 +10,8 @@ import torch.nn.functional as F
 
 from oracle import modules as om
 from tests import transformer_ref as TR
+from tests.kernel_check import unit_input
 from ultralytics_pro_amd.utils import procedural as P
-
-
-def unit_input(name, shape, lo=-1.0, hi=1.0):
-    return P.uniform(f"unit:{name}", shape, lo, hi)
 
 
 @pytest.mark.parametrize("n,L,heads,D,scale", [(2, 5, 3, 4, 1.0), (1, 65, 2, 32, 32 ** -0.5), (2, 17, 4, 16, 0.25)])

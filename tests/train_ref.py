@@ -10,6 +10,8 @@ import math
 
 import torch
 
+from tests.conv_ref import stored  # noqa: F401  (the values a buffer of `dtype` really stores, as float32)
+
 F64 = torch.float64
 ACT_NONE, ACT_SILU = 0, 1  # UPA_ACT_* of include/upa.h
 U24 = 2.0 ** -24
@@ -18,11 +20,6 @@ U24 = 2.0 ** -24
 def f32(v):
     """The float64 value of the float32 nearest to v (scalars the C ABI takes as `float`)."""
     return float(torch.tensor(v, dtype=torch.float32))
-
-
-def stored(t, dtype):
-    """The values a buffer of `dtype` really stores, as float32."""
-    return t.to(dtype).float()
 
 
 def reduce_grid(npix):
