@@ -383,6 +383,34 @@ int upa_dwconv2d(const void* x, int n, int h, int w, int c, int ldx, const float
 int upa_psa_attention(const void* qkv, int ldqkv, int n, int h, int w, int heads, int key_dim, int head_dim, float scale,
                       const float* pe_weight, const float* pe_bias, void* y, int ldy, int dtype, void* stream);
 
+/* Training forms of the two YOLO11 kernels (C2PSA in train mode; block.py:1668-1722, conv.py:411-425).  NHWC views with pitches, f32 |
+ * bf16 storage with f32 accumulation, parameters and their gradients f32 in the module's own layouts, no atomics (two calls and a graph
+ * replay are bit-identical), no allocation, no host synchronisation.
+ *
+ * v10_Attention core for training (block.py:1713-1718 without `+ self.pe(...)`, :1719): o[:, head*head_dim + j] = softmax_keys(scale q^T k) v,
+ * bit-identical to upa_psa_attention with a zero pe, and lse[(image*heads + head)*h*w + query] = log sum_keys exp(scale q.k) (f32).
+ * key_dim 32 / head_dim 64, any h*w; o must not overlap qkv. */
+int upa_psa_attention_train_fwd(const void* qkv, int ldqkv, int n, int h, int w, int heads, int key_dim, int head_dim, float scale, void* o,
+                                int ldo, float* lse, int dtype, void* stream);
+/* Its backward (the gradient block.py:1713-1718 has under autograd): dqkv in qkv's per-head layout [dq | dk | dv], every element written.
+ * P = exp(scale q.k - lse), D_i = d_o_i . o_i, dS = P (d_o . v - D); dv = P^T d_o, dq = scale dS k, dk = scale dS^T q.  P, dS, D stay f32;
+ * one rounding at the store.  dqkv must not overlap qkv, o or d_o.  ws: upa_psa_attention_bwd_workspace_bytes (0 today; may be NULL). */
+size_t upa_psa_attention_bwd_workspace_bytes(int n, int h, int w, int heads);
+int upa_psa_attention_bwd(const void* qkv, int ldqkv, const void* o, int ldo, const float* lse, const void* d_o, int ldd_o, void* dqkv,
+                          int lddqkv, int n, int h, int w, int heads, int key_dim, int head_dim, float scale, void* ws, size_t ws_bytes,
+                          int dtype, void* stream);
+/* Depthwise 3x3, stride 1, pad 1 for training (conv.py:411-425 = Conv(c, c, 3, g=c) before its BatchNorm): z = dwconv(x), no bias, no
+ * activation; w_c133 is the module's (C, 1, 3, 3) f32 weight.  c a multiple of the 16-byte vector (8 bf16 / 4 f32), pitches likewise,
+ * 16-byte aligned views (UPA_EINVAL otherwise); channel slices allowed, e.g. one head's v slice of qkv with the weight pointer moved
+ * to that head's channels (the gather of block.py:1716 costs no copy).  z must not overlap x. */
+int upa_dwconv2d_train_fwd(const void* x, int n, int h, int w, int c, int ldx, const float* w_c133, void* z, int ldz, int dtype, void* stream);
+/* Its backward: dx (+)= the correlation of dz with the flipped taps; dw_c133 (+)= sum_pixels dz * shifted x, as per-workgroup partials in
+ * ws (upa_dwconv2d_bwd_workspace_bytes(c)) added in a fixed order.  dx or dw_c133 may be NULL (then w_c133, or x and ws, may be too).
+ * dx must not overlap dz; it may be another channel slice of x's buffer. */
+size_t upa_dwconv2d_bwd_workspace_bytes(int c);
+int upa_dwconv2d_bwd(const void* x, const void* dz, int n, int h, int w, int c, int ldx, int lddz, const float* w_c133, void* dx, int lddx,
+                     int accumulate_dx, float* dw_c133, int accumulate_dw, void* ws, size_t ws_bytes, int dtype, void* stream);
+
 /* ---- RT-DETR decoder head pieces (f32 token rows) -------------------------------------------------------------------
  * nn.Linear: y[m,n] = act(x[m,k] . W[n,k]^T + bias[n]) (+ residual); W packed by upa_pack_conv_weight(k=1, UPA_F32).
  *                                                                     transformer.py:348-399, head.py:1993-2003 */

@@ -31,12 +31,20 @@ from ultralytics_pro_amd.utils import procedural as P  # noqa: E402
 
 NEW_KERNELS = ("avgpool_fwd_kernel", "avgpool_bwd_kernel", "cross_entropy_rows_kernel", "cross_entropy_mean_kernel", "linear_wgrad_kernel",
                "linear_dgrad_kernel")
+# --model yolov11n-cls: the kernels only C2PSA's training path launches (csrc/psa.hip, csrc/dwconv.hip)
+YOLO11_KERNELS = ("psa_attn_kernel", "psa_attn_mfma_kernel", "psa_bwd_dq_kernel", "psa_bwd_dkv_kernel", "dwconv3_train_kernel",
+                  "dwconv3_wgrad_partial_kernel", "dwconv3_wgrad_combine_kernel")
+
+
+def out_name(model):
+    """profiles/classify_train_bench.json for the default model (unchanged), profiles/classify_train11_bench.json for yolov11n-cls."""
+    return "classify_train_bench.json" if model == "yolov8n-cls" else f"classify_train{model.replace('yolov', '').replace('n-cls', '')}_bench.json"
 
 
 def make(a, dtype, dev):
     m = ClassificationModel(a.model + ".yaml", nc=a.nc)
     P.apply_procedural_weights(m, family=a.model)
-    tr = ClassificationTrainer(m, dtype=dtype, device=dev)
+    tr = ClassificationTrainer(m, dtype=dtype, device=dev, yolo11="11" in a.model)
     x = P.synthetic_images(a.batch, h=a.imgsz, w=a.imgsz).to(dev)
     cls = (P.uniform("bench:cls", (a.batch,), 0.0, 1.0) * a.nc).long().clamp_(0, a.nc - 1)
     return tr, x, {"cls": cls}
@@ -63,7 +71,7 @@ def kernel_shares(a):
     """Run `--steps-only bf16` under the profiler (a run of its own) and add up the kernel-stats rows."""
     out = ROOT / "profiles" / "classify_train_trace"
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", str(out), "--", sys.executable, "-m",
-           "tools.bench_classify_train", "--steps-only", "bf16", "--batch", str(a.batch), "--imgsz", str(a.imgsz), "--nc", str(a.nc),
+           "tools.bench_classify_train", "--model", a.model, "--steps-only", "bf16", "--batch", str(a.batch), "--imgsz", str(a.imgsz), "--nc", str(a.nc),
            "--steps", str(a.steps), "--warmup", str(a.warmup)]
     subprocess.run(cmd, check=True, cwd=str(ROOT), timeout=600)
     rows = []
@@ -73,13 +81,20 @@ def kernel_shares(a):
     if not rows:
         raise RuntimeError(f"no kernel_stats.csv under {out}")
     total = sum(float(r["TotalDurationNs"]) for r in rows)
-    new = {k: 0.0 for k in NEW_KERNELS}
+    names = NEW_KERNELS + (YOLO11_KERNELS if "11" in a.model else ())
+    new = {k: 0.0 for k in names}
     for r in rows:
-        for k in NEW_KERNELS:
-            if k in r["Name"]:
+        for k in names:
+            if k + "<" in r["Name"] or k + "(" in r["Name"] or r["Name"].endswith(k) or k + " " in r["Name"]:
                 new[k] += float(r["TotalDurationNs"])
-    return {"kernel_time_share_of_new_kernels": round(sum(new.values()) / total, 5),
-            "per_kernel_share": {k: round(v / total, 5) for k, v in new.items()}, "kernels_in_trace": len(rows)}
+    res = {"kernel_time_share_of_new_kernels": round(sum(new.values()) / total, 5),
+           "per_kernel_share": {k: round(v / total, 5) for k, v in new.items()}, "kernels_in_trace": len(rows)}
+    calls = sum(int(float(r.get("Calls", 0) or 0)) for r in rows)
+    ran = a.warmup + a.steps + 3  # the child's steps: one eager + compile(warm_steps=2) + warmup + steps
+    res["kernel_launches_per_step"] = round(calls / ran, 1)  # trace-wide calls / steps the child ran (the one-time packing included)
+    if "11" in a.model:
+        res["kernel_time_share_of_attention_bwd"] = round((new["psa_bwd_dq_kernel"] + new["psa_bwd_dkv_kernel"]) / total, 5)
+    return res
 
 
 def main():
@@ -121,7 +136,7 @@ def main():
             res["kernel_shares"] = f"not measured: {type(e).__name__}: {e}"
     line = json.dumps(res)
     (ROOT / "profiles").mkdir(exist_ok=True)
-    (ROOT / "profiles" / "classify_train_bench.json").write_text(line + "\n")
+    (ROOT / "profiles" / out_name(a.model)).write_text(line + "\n")
     print(line)
 
 

@@ -158,6 +158,12 @@ PROTOTYPES = {
     "upa_mhsa": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _i, _vp]),
     "upa_dwconv2d": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "upa_psa_attention": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _i, _vp]),
+    "upa_psa_attention_train_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp]),
+    "upa_psa_attention_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "upa_psa_attention_bwd": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _i, _vp]),
+    "upa_dwconv2d_train_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
+    "upa_dwconv2d_bwd_workspace_bytes": (_sz, [_i]),
+    "upa_dwconv2d_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _sz, _i, _vp]),
     "upa_linear": (_i, [_vp, C.c_long, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "upa_linear_bf16": (_i, [_vp, C.c_long, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "upa_linear_mixed": (_i, [_vp, _i, C.c_long, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp]),

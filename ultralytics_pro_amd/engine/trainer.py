@@ -12,8 +12,9 @@ explicit forward that keeps what its explicit backward needs, all of it upa_* ke
 torch is used for memory, streams, views and torch.distributed (the gradient all-reduce over RCCL).  Parameters live
 in one flat f32 buffer (grouped: biases | decayed weights | norm weights, trainer.py:917-926) so the optimizer is three
 fused launches; `model.parameters()` are views into it, the state_dict stays the reference's.
-Only the yolov8 module set is differentiable here (Conv, C2f, Bottleneck, SPPF, nn.Upsample, Concat, Detect); other
-modules raise.
+The yolov8 module set is differentiable here (Conv, C2f, Bottleneck, SPPF, nn.Upsample, Concat, Detect) and, for classification,
+YOLO11's C3k2 (C3k inside) and C2PSA (`AttentionT`: upa_psa_attention_train_fwd / _bwd, upa_dwconv2d_train_fwd / _bwd); other modules
+raise, and so does the non-legacy Detect head.
 
 `ClassificationTrainer` is the same step with another tail (`_tail_op`): `ClassifyT` = the train-mode Classify head, global average
 pool, exact-f32 linear, fused cross-entropy (v8ClassificationLoss, utils/loss.py:873-880) and their backward (include/upa.h, "image
@@ -410,6 +411,237 @@ class SPPFT(_Seq):
         self.cv1.backward(g[:, :cm], dx, accumulate)
 
 
+class C3T(_Seq):
+    """Train-mode C3 / C3k (block.py:237-262, :1510-1530): cv3(cat(m(cv1(x)), cv2(x))).  cv2 and the last inner Bottleneck write their
+    halves of one concat buffer; the gradient of the buffer is sliced the same way."""
+
+    def __init__(self, ctx, m: B.C3, name):
+        super().__init__(ctx)
+        self.cv1 = ConvT(ctx, m.cv1.conv, m.cv1.bn, m.cv1._act_code(), name + ".cv1")
+        self.cv2 = ConvT(ctx, m.cv2.conv, m.cv2.bn, m.cv2._act_code(), name + ".cv2")
+        self.cv3 = ConvT(ctx, m.cv3.conv, m.cv3.bn, m.cv3._act_code(), name + ".cv3")
+        self.c_ = self.cv1.cout
+        self.m = []
+        for i, b in enumerate(m.m):
+            if not isinstance(b, B.Bottleneck):
+                raise L.UpaError(f"{name}.m.{i}: {type(b).__name__} inside a C3 has no training path on HIP")
+            self.m.append(BottleneckT(ctx, b, f"{name}.m.{i}"))
+
+    def convs(self):
+        return [self.cv1, self.cv2, self.cv3] + [cv for b in self.m for cv in b.convs()]
+
+    def forward(self, x, out=None):
+        c, k = self.ctx, self.c_
+        n, _, h, w = x.shape
+        cat = _new(n, 2 * k, h, w, c.dtype, c.device, (id(self), "cat"))
+        t = self.cv1.forward(x, out=None if self.m else cat[:, :k])
+        for i, b in enumerate(self.m):
+            t = b.forward(t, out=cat[:, :k] if i == len(self.m) - 1 else None)
+        self.cv2.forward(x, out=cat[:, k:])
+        self.cat = cat
+        return self.cv3.forward(cat, out=out)
+
+    def backward(self, dy, dx, accumulate):
+        c, k = self.ctx, self.c_
+        n, ct, h, w = self.cat.shape
+        g = _new(n, ct, h, w, c.dtype, c.device, (id(self), "gcat"))
+        self.cv3.backward(dy, g, False)
+        gt = g[:, :k]
+        for i in reversed(range(len(self.m))):  # a Bottleneck's dx must not be its dy (the shortcut adds dy after dx is written)
+            gp = _new(n, k, h, w, c.dtype, c.device, (id(self), "gm", i))
+            self.m[i].backward(gt, gp, False)
+            gt = gp
+        self.cv1.backward(gt, dx, accumulate)
+        self.cv2.backward(g[:, k:], dx, True)
+
+
+class C3k2T(C2fT):
+    """Train-mode C3k2 (block.py:1485-1507): C2f's graph with Bottleneck(c, c, e=0.5) (c3k=False) or C3k(c, c, 2) (c3k=True) inside."""
+
+    def __init__(self, ctx, m: B.C3k2, name):
+        _Seq.__init__(self, ctx)
+        self.c = m.c
+        self.cv1 = ConvT(ctx, m.cv1.conv, m.cv1.bn, m.cv1._act_code(), name + ".cv1")
+        self.cv2 = ConvT(ctx, m.cv2.conv, m.cv2.bn, m.cv2._act_code(), name + ".cv2")
+        self.m = []
+        for i, b in enumerate(m.m):
+            if isinstance(b, B.C3):
+                self.m.append(C3T(ctx, b, f"{name}.m.{i}"))
+            elif isinstance(b, B.Bottleneck):
+                self.m.append(BottleneckT(ctx, b, f"{name}.m.{i}"))
+            else:
+                raise L.UpaError(f"{name}.m.{i}: {type(b).__name__} inside a C3k2 has no training path on HIP")
+
+
+class AttentionT(_Seq):
+    """Train-mode v10_Attention (block.py:1668-1722): proj(softmax(scale q^T k) v + pe(v)) (+ the block's residual).
+    forward:  qkv ConvT (no act) -> upa_psa_attention_train_fwd (o, lse) -> pe: upa_dwconv2d_train_fwd on each head's v slice of qkv
+              (no gather copy) -> batch statistics -> upa_bn_act_fwd with o as its residual (t = o + bn(pe)) -> proj ConvT.
+    backward: proj -> dt; dt is the gradient of BOTH o and pe's BatchNorm output (the sum node, no copy): upa_bn_act_bwd (pe's BN) ->
+              upa_psa_attention_bwd writes dqkv -> upa_dwconv2d_bwd accumulates pe's data gradient into the dv slices and pe's weight
+              gradient -> qkv ConvT.backward."""
+
+    def __init__(self, ctx, m: B.v10_Attention, name):
+        super().__init__(ctx)
+        self.heads, self.kd, self.hd, self.scale = m.num_heads, m.key_dim, m.head_dim, float(m.scale)
+        if self.kd != 32 or self.hd != 64:
+            raise L.UpaError(f"{name}: training supports key_dim 32 / head_dim 64 (every YOLO11 scale), got {self.kd} / {self.hd}")
+        pe = m.pe
+        if not (pe.conv.groups == pe.conv.in_channels == pe.conv.out_channels and pe.conv.kernel_size == (3, 3) and pe.conv.stride == (1, 1)
+                and pe.conv.padding == (1, 1) and pe.conv.dilation == (1, 1) and pe.conv.bias is None and isinstance(pe.act, nn.Identity)):
+            raise L.UpaError(f"{name}.pe: training supports a depthwise 3x3, stride 1, pad 1 conv + BatchNorm without activation, got {pe}")
+        self.qkv = ConvT(ctx, m.qkv.conv, m.qkv.bn, m.qkv._act_code(), name + ".qkv")
+        self.proj = ConvT(ctx, m.proj.conv, m.proj.bn, m.proj._act_code(), name + ".proj")
+        self.pe = pe
+        self.c = self.heads * self.hd
+        dev = ctx.device
+        self.pe_mean = torch.empty(self.c, dtype=torch.float32, device=dev)
+        self.pe_var = torch.empty(self.c, dtype=torch.float32, device=dev)
+        self.dw_ws = torch.empty(L.lib().upa_dwconv2d_bwd_workspace_bytes(self.hd), dtype=torch.uint8, device=dev)
+
+    def convs(self):
+        return [self.qkv, self.proj]  # pe's depthwise weight is read in the module's own layout: no MFMA repack
+
+    def _v(self, t, hh):
+        """Head hh's v channels of a qkv-shaped tensor."""
+        c0 = hh * (2 * self.kd + self.hd) + 2 * self.kd
+        return R.view_of(t[:, c0:c0 + self.hd])
+
+    def forward(self, x, out=None, residual=None):
+        c, lib = self.ctx, L.lib()
+        dev, st = c.device, _s(c.device)
+        n, _, h, w = x.shape
+        qkv = self.qkv.forward(x)
+        o = _new(n, self.c, h, w, c.dtype, dev, (id(self), "o"))
+        lse = R.alloc_plain((n * self.heads * h * w,), torch.float32, dev, (id(self), "lse"))
+        vq, vo = R.view_of(qkv), R.view_of(o)
+        L.check(lib.upa_psa_attention_train_fwd(vq.ptr, vq.ld, n, h, w, self.heads, self.kd, self.hd, self.scale, vo.ptr, vo.ld,
+                                                lse.data_ptr(), vq.dtype, st), "psa_attention_train_fwd")
+        z = _new(n, self.c, h, w, c.dtype, dev, (id(self), "zpe"))
+        wt = self.pe.conv.weight
+        for hh in range(self.heads):
+            vv, vz = self._v(qkv, hh), R.view_of(z[:, hh * self.hd:(hh + 1) * self.hd])
+            L.check(lib.upa_dwconv2d_train_fwd(vv.ptr, n, h, w, self.hd, vv.ld, wt.data_ptr() + hh * self.hd * 9 * 4, vz.ptr, vz.ld,
+                                               vq.dtype, st), "dwconv2d_train_fwd")
+        bn = self.pe.bn
+        vz = R.view_of(z)
+        npix = n * h * w
+        L.check(lib.upa_bn_stats(vz.ptr, npix, self.c, vz.ld, c.ws.data_ptr(), vz.dtype, st), "bn_stats[pe]")
+        L.check(lib.upa_bn_finalize(c.ws.data_ptr(), npix, self.c, ConvT._momentum(bn), self.pe_mean.data_ptr(), self.pe_var.data_ptr(),
+                                    bn.running_mean.data_ptr(), bn.running_var.data_ptr(), st), "bn_finalize[pe]")
+        t = _new(n, self.c, h, w, c.dtype, dev, (id(self), "t"))
+        vt = R.view_of(t)
+        L.check(lib.upa_bn_act_fwd(vz.ptr, npix, self.c, vz.ld, self.pe_mean.data_ptr(), self.pe_var.data_ptr(), bn.weight.data_ptr(),
+                                   bn.bias.data_ptr(), float(bn.eps), L.ACT_NONE, vt.ptr, vt.ld, vo.ptr, vo.ld, vz.dtype, st),
+                "bn_act_fwd[pe]")
+        self.qkv_y, self.o, self.lse, self.z = qkv, o, lse, z
+        return self.proj.forward(t, out=out, residual=residual)
+
+    def backward(self, dy, dx, accumulate):
+        c, lib = self.ctx, L.lib()
+        dev, st = c.device, _s(c.device)
+        n, _, h, w = self.o.shape
+        npix = n * h * w
+        dt = _new(n, self.c, h, w, c.dtype, dev, (id(self), "dt"))
+        self.proj.backward(dy, dt, False)
+        bn = self.pe.bn
+        dz = _new(n, self.c, h, w, c.dtype, dev, (id(self), "dzpe"))
+        vz, vdt, vdz = R.view_of(self.z), R.view_of(dt), R.view_of(dz)
+        L.check(lib.upa_bn_act_bwd(vz.ptr, vdt.ptr, npix, self.c, vz.ld, vdt.ld, self.pe_mean.data_ptr(), self.pe_var.data_ptr(),
+                                   bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps), L.ACT_NONE, vdz.ptr, vdz.ld,
+                                   bn.weight.grad.data_ptr(), bn.bias.grad.data_ptr(), 1, c.ws.data_ptr(), vz.dtype, st), "bn_act_bwd[pe]")
+        qkv = self.qkv_y
+        dqkv = _new(n, qkv.shape[1], h, w, c.dtype, dev, (id(self), "dqkv"))
+        vq, vo, vdq = R.view_of(qkv), R.view_of(self.o), R.view_of(dqkv)
+        L.check(lib.upa_psa_attention_bwd(vq.ptr, vq.ld, vo.ptr, vo.ld, self.lse.data_ptr(), vdt.ptr, vdt.ld, vdq.ptr, vdq.ld, n, h, w,
+                                          self.heads, self.kd, self.hd, self.scale, None, 0, vq.dtype, st), "psa_attention_bwd")
+        wt = self.pe.conv.weight
+        for hh in range(self.heads):
+            vv, vg, vdv = self._v(qkv, hh), R.view_of(dz[:, hh * self.hd:(hh + 1) * self.hd]), self._v(dqkv, hh)
+            off = hh * self.hd * 9 * 4
+            L.check(lib.upa_dwconv2d_bwd(vv.ptr, vg.ptr, n, h, w, self.hd, vv.ld, vg.ld, wt.data_ptr() + off, vdv.ptr, vdv.ld, 1,
+                                         wt.grad.data_ptr() + off, 1, self.dw_ws.data_ptr(), self.dw_ws.numel(), vq.dtype, st),
+                    "dwconv2d_bwd[pe]")
+        self.qkv.backward(dqkv, dx, accumulate)
+
+
+class PSABlockT(_Seq):
+    """Train-mode PSABlock (block.py:1724-1766): u = x + attn(x), y = u + ffn(u); both adds in the last conv's epilogue, their
+    gradients through `add_into` as in BottleneckT."""
+
+    def __init__(self, ctx, m: B.PSABlock, name):
+        super().__init__(ctx)
+        self.attn = AttentionT(ctx, m.attn, name + ".attn")
+        self.ffn = [ConvT(ctx, f.conv, f.bn, f._act_code(), f"{name}.ffn.{i}") for i, f in enumerate(m.ffn)]
+        self.add = m.add
+
+    def convs(self):
+        return self.attn.convs() + self.ffn
+
+    def forward(self, x, out=None):
+        c = self.ctx
+        n, ch, h, w = x.shape
+        u = _new(n, ch, h, w, c.dtype, c.device, (id(self), "u"))
+        self.attn.forward(x, out=u, residual=x if self.add else None)
+        return self.ffn[1].forward(self.ffn[0].forward(u), out=out, residual=u if self.add else None)
+
+    def backward(self, dy, dx, accumulate):
+        """dx may be dy's own buffer when not accumulating: dy is last read before the attention's qkv conv writes dx."""
+        c = self.ctx
+        vf = R.view_of(self.ffn[1].x)
+        df = _new(vf.n, vf.c, vf.h, vf.w, c.dtype, c.device, (id(self), "df"))
+        n, ch, h, w = dy.shape
+        du = _new(n, ch, h, w, c.dtype, c.device, (id(self), "du"))
+        self.ffn[1].backward(dy, df, False)
+        self.ffn[0].backward(df, du, False)
+        if self.add:
+            add_into(c, dy, du)
+        self.attn.backward(du, dx, accumulate)
+        if self.add:
+            add_into(c, du, dx)
+
+
+class C2PSAT(_Seq):
+    """Train-mode C2PSA (block.py:1829-1881): cv1 -> [a | b], b through the PSABlocks, cv2(cat(a, b')).  In train mode b must survive
+    (the first block's qkv conv needs it for its weight gradient), so cv2 reads a second 2c buffer: the last block writes its b half,
+    a is copied.  The gradient of that buffer is cv1's output gradient: its a half as it is, its b half rewritten by the blocks."""
+
+    def __init__(self, ctx, m: B.C2PSA, name):
+        super().__init__(ctx)
+        self.c = m.c
+        self.cv1 = ConvT(ctx, m.cv1.conv, m.cv1.bn, m.cv1._act_code(), name + ".cv1")
+        self.cv2 = ConvT(ctx, m.cv2.conv, m.cv2.bn, m.cv2._act_code(), name + ".cv2")
+        self.m = [PSABlockT(ctx, b, f"{name}.m.{i}") for i, b in enumerate(m.m)]
+        if not self.m:
+            raise L.UpaError(f"{name}: a C2PSA without PSABlocks has no training path on HIP")
+
+    def convs(self):
+        return [self.cv1, self.cv2] + [cv for b in self.m for cv in b.convs()]
+
+    def forward(self, x, out=None):
+        c, k = self.ctx, self.c
+        n, _, h, w = x.shape
+        ab = self.cv1.forward(x)
+        cat = _new(n, 2 * k, h, w, c.dtype, c.device, (id(self), "cat"))
+        copy_into(c, ab[:, :k], cat[:, :k])
+        b = ab[:, k:]
+        for i, blk in enumerate(self.m):
+            b = blk.forward(b, out=cat[:, k:] if i == len(self.m) - 1 else None)
+        return self.cv2.forward(cat, out=out)
+
+    def backward(self, dy, dx, accumulate):
+        c, k = self.ctx, self.c
+        vc = R.view_of(self.cv2.x)
+        g = _new(vc.n, 2 * k, vc.h, vc.w, c.dtype, c.device, (id(self), "gcat"))
+        self.cv2.backward(dy, g, False)
+        gcur = g[:, k:]
+        for i in reversed(range(len(self.m))):  # the first block writes b's gradient back into g's b half (PSABlockT.backward: dx may be dy)
+            gp = g[:, k:] if i == 0 else _new(vc.n, k, vc.h, vc.w, c.dtype, c.device, (id(self), "gb", i))
+            self.m[i].backward(gcur, gp, False)
+            gcur = gp
+        self.cv1.backward(g, dx, accumulate)
+
+
 class _Node:
     """One row of the model YAML inside the training graph."""
 
@@ -475,13 +707,14 @@ class DetectionTrainer:
 
     def __init__(self, model, dtype=torch.bfloat16, hyp=None, device=None, world_size=1, ema=True, wgrad_streams: int = 1,
                  amp_scaler: bool = False):
-        # YOLO11 blocks subclass / reuse C2f and Detect but have no backward here: the graph below would take a C3k2 for a C2f
-        # and the DWConv class branch for the legacy one
+        # the non-legacy Detect head (YOLO11: depthwise class branch) has no backward here: the graph below would take its DWConv
+        # class branch for the legacy one.  C3k2 / C2PSA train (ClassificationTrainer), but no YOLO11 detection model is enabled by them
         if any(isinstance(m, H.Segment) for m in model.modules()):
             raise L.UpaError("segmentation models (Segment head) have no training path on HIP: v8SegmentationLoss is out of scope")
         for m in model.modules():
-            if isinstance(m, (B.C3k2, B.C2PSA)) or (isinstance(m, H.Detect) and not m.legacy_cls):
-                raise L.UpaError(f"{type(m).__name__} (YOLO11) has no training path on HIP yet")
+            if isinstance(m, H.Detect) and not m.legacy_cls:
+                raise L.UpaError(f"{type(m).__name__} (YOLO11, non-legacy head with a depthwise class branch) has no training path on HIP "
+                                 "yet: YOLO11 detection models do not train")
         self.model = model
         self.hyp = dict(HYP, **(hyp or {}))
         self.device = torch.device(device or "cuda:0")
@@ -549,6 +782,10 @@ class DetectionTrainer:
             tail = self._tail_op(m, name)
             if tail is not None:
                 op, kind = tail
+            elif isinstance(m, B.C3k2):  # (a C2f subclass: before it)
+                op, kind = C3k2T(ctx, m, name), "c2f"
+            elif isinstance(m, B.C2PSA):
+                op, kind = C2PSAT(ctx, m, name), "c2f"
             elif isinstance(m, B.C2f):
                 op, kind = C2fT(ctx, m, name), "c2f"
             elif isinstance(m, B.SPPF):
@@ -1363,16 +1600,22 @@ class ClassificationTrainer(DetectionTrainer):
     GradScaler, EMA, `sync_ema_buffers` and `all_reduce_gradients` are DetectionTrainer's; the tail of the graph is `ClassifyT` and the
     labels are the batch's `cls` vector.  The loss is a mean over the rank's batch, so the SUM all-reduce of the per-rank gradients is
     what the reference's `loss * world_size` under DDP's average gives.  `step()` returns the (1,) unscaled loss.
-    Only the yolov8-cls module set trains (Conv, C2f, Classify); the optimizer is the SGD-Nesterov groups of the detection step."""
+    The yolov8-cls module set (Conv, C2f, Classify) trains by default; YOLO11's (C3k2, C2PSA) trains on request, `yolo11=True`: without
+    it a YOLO11 model is refused as before, so a caller that relies on that refusal keeps it.  The optimizer is the SGD-Nesterov groups
+    of the detection step."""
 
     def __init__(self, model, dtype=torch.bfloat16, hyp=None, device=None, world_size=1, ema=True, wgrad_streams: int = 1,
-                 amp_scaler: bool = False):
+                 amp_scaler: bool = False, yolo11: bool = False):
         tail = model.model[-1] if hasattr(model, "model") and len(model.model) else None
         if not isinstance(tail, H.Classify):
             raise L.UpaError(f"ClassificationTrainer needs a model that ends in a Classify head, got {type(tail).__name__}")
         for m in model.modules():
-            if isinstance(m, (B.C3k2, B.C2PSA)):
-                raise L.UpaError(f"{type(m).__name__} (YOLO11) has no training path on HIP yet")
+            if isinstance(m, (B.C3k2, B.C2PSA)) and not yolo11:
+                raise L.UpaError(f"{type(m).__name__} (YOLO11) trains on request only: ClassificationTrainer(..., yolo11=True) enables the "
+                                 "C3k2 / C2PSA training path")
+            if isinstance(m, B.v10_Attention) and (m.key_dim, m.head_dim) != (32, 64):
+                raise L.UpaError(f"v10_Attention with key_dim {m.key_dim} / head_dim {m.head_dim} has no training path on HIP (32 / 64, every "
+                                 "YOLO11 scale)")
             if isinstance(m, nn.Dropout) and m.p > 0:
                 raise L.UpaError(f"Dropout(p={m.p:g}) has no training path on HIP (the reference trains with dropout=0.0; no device RNG)")
         self.cls_d = None
