@@ -594,6 +594,24 @@ int upa_sgd_nesterov_ema_scaled(float* p, float* g, float* momentum_buf, float* 
                                 int zero_grad, const float* scaler_state, void* stream);
 int upa_grad_scaler_update(float* scaler_state, const double* grad_sumsq, float growth_factor, float backoff_factor,
                            int growth_interval, void* stream);
+/* clip_grad_norm_(max_norm) + torch.optim.Adam (decoupled = 0: g += wd p) / AdamW (decoupled = 1: p *= 1 - lr wd) + ModelEMA update
+ * over a flat parameter segment: the optimizer the reference's build_optimizer makes for optimizer=Adam / AdamW, and for auto on runs
+ * of at most 10 000 iterations (engine/trainer.py:891-950; torch/optim/adamw.py, adam.py _single_tensor_adam without amsgrad, maximize
+ * or capturable scaling).  float32 per element, in torch's order: m += (g - m)(1 - beta1); v = v beta2 + (1 - beta2) g g;
+ * denom = sqrt(v) / sqrt(1 - beta2^t) + eps; p -= lr / (1 - beta1^t) m / denom, the scalars formed in double from t = *step_dev (device
+ * int32, >= 1: upa_adam_step_advance ran first; a smaller count is taken as 1) and rounded to float32.  The clip coefficient, ema,
+ * ema_d_dev, zero_grad and scaler_state (all three pointers nullable) are upa_sgd_nesterov_ema_scaled's; a step is skipped iff
+ * scaler_state != NULL and *grad_sumsq is inf / NaN: p, exp_avg, exp_avg_sq stay bit-identical, the EMA still moves, g is still zeroed.
+ * n = 0 does nothing; n < 0, a NULL p / g / exp_avg / exp_avg_sq / grad_sumsq / step_dev or a beta outside [0, 1): UPA_EINVAL, nothing
+ * written.  No alignment rule: segments whose pointers share one offset from a 16-byte boundary move in 16-byte groups. */
+int upa_adam_ema(float* p, float* g, float* exp_avg, float* exp_avg_sq, float* ema, long n, const double* grad_sumsq, float max_norm,
+                 float lr, float beta1, float beta2, float eps, float weight_decay, int decoupled, const int* step_dev, float ema_d,
+                 const float* ema_d_dev, int zero_grad, const float* scaler_state, void* stream);
+/* The step count of upa_adam_ema (torch.optim.AdamW's state["step"], engine/trainer.py:891-950) on the device: *step_dev += 1 unless
+ * the step is a skipped one (scaler_state != NULL and *grad_sumsq inf / NaN - scaler.step() does not call optimizer.step() then).
+ * One launch per optimizer step, in front of the group launches, so that all of them - and every replay of a captured graph - read
+ * the same, new t. */
+int upa_adam_step_advance(int* step_dev, const double* grad_sumsq, const float* scaler_state, void* stream);
 int upa_ema_update(float* ema, const float* v, long n, float d, const float* d_dev, void* stream);
 /* dst view = src view converted between f32 and bf16 (head maps enter the loss as f32; c, lds, ldd positive multiples of 8). */
 int upa_cast_view(const void* src, int src_dtype, int lds, void* dst, int dst_dtype, int ldd, long npix, int c, void* stream);

@@ -214,6 +214,8 @@ PROTOTYPES = {
     "upa_detection_loss_scaled": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _f, _f, _f, _f, _vp, _vp, _vp, _sz, _vp]),
     "upa_sgd_nesterov_ema_scaled": (_i, [_vp, _vp, _vp, _vp, C.c_long, _vp, _f, _f, _f, _f, _i, _f, _vp, _i, _vp, _vp]),
     "upa_grad_scaler_update": (_i, [_vp, _vp, _f, _f, _i, _vp]),
+    "upa_adam_ema": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_long, _vp, _f, _f, _f, _f, _f, _f, _i, _vp, _f, _vp, _i, _vp, _vp]),
+    "upa_adam_step_advance": (_i, [_vp, _vp, _vp, _vp]),
     "upa_conv_transpose2x2_packed_weight_bytes": (_sz, [_i, _i, _i]),
     "upa_pack_conv_transpose2x2_weight": (_i, [_vp, _i, _i, _i, _vp]),
     "upa_conv_transpose2x2": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -1333,6 +1333,120 @@ __global__ void sgd_nesterov_ema_kernel(float* p, float* g, float* buf, float* e
   }
 }
 
+// torch.nn.utils.clip_grad_norm_ + torch.optim.Adam / AdamW (_single_tensor_adam; no amsgrad, maximize or capturable scaling) +
+// ModelEMA.update over one flat parameter segment: what the reference's build_optimizer makes of optimizer=Adam / AdamW / auto
+// (engine/trainer.py:891-950).  The step count t lives on the device (adam_step_advance_kernel moved it before this launch), so a
+// replayed graph sees a new t and a step the GradScaler skips does not count.  Thread 0 of each block forms the scalars of the step in
+// double from t, as torch forms them on the host, and hands them to the block rounded to float32.
+struct AdamScalars {
+  float coef;      // clip coefficient / loss scale
+  float decay;     // 1 - lr wd (AdamW)
+  float wd;        // weight decay added to the gradient (Adam)
+  float omb1;      // 1 - beta1
+  float beta2;
+  float omb2;      // 1 - beta2
+  float sqrt_bc2;  // sqrt(1 - beta2^t)
+  float eps;
+  float step;      // lr / (1 - beta1^t)
+  float ema_d;
+  int decoupled, skip, has_ema, zero_grad;
+};
+
+__device__ __forceinline__ void adam_elem(float& p, float& g, float& m, float& v, float& e, const AdamScalars& k) {
+  if (!k.skip) {
+    float gi = g * k.coef;
+    if (k.decoupled) p = p * k.decay;
+    else if (k.wd != 0.f) gi = gi + k.wd * p;
+    m = m + (gi - m) * k.omb1;
+    v = v * k.beta2 + (k.omb2 * gi) * gi;
+    const float denom = sqrtf(v) / k.sqrt_bc2 + k.eps;
+    p = p - (k.step * m) / denom;
+  }
+  if (k.has_ema) {
+    float en = e * k.ema_d;
+    e = en + (1.0f - k.ema_d) * p;
+  }
+  if (k.zero_grad) g = 0.f;
+}
+
+// VEC: all five pointers sit at the same offset from a 16-byte boundary, so after `head` (< 4) leading elements every lane moves one
+// 16-byte group per array and trip (40 to 64 bytes per element group in flight per lane); the < 4 trailing elements and the head go
+// one by one on the first lanes of block 0.  !VEC: pointers of mixed alignment, element by element.
+template <bool VEC>
+__global__ void adam_ema_kernel(float* p, float* g, float* m, float* v, float* ema, long n, int head, const double* sumsq, float max_norm,
+                                float lr, float beta1, float beta2, float eps, float wd, int decoupled, const int* step_dev, float ema_d,
+                                const float* ema_d_dev, int zero_grad, const float* scaler) {
+  __shared__ AdamScalars sk;
+  if (threadIdx.x == 0) {
+    const double ss = *sumsq;
+    const float inv_scale = scaler ? 1.0f / scaler[0] : 1.0f;
+    const float total = (float)sqrt(ss) * inv_scale;
+    float coef = max_norm / (total + 1e-6f);
+    if (coef > 1.0f) coef = 1.0f;
+    int t = *step_dev;
+    if (t < 1) t = 1;  // (a count that was never advanced: taken as the first step, never a division by zero)
+    const double bc1 = 1.0 - pow((double)beta1, (double)t), bc2 = 1.0 - pow((double)beta2, (double)t);
+    AdamScalars k;
+    k.coef = coef * inv_scale;
+    k.decay = (float)(1.0 - (double)lr * (double)wd);
+    k.wd = wd;
+    k.omb1 = (float)(1.0 - (double)beta1);
+    k.beta2 = beta2;
+    k.omb2 = (float)(1.0 - (double)beta2);
+    k.sqrt_bc2 = (float)sqrt(bc2);
+    k.eps = eps;
+    k.step = (float)((double)lr / bc1);
+    k.ema_d = ema_d_dev ? *ema_d_dev : ema_d;  // replayed graphs read the per-step decay from device memory
+    k.decoupled = decoupled;
+    k.skip = scaler != nullptr && !isfinite(ss);
+    k.has_ema = ema != nullptr;
+    k.zero_grad = zero_grad;
+    sk = k;
+  }
+  __syncthreads();
+  const AdamScalars k = sk;
+  const long tid = (long)blockIdx.x * 256 + threadIdx.x, nthreads = (long)gridDim.x * 256;
+  if constexpr (VEC) {
+    const long nvec = (n - head) / 4;
+    for (long u = tid; u < nvec; u += nthreads) {
+      const long i = head + 4 * u;
+      float4 pv = *reinterpret_cast<const float4*>(p + i), gv = *reinterpret_cast<const float4*>(g + i);
+      float4 mv = *reinterpret_cast<const float4*>(m + i), vv = *reinterpret_cast<const float4*>(v + i);
+      float4 ev = k.has_ema ? *reinterpret_cast<const float4*>(ema + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+      adam_elem(pv.x, gv.x, mv.x, vv.x, ev.x, k);
+      adam_elem(pv.y, gv.y, mv.y, vv.y, ev.y, k);
+      adam_elem(pv.z, gv.z, mv.z, vv.z, ev.z, k);
+      adam_elem(pv.w, gv.w, mv.w, vv.w, ev.w, k);
+      if (!k.skip) {
+        *reinterpret_cast<float4*>(p + i) = pv;
+        *reinterpret_cast<float4*>(m + i) = mv;
+        *reinterpret_cast<float4*>(v + i) = vv;
+      }
+      if (k.has_ema) *reinterpret_cast<float4*>(ema + i) = ev;
+      if (k.zero_grad) *reinterpret_cast<float4*>(g + i) = gv;
+    }
+  }
+  // element by element: everything (!VEC), or the head and the tail around the 16-byte groups
+  const long nvec4 = VEC ? (n - head) / 4 * 4 : 0;
+  const long nscalar = n - nvec4;  // VEC: head + tail < 8
+  for (long s = tid; s < nscalar; s += nthreads) {
+    const long i = (VEC && s >= head) ? s + nvec4 : s;
+    float pi = p[i], gi = g[i], mi = m[i], vi = v[i], ei = k.has_ema ? ema[i] : 0.f;
+    adam_elem(pi, gi, mi, vi, ei, k);
+    if (!k.skip) { p[i] = pi; m[i] = mi; v[i] = vi; }
+    if (k.has_ema) ema[i] = ei;
+    if (k.zero_grad) g[i] = 0.f;
+  }
+}
+
+// The optimizer's step count (torch: state["step"]) on the device: + 1 unless the GradScaler skips this step (the predicate of the
+// update kernels).  One launch per optimizer step, in front of the group launches: all of them read the same t.
+__global__ void adam_step_advance_kernel(int* step_dev, const double* sumsq, const float* scaler) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const bool skip = scaler != nullptr && !isfinite(*sumsq);
+  if (!skip) *step_dev = *step_dev + 1;
+}
+
 // GradScaler.update() (torch/amp/grad_scaler.py): state = {scale, growth tracker, found_inf of the last step, the scale before this update}.  An overflowing step
 // multiplies the scale by backoff and clears the tracker; `interval` clean steps in a row multiply it by growth.
 __global__ void grad_scaler_update_kernel(float* state, const double* sumsq, float growth, float backoff, int interval) {
@@ -1881,6 +1995,38 @@ extern "C" int upa_sgd_nesterov_ema_scaled(float* p, float* g, float* momentum_b
   UPA_CHECK_ARG(p && g && momentum_buf && grad_sumsq && scaler_state && n > 0, "sgd_scaled: bad args");
   hipLaunchKernelGGL(sgd_nesterov_ema_kernel, dim3(grid_for(n, 1024, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, momentum_buf,
                      ema, n, grad_sumsq, max_norm, lr, momentum, weight_decay, first_step, ema_d, ema_d_dev, zero_grad, scaler_state);
+  UPA_LAUNCH_CHECK();
+  return UPA_OK;
+}
+
+// clip_grad_norm_ + Adam (decoupled = 0) / AdamW (decoupled = 1) + EMA over a flat segment; scaler_state as in the SGD entry (nullable).
+// Memory-bound: 10 floats move per parameter (8 without an EMA), so the grid is the SGD launch's, in 16-byte groups where the pointers allow.
+extern "C" int upa_adam_ema(float* p, float* g, float* exp_avg, float* exp_avg_sq, float* ema, long n, const double* grad_sumsq,
+                            float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int decoupled,
+                            const int* step_dev, float ema_d, const float* ema_d_dev, int zero_grad, const float* scaler_state,
+                            void* stream) {
+  UPA_CHECK_ARG(p && g && exp_avg && exp_avg_sq && grad_sumsq && step_dev && n >= 0, "adam: bad args");
+  UPA_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "adam: beta1 = %g, beta2 = %g outside [0, 1)", (double)beta1,
+                (double)beta2);
+  if (n == 0) return UPA_OK;
+  const uintptr_t a = (uintptr_t)p & 15;
+  const bool vec = n >= 8 && (a & 3) == 0 && ((uintptr_t)g & 15) == a && ((uintptr_t)exp_avg & 15) == a &&
+                   ((uintptr_t)exp_avg_sq & 15) == a && (!ema || ((uintptr_t)ema & 15) == a);
+  const int head = vec ? (int)(((16 - a) & 15) / 4) : 0;
+  const dim3 grid(grid_for(vec ? n / 4 + 8 : n, 1024, 2048));
+  if (vec)
+    hipLaunchKernelGGL(adam_ema_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_avg_sq, ema, n, head, grad_sumsq,
+                       max_norm, lr, beta1, beta2, eps, weight_decay, decoupled, step_dev, ema_d, ema_d_dev, zero_grad, scaler_state);
+  else
+    hipLaunchKernelGGL(adam_ema_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_avg_sq, ema, n, head, grad_sumsq,
+                       max_norm, lr, beta1, beta2, eps, weight_decay, decoupled, step_dev, ema_d, ema_d_dev, zero_grad, scaler_state);
+  UPA_LAUNCH_CHECK();
+  return UPA_OK;
+}
+
+extern "C" int upa_adam_step_advance(int* step_dev, const double* grad_sumsq, const float* scaler_state, void* stream) {
+  UPA_CHECK_ARG(step_dev && grad_sumsq, "adam_step_advance: bad args");
+  hipLaunchKernelGGL(adam_step_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step_dev, grad_sumsq, scaler_state);
   UPA_LAUNCH_CHECK();
   return UPA_OK;
 }

@@ -12,6 +12,9 @@ explicit forward that keeps what its explicit backward needs, all of it upa_* ke
 torch is used for memory, streams, views and torch.distributed (the gradient all-reduce over RCCL).  Parameters live
 in one flat f32 buffer (grouped: biases | decayed weights | norm weights, trainer.py:917-926) so the optimizer is three
 fused launches; `model.parameters()` are views into it, the state_dict stays the reference's.
+`optimizer=` follows the reference's build_optimizer (trainer.py:891-950): SGD-Nesterov by default, Adam / AdamW as the same three
+launches of upa_adam_ema behind one upa_adam_step_advance (second-moment buffer `V`, step count on the device), "auto" resolved from
+`iterations` and the head's class count (`resolve_optimizer`).
 The yolov8 module set is differentiable here (Conv, C2f, Bottleneck, SPPF, nn.Upsample, Concat, Detect) and, for classification,
 YOLO11's C3k2 (C3k inside) and C2PSA (`AttentionT`: upa_psa_attention_train_fwd / _bwd, upa_dwconv2d_train_fwd / _bwd); other modules
 raise, and so does the non-legacy Detect head.
@@ -39,7 +42,8 @@ from ..nn.modules import resample as RS
 from . import runtime as R
 
 HYP = dict(lr=0.01, momentum=0.9, weight_decay=5e-4, max_norm=10.0, ema_decay=0.9999, ema_tau=2000.0,
-           box=7.5, cls=0.5, dfl=1.5)
+           box=7.5, cls=0.5, dfl=1.5, beta2=0.999, adam_eps=1e-8)  # (beta2, adam_eps: Adam / AdamW only; `momentum` is their beta1)
+OPTIMIZERS = ("SGD", "Adam", "AdamW", "auto")  # of the reference's build_optimizer names (trainer.py:930); the others are refused
 # warm-up / accumulation schedule of the reference's training loop (engine/trainer.py:337-338, 392-413, 245; cfg/default.yaml)
 SCHED = dict(nbs=64, warmup_epochs=3.0, warmup_momentum=0.8, warmup_bias_lr=0.1, lrf=0.01, epochs=100)
 MAX_GT = 64        # initial gt-row capacity per image; grows with the data (the loss kernels take it at run time)
@@ -702,11 +706,44 @@ class GradScaler:
         self.state.copy_(torch.tensor([float(sd["scale"]), float(sd["_growth_tracker"]), 0.0, 0.0]))
 
 
+def resolve_optimizer(name, iterations, nc):
+    """`build_optimizer`'s choice (engine/trainer.py:891-950) as (name, hyp overrides, auto?): the name is case-insensitive; "auto" takes
+    SGD(lr 0.01, momentum 0.9) for more than 10 000 iterations and AdamW(lr round(0.002 * 5 / (4 + nc), 6), beta1 0.9) otherwise,
+    whatever `hyp` says, and forces warmup_bias_lr = 0 (the third element: `set_schedule` reads it)."""
+    known = {x.lower(): x for x in OPTIMIZERS}
+    got = known.get(str(name).lower())
+    if got is None:
+        raise L.UpaError(f"optimizer={name!r} has no fused step on HIP: supported are {', '.join(OPTIMIZERS)} (Adamax, NAdam, RAdam and "
+                         "RMSProp of the reference's list are not built)")
+    if got != "auto":
+        return got, {}, False
+    if iterations is None:
+        raise L.UpaError("optimizer='auto' needs iterations= (the number of optimizer iterations of the run: auto picks SGD above 10000, "
+                         "AdamW otherwise); or name one of SGD, Adam, AdamW")
+    if iterations > 10000:
+        return "SGD", dict(lr=0.01, momentum=0.9), True
+    return "AdamW", dict(lr=round(0.002 * 5 / (4 + nc), 6), momentum=0.9), True
+
+
+def _head_nc(model) -> int:
+    """Number of classes of the model's head (the reference's `self.data["nc"]`)."""
+    tail = model.model[-1] if hasattr(model, "model") and len(model.model) else None
+    if isinstance(tail, H.Classify):
+        return int(tail.linear.out_features)
+    if tail is not None and hasattr(tail, "nc"):
+        return int(tail.nc)
+    raise L.UpaError(f"optimizer='auto' reads the number of classes from the model's head, got {type(tail).__name__}")
+
+
 class DetectionTrainer:
-    """One-process-per-GPU trainer for a DetectionModel (reference: engine/trainer.py BaseTrainer._do_train inner loop)."""
+    """One-process-per-GPU trainer for a DetectionModel (reference: engine/trainer.py BaseTrainer._do_train inner loop).
+    `optimizer`: "SGD" (default: SGD-Nesterov), "Adam", "AdamW" (lr and beta1 = `momentum` from `hyp`, plus `beta2`, `adam_eps`) or
+    "auto" with `iterations` (`resolve_optimizer`); `optimizer_name` is the resolved one."""
 
     def __init__(self, model, dtype=torch.bfloat16, hyp=None, device=None, world_size=1, ema=True, wgrad_streams: int = 1,
-                 amp_scaler: bool = False):
+                 amp_scaler: bool = False, optimizer: str = "SGD", iterations=None):
+        self.optimizer_name, opt_hyp, self._auto_optimizer = resolve_optimizer(
+            optimizer, iterations, _head_nc(model) if str(optimizer).lower() == "auto" and iterations is not None else 0)
         # the non-legacy Detect head (YOLO11: depthwise class branch) has no backward here: the graph below would take its DWConv
         # class branch for the legacy one.  C3k2 / C2PSA train (ClassificationTrainer), but no YOLO11 detection model is enabled by them
         if any(isinstance(m, H.Segment) for m in model.modules()):
@@ -717,6 +754,8 @@ class DetectionTrainer:
                                  "yet: YOLO11 detection models do not train")
         self.model = model
         self.hyp = dict(HYP, **(hyp or {}))
+        self.hyp.update(opt_hyp)  # auto ignores lr0 and momentum of the arguments, as the reference does
+        self.adam = self.optimizer_name in ("Adam", "AdamW")
         self.device = torch.device(device or "cuda:0")
         self.dtype = dtype
         self.world_size = world_size
@@ -748,7 +787,11 @@ class DetectionTrainer:
         dev = self.device
         self.P = torch.empty(total, dtype=torch.float32, device=dev)
         self.G = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.M = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.M = torch.zeros(total, dtype=torch.float32, device=dev)  # SGD: momentum buffer; Adam / AdamW: exp_avg
+        self.V = self.opt_step_dev = None
+        if self.adam:  # exp_avg_sq and the step count (torch's state["step"]), device-side: see upa_adam_step_advance
+            self.V = torch.zeros(total, dtype=torch.float32, device=dev)
+            self.opt_step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         for _name, off, n, p in meta:
             self.P[off:off + n].copy_(p.detach().reshape(-1))  # plumbing: one-time gather of the initial weights
             p.data = self.P[off:off + n].view(p.shape)
@@ -1067,6 +1110,8 @@ class DetectionTrainer:
         grows from 1 to nbs / batch; afterwards the optimizer steps every max(round(nbs / batch), 1) iterations with
         weight_decay * batch * accumulate / nbs.  `global_batch` = the reference's `batch_size` (all ranks together)."""
         sc = dict(SCHED, **overrides)
+        if self._auto_optimizer:
+            sc["warmup_bias_lr"] = 0.0  # trainer.py:917, whichever optimizer auto resolved to
         sc["nb"] = int(batches_per_epoch)
         sc["global_batch"] = global_batch
         self.schedule = sc
@@ -1089,7 +1134,9 @@ class DetectionTrainer:
             xi = [0, nw]
             acc = max(1, int(np.interp(ni, xi, [1, sc["nbs"] / gb]).round()))
             lrs = [float(np.interp(ni, xi, [sc["warmup_bias_lr"] if j == 0 else 0.0, lr])) for j in range(3)]
-            return acc, lrs, float(np.interp(ni, xi, [sc["warmup_momentum"], h["momentum"]])), wd
+            # Adam's param groups have no "momentum" key, so the reference's warm-up leaves beta1 alone (trainer.py:411)
+            mom = h["momentum"] if self.adam else float(np.interp(ni, xi, [sc["warmup_momentum"], h["momentum"]]))
+            return acc, lrs, mom, wd
         return acc0, [lr, lr, lr], h["momentum"], wd
 
     def optimizer_step(self, lrs=None, momentum=None, weight_decay=None):
@@ -1103,12 +1150,21 @@ class DetectionTrainer:
             dp = self.ema_d_dev.data_ptr()
         lrs = [h["lr"]] * 3 if lrs is None else lrs
         mom = h["momentum"] if momentum is None else momentum
+        if self.adam:  # the count moves first (not on a step the scaler skips): the three launches read the same t
+            L.check(lib.upa_adam_step_advance(self.opt_step_dev.data_ptr(), self.sumsq.data_ptr(), self.scaler.ptr(), st), "adam_step_advance")
         for gi, (start, n, wd) in enumerate(self.groups):
             if n == 0:
                 continue
             if wd and weight_decay is not None:
                 wd = weight_decay
             o = 4 * start
+            if self.adam:
+                L.check(lib.upa_adam_ema(self.P.data_ptr() + o, self.G.data_ptr() + o, self.M.data_ptr() + o, self.V.data_ptr() + o,
+                                         (self.E.data_ptr() + o) if self.E is not None else None, n, self.sumsq.data_ptr(),
+                                         h["max_norm"], lrs[gi], mom, h["beta2"], h["adam_eps"], wd,
+                                         int(self.optimizer_name == "AdamW"), self.opt_step_dev.data_ptr(), d, dp, 1, self.scaler.ptr(),
+                                         st), "adam")
+                continue
             if self.scaler.enabled:  # unscale_ + clip + scaler.step in the same kernel (the momentum buffers start at zero, so the
                 # first-step form b = g equals momentum * 0 + g: a skipped first step needs no special case)
                 L.check(lib.upa_sgd_nesterov_ema_scaled(self.P.data_ptr() + o, self.G.data_ptr() + o, self.M.data_ptr() + o,
@@ -1128,6 +1184,19 @@ class DetectionTrainer:
         # parameters and BN buffers were just rewritten through raw pointers: no `_version` moved, so every packed-weight
         # cache of the inference path (Conv / Detect / C2f) is told explicitly
         CV.bump_weights_generation()
+
+    @property
+    def opt_step(self):
+        """Adam / AdamW: the optimizer's step count (torch's state["step"]; skipped AMP steps do not count), read from the device
+        (a host synchronisation: logging / tests / checkpoints only).  None under SGD, which keeps none."""
+        return None if self.opt_step_dev is None else int(self.opt_step_dev.item())
+
+    def optimizer_state(self):
+        """Views of the flat optimizer state in parameter-buffer order: SGD {"momentum_buffer"}; Adam / AdamW {"exp_avg", "exp_avg_sq",
+        "step"} - what a checkpoint has to keep next to the parameters and the EMA."""
+        if not self.adam:
+            return {"momentum_buffer": self.M}
+        return {"exp_avg": self.M, "exp_avg_sq": self.V, "step": self.opt_step}
 
     def step(self, img, labels):
         """One training step. After `compile()` the step is replayed as hipGraphs (one graph on a single GPU; forward +
@@ -1601,11 +1670,11 @@ class ClassificationTrainer(DetectionTrainer):
     labels are the batch's `cls` vector.  The loss is a mean over the rank's batch, so the SUM all-reduce of the per-rank gradients is
     what the reference's `loss * world_size` under DDP's average gives.  `step()` returns the (1,) unscaled loss.
     The yolov8-cls module set (Conv, C2f, Classify) trains by default; YOLO11's (C3k2, C2PSA) trains on request, `yolo11=True`: without
-    it a YOLO11 model is refused as before, so a caller that relies on that refusal keeps it.  The optimizer is the SGD-Nesterov groups
-    of the detection step."""
+    it a YOLO11 model is refused as before, so a caller that relies on that refusal keeps it.  The optimizer is the detection step's:
+    SGD-Nesterov by default, Adam / AdamW / auto on request (`optimizer=`, `iterations=`)."""
 
     def __init__(self, model, dtype=torch.bfloat16, hyp=None, device=None, world_size=1, ema=True, wgrad_streams: int = 1,
-                 amp_scaler: bool = False, yolo11: bool = False):
+                 amp_scaler: bool = False, yolo11: bool = False, optimizer: str = "SGD", iterations=None):
         tail = model.model[-1] if hasattr(model, "model") and len(model.model) else None
         if not isinstance(tail, H.Classify):
             raise L.UpaError(f"ClassificationTrainer needs a model that ends in a Classify head, got {type(tail).__name__}")
@@ -1620,7 +1689,7 @@ class ClassificationTrainer(DetectionTrainer):
                 raise L.UpaError(f"Dropout(p={m.p:g}) has no training path on HIP (the reference trains with dropout=0.0; no device RNG)")
         self.cls_d = None
         super().__init__(model, dtype=dtype, hyp=hyp, device=device, world_size=world_size, ema=ema, wgrad_streams=wgrad_streams,
-                         amp_scaler=amp_scaler)
+                         amp_scaler=amp_scaler, optimizer=optimizer, iterations=iterations)
 
     def _tail_op(self, m, name):
         if isinstance(m, H.Classify):
