@@ -369,6 +369,24 @@ int upa_nms_batched(const float* pred, int b, int nc, int a, float conf_thres, f
  * scale = 1 for MHSA (block.py:6036-6091, unscaled), 1/sqrt(d) for nn.MultiheadAttention (transformer.py:670-673). */
 int upa_mhsa(const void* q, const void* k, const void* v, int ldqkv, int n, int hw, int heads, int d, float scale,
              const void* residual, int ldr, void* y, int ldy, int dtype, void* stream);
+/* MHSA for training (BottleneckTransformer in train mode; block.py:6036-6062, :6090-6091).  upa_mhsa_train_fwd = upa_mhsa + the row
+ * statistic lse[(image*heads + head)*hw + query] = log sum_keys exp(scale q.k) (f32, natural log, from the online softmax's running max
+ * and sum); y (residual included) is bit-identical to upa_mhsa's on the same arguments, and the same d (4, 8, 16, 32, 64) and hw are
+ * supported (UPA_EUNSUPPORTED otherwise).  y must not overlap q, k, v or lse (UPA_EINVAL). */
+int upa_mhsa_train_fwd(const void* q, const void* k, const void* v, int ldqkv, int n, int hw, int heads, int d, float scale,
+                       const void* residual, int ldr, void* y, int ldy, float* lse, int dtype, void* stream);
+/* Its backward: dq, dk, dv row views (one pitch lddqkv, heads*d channels each, every element written) from q, k, v (one pitch ldqkv),
+ * the forward's lse and d_o = the gradient of y.  P = exp(scale q.k - lse), dP = d_o . v, D_i = sum_j P_ij dP_ij, dS = P (dP - D);
+ * dv = P^T d_o, dq = scale dS k, dk = scale dS^T q.  D is recomputed from P inside the pass and NOT taken as d_o . (y - residual): y holds
+ * the residual and one storage rounding of the sum, so neither y nor the residual is an argument.  The gradient of the residual branch is
+ * d_o itself and is the caller's to add.  Any hw (keys and queries are streamed); f32 | bf16 storage, every sum an f32 fmaf chain in an
+ * order fixed by the shapes, no atomics (two calls and a graph replay are bit-identical), one rounding at the store.  Views need only
+ * element alignment (16-byte aligned views with 16-byte pitches are read with vector loads).  ws: upa_mhsa_bwd_workspace_bytes bytes
+ * (D, one f32 per image, head and query), 4-byte aligned.  A gradient view that overlaps q, k, v, d_o, lse or ws: UPA_EINVAL; a d
+ * outside the list above: UPA_EUNSUPPORTED; nothing is launched in either case. */
+size_t upa_mhsa_bwd_workspace_bytes(int n, int hw, int heads);
+int upa_mhsa_bwd(const void* q, const void* k, const void* v, int ldqkv, const float* lse, const void* d_o, int ldd_o, void* dq, void* dk,
+                 void* dv, int lddqkv, int n, int hw, int heads, int d, float scale, void* ws, size_t ws_bytes, int dtype, void* stream);
 
 /* ---- YOLO11 (C2PSA, non-legacy Detect) -----------------------------------------------------------------------------
  * Depthwise k x k conv (DWConv, groups = C; nn/modules/conv.py:411-425): y = act(dwconv(x) + bias) on NHWC views (any C, channel
@@ -543,7 +561,10 @@ int upa_conv_bn_act_bwd(const void* x, int n, int h, int w, int cin, int ldx, co
 int upa_channel_sum(const void* z, long npix, int c, int ldz, float* out, int accumulate, double* ws, int dtype, void* stream);
 /* dW[co][ci][kh][kw] (OIHW f32, optionally accumulated) = sum_{n,oy,ox} dz[n,oy,ox,co] * x[n,oy*s+kh-p,ox*s+kw-p,ci]
  * on exact-f32 MFMA; k in {1, 3}.  Workgroups store partial blocks into the caller's workspace and a second kernel sums
- * them in a fixed order (deterministic, and no contended atomics). */
+ * them in a fixed order (deterministic, and no contended atomics).
+ * k = 6 is built for the yolov5 stem only - cin 3 (x a view of pitch ldx >= 3, e.g. the 3 channels padded to one 16-byte group),
+ * cout >= 16, stride 2, pad 2 - as f32 fmaf sums on the vector ALU with the same two-stage fixed-order reduction; every other k = 6
+ * shape is UPA_EUNSUPPORTED and upa_conv2d_wgrad_workspace_bytes returns 0 for it. */
 size_t upa_conv2d_wgrad_workspace_bytes(int cin, int cout, int k);
 int upa_conv2d_wgrad(const void* x, int n, int h, int w, int cin, int ldx, const void* dz, int cout, int lddz, float* dw_oihw,
                      int k, int stride, int pad, int accumulate, int dtype, void* workspace, size_t workspace_bytes, void* stream);

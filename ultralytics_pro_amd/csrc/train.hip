@@ -974,6 +974,117 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_kernel(const float* partial
   }
 }
 
+// ---- 6x6 stride-2 pad-2 stem (yolov5's Conv(3, c, 6, 2, 2)): 3 input channels, 108 weights per output channel.  Nothing here is MFMA
+// shaped (K = 3 channels per tap), and the layer gets no data gradient, so this is the whole backward of the stem's convolution.
+// Workgroup = 16 output channels x a persistent walk over 8 x 16 output-pixel tiles; per tile the dz block ([128][16] f32) and the x halo
+// ([20][36][3] f32) are staged in LDS.  Wave `part` takes pixels [32 part, 32 part + 32) of every tile; lane = (cg = lane & 3: output
+// channels 4 cg .. 4 cg + 3, tg = lane >> 2: weights 7 tg .. 7 tg + 6 of the channel's 108 in [kh][kw][ci] order), so a lane keeps 28 f32
+// sums in registers and reads one 16-byte dz group + 7 halo words per pixel for 28 fmaf.  The four waves' sums are added in partition
+// order through LDS, the workgroup's 16 x 108 block goes to the workspace and wgrad_k6_reduce_kernel adds the workgroups' blocks in index
+// order: every sum has an order fixed by the shapes (deterministic, no atomics).
+constexpr int K6_TH = 8, K6_TW = 16, K6_IH = (K6_TH - 1) * 2 + 6, K6_IW = (K6_TW - 1) * 2 + 6, K6_W = 108, K6_CO = 16, K6_TPL = 7;
+constexpr int K6_WGS = 512;  // workgroups (pixel slices) per block of output channels at most
+
+template <typename T>
+__global__ __launch_bounds__(256) void wgrad_k6s2_kernel(const WgradParams p) {
+  static_assert(3 * 28 * 64 >= K6_TH * K6_TW * K6_CO, "the merge block holds the dz tile");
+  __shared__ __attribute__((aligned(16))) float zt[3 * 28 * 64];  // dz tile [128][16] (8 KiB), then the partition merge [3][28][64] (21 KiB)
+  __shared__ float xt[K6_IH * K6_IW * 3];                         // 8.4 KiB
+  const int tid = threadIdx.x, lane = tid & 63, part = tid >> 6;
+  const int cg = lane & 3, tg = lane >> 2;
+  const int co0 = blockIdx.y * K6_CO;
+  int off[K6_TPL];
+#pragma unroll
+  for (int t = 0; t < K6_TPL; ++t) {
+    const int j = min(tg * K6_TPL + t, K6_W - 1);  // (weights past 108 repeat the last one and are not stored)
+    const int tap = j / 3, ci = j - tap * 3;
+    const int kh = tap / 6, kw = tap - kh * 6;
+    off[t] = (kh * K6_IW + kw) * 3 + ci;
+  }
+  float acc[K6_TPL][4];
+#pragma unroll
+  for (int t = 0; t < K6_TPL; ++t)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[t][c] = 0.f;
+  const int tilesPerImg = p.tilesX * p.tilesY;
+  for (int tile = blockIdx.x; tile < p.numTiles; tile += gridDim.x) {
+    const int n = tile / tilesPerImg;
+    const int t2 = tile - n * tilesPerImg;
+    const int tyi = t2 / p.tilesX, txi = t2 - tyi * p.tilesX;
+    const int oy0 = tyi * K6_TH, ox0 = txi * K6_TW;
+    const int iy0 = oy0 * 2 - 2, ix0 = ox0 * 2 - 2;
+    __syncthreads();  // the previous tile has been consumed
+    for (int i = tid; i < K6_TH * K6_TW * K6_CO; i += 256) {
+      const int px = i / K6_CO, c = i - px * K6_CO;
+      const int oy = oy0 + px / K6_TW, ox = ox0 + px % K6_TW, co = co0 + c;
+      float val = 0.f;
+      if (oy < p.OH && ox < p.OW && co < p.Cout)
+        val = ElemTraits<T>::load(reinterpret_cast<const T*>(p.dz) + (((size_t)n * p.OH + oy) * p.OW + ox) * p.lddz + co);
+      zt[i] = val;
+    }
+    for (int i = tid; i < K6_IH * K6_IW * 3; i += 256) {
+      const int px = i / 3, ci = i - px * 3;
+      const int iy = iy0 + px / K6_IW, ix = ix0 + px % K6_IW;
+      float val = 0.f;
+      if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W)
+        val = ElemTraits<T>::load(reinterpret_cast<const T*>(p.x) + (((size_t)n * p.H + iy) * p.W + ix) * p.ldx + ci);
+      xt[i] = val;
+    }
+    __syncthreads();
+    for (int q = 0; q < 32; ++q) {
+      const int px = part * 32 + q;
+      const int ty = px / K6_TW, tx = px - ty * K6_TW;
+      const f32x4 z = *reinterpret_cast<const f32x4*>(zt + px * K6_CO + cg * 4);
+      const float* xb = xt + (ty * 2 * K6_IW + tx * 2) * 3;
+#pragma unroll
+      for (int t = 0; t < K6_TPL; ++t) {
+        const float xv = xb[off[t]];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[t][c] = fmaf(z[c], xv, acc[t][c]);
+      }
+    }
+  }
+  __syncthreads();  // zt is reused for the merge
+  float* merge = zt;  // [3][28][64]
+  if (part > 0) {
+#pragma unroll
+    for (int t = 0; t < K6_TPL; ++t)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) merge[((part - 1) * 28 + t * 4 + c) * 64 + lane] = acc[t][c];
+  }
+  __syncthreads();
+  if (part == 0) {
+    float* blk = p.partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (K6_CO * K6_W);
+#pragma unroll
+    for (int t = 0; t < K6_TPL; ++t) {
+      const int j = tg * K6_TPL + t;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        float a = acc[t][c];
+#pragma unroll
+        for (int q_ = 1; q_ < 4; ++q_) a += merge[((q_ - 1) * 28 + t * 4 + c) * 64 + lane];
+        if (j < K6_W) blk[(cg * 4 + c) * K6_W + j] = a;
+      }
+    }
+  }
+}
+
+// dW[co][ci][kh][kw] (+)= the workgroups' [16][kh][kw][ci] blocks, added in workgroup order
+__global__ __launch_bounds__(256) void wgrad_k6_reduce_kernel(const float* partial, int wgs, float* dw, int Cout, int accumulate) {
+  const int i = blockIdx.x * 256 + threadIdx.x;  // (co block, co in block, weight)
+  const int per = K6_CO * K6_W;
+  const int cb = i / per, r = i - cb * per;
+  const int col = r / K6_W, j = r - col * K6_W;
+  const int co = cb * K6_CO + col;
+  if (co >= Cout) return;
+  const float* src = partial + (size_t)cb * wgs * per + r;
+  float tot = 0.f;
+  for (int w = 0; w < wgs; ++w) tot += src[(size_t)w * per];
+  const int tap = j / 3, ci = j - tap * 3;
+  float* d = dw + ((size_t)co * 3 + ci) * 36 + tap;
+  *d = accumulate ? *d + tot : tot;
+}
+
 static void launch_wgrad_reduce(const float* partial, int wgs, int bco, int bci, int BCO, int BCI, int kk2, float* dw, int Cout, int Cin,
                                 int accumulate, hipStream_t s) {
   const int EG = kk2 * BCI / 4;
@@ -1846,7 +1957,31 @@ static int launch_wgrad_bf16_k3(WgradParams& p, int accumulate, void* ws, size_t
                      : launch_wgrad_bf16_k3_t<64>(p, accumulate, ws, ws_bytes, s);
 }
 
+static size_t wgrad_k6_bytes(int cout) { return (size_t)cdiv(cout, K6_CO) * K6_WGS * K6_CO * K6_W * sizeof(float); }
+
+template <typename T>
+static int launch_wgrad_k6s2(WgradParams& p, int accumulate, void* ws, size_t ws_bytes, hipStream_t s) {
+  p.TH = K6_TH; p.TW = K6_TW;
+  p.tilesX = cdiv(p.OW, K6_TW); p.tilesY = cdiv(p.OH, K6_TH);
+  const long tiles = (long)p.tilesX * p.tilesY * p.N;
+  UPA_CHECK_ARG(tiles <= 0x7fffffffl, "wgrad: too many tiles");
+  p.numTiles = (int)tiles;
+  const int cb = cdiv(p.Cout, K6_CO);
+  int wgs = K6_WGS;
+  if (wgs > p.numTiles) wgs = p.numTiles;
+  const size_t need = (size_t)cb * wgs * K6_CO * K6_W * sizeof(float);
+  UPA_CHECK_ARG(ws && ws_bytes >= need, "wgrad: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+  p.partial = (float*)ws;
+  hipLaunchKernelGGL(wgrad_k6s2_kernel<T>, dim3((unsigned)wgs, (unsigned)cb), dim3(256), 0, s, p);
+  UPA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(wgrad_k6_reduce_kernel, dim3((unsigned)cdiv(cb * K6_CO * K6_W, 256)), dim3(256), 0, s, (const float*)p.partial, wgs, p.dw,
+                     p.Cout, accumulate);
+  UPA_LAUNCH_CHECK();
+  return UPA_OK;
+}
+
 extern "C" size_t upa_conv2d_wgrad_workspace_bytes(int cin, int cout, int k) {
+  if (k == 6) return cin == 3 && cout >= 16 ? wgrad_k6_bytes(cout) : 0;  // the stem form is the only k = 6 kernel
   // upper bound over the kernels the dispatcher may pick (f32 32/64/128 blocks with <= 256 workgroups, bf16 3x3 64-blocks
   // with <= 512, bf16 pointwise 128-blocks with <= 256)
   size_t best = 0;
@@ -1876,6 +2011,14 @@ extern "C" int upa_conv2d_wgrad(const void* x, int n, int h, int w, int cin, int
   p.N = n; p.H = h; p.W = w; p.Cin = cin; p.ldx = ldx; p.Cout = cout; p.lddz = lddz;
   p.OH = (h + 2 * pad - k) / stride + 1; p.OW = (w + 2 * pad - k) / stride + 1;
   p.KS = k; p.stride = stride; p.pad = pad;
+  if (k == 6) {  // the 3-channel 6x6 stride-2 pad-2 stem only (wgrad_k6s2_kernel); ldx is the padded input's pitch
+    if (!(cin == 3 && cout >= 16 && stride == 2 && pad == 2 && ldx >= 3 && h + 4 >= 6 && w + 4 >= 6)) {
+      upa_set_error("wgrad: kernel size 6 is built for the stem form only (cin 3, cout >= 16, stride 2, pad 2)");
+      return UPA_EUNSUPPORTED;
+    }
+    return dtype == UPA_BF16 ? launch_wgrad_k6s2<bf16_t>(p, accumulate, workspace, workspace_bytes, s)
+                             : launch_wgrad_k6s2<float>(p, accumulate, workspace, workspace_bytes, s);
+  }
   const bool small = wgrad_small(cin, cout);
   constexpr bool no_bf16_mfma = false;
   if (dtype == UPA_BF16 && k == 3 && cout >= 16 && !no_bf16_mfma && (cin % 8 == 0 || (cin < 8 && ldx >= 8)))

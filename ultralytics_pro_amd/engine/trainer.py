@@ -15,9 +15,10 @@ fused launches; `model.parameters()` are views into it, the state_dict stays the
 `optimizer=` follows the reference's build_optimizer (trainer.py:891-950): SGD-Nesterov by default, Adam / AdamW as the same three
 launches of upa_adam_ema behind one upa_adam_step_advance (second-moment buffer `V`, step count on the device), "auto" resolved from
 `iterations` and the head's class count (`resolve_optimizer`).
-The yolov8 module set is differentiable here (Conv, C2f, Bottleneck, SPPF, nn.Upsample, Concat, Detect) and, for classification,
-YOLO11's C3k2 (C3k inside) and C2PSA (`AttentionT`: upa_psa_attention_train_fwd / _bwd, upa_dwconv2d_train_fwd / _bwd); other modules
-raise, and so does the non-legacy Detect head.
+The yolov8 module set is differentiable here (Conv, C2f, Bottleneck, SPPF, nn.Upsample, Concat, Detect), the yolov5-BoT3 set (the 6x6
+stride-2 stem, bare C3, BoT3 = `MHSAT`: upa_mhsa_train_fwd / upa_mhsa_bwd) and, for classification, YOLO11's C3k2 (C3k inside) and C2PSA
+(`AttentionT`: upa_psa_attention_train_fwd / _bwd, upa_dwconv2d_train_fwd / _bwd); other modules raise, and so does the non-legacy
+Detect head.
 
 `ClassificationTrainer` is the same step with another tail (`_tail_op`): `ClassifyT` = the train-mode Classify head, global average
 pool, exact-f32 linear, fused cross-entropy (v8ClassificationLoss, utils/loss.py:873-880) and their backward (include/upa.h, "image
@@ -105,19 +106,24 @@ def _new(n, c, h, w, dtype, dev, key):
 class ConvT:
     """Train-mode forward/backward of one conv (+ BatchNorm2d + activation, or + bias for the plain head outputs)."""
 
-    def __init__(self, ctx: _Ctx, conv: nn.Conv2d, bn, act_code: int, name: str):
+    def __init__(self, ctx: _Ctx, conv: nn.Conv2d, bn, act_code: int, name: str, no_dgrad: bool = False):
+        """`no_dgrad`: the layer's input needs no gradient (the model's first layer).  Only such a layer may be yolov5's 6x6 stride-2 pad-2
+        stem: its weight gradient has a kernel of its own and no transposed weights are packed for it."""
         if conv.groups != 1 or conv.dilation != (1, 1) or conv.kernel_size[0] != conv.kernel_size[1]:
             raise L.UpaError(f"training supports square kernels, groups=1, dilation=1 only ({name})")
         self.ctx, self.conv, self.bn, self.act, self.name = ctx, conv, bn, act_code, name
         self.k, self.s, self.p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        if self.k not in (1, 3) or self.s not in (1, 2):
+        self.stem6 = bool(no_dgrad) and (self.k, self.s, self.p) == (6, 2, 2) and conv.in_channels == 3
+        if (self.k not in (1, 3) or self.s not in (1, 2)) and not self.stem6:
             raise L.UpaError(f"training supports k in (1,3), stride in (1,2) ({name}: k={self.k} s={self.s})")
         self.cout, self.cin = conv.out_channels, conv.in_channels
         dev, code = ctx.device, ctx.code
         nb = L.lib().upa_conv_packed_weight_bytes(self.cout, self.cin, self.k, code)
         self.wp = torch.empty(nb, dtype=torch.uint8, device=dev)          # forward layout
-        nbt = L.lib().upa_conv_packed_weight_bytes(self.cin, self.cout, self.k, code)
-        self.wpt = torch.empty(nbt, dtype=torch.uint8, device=dev)        # transposed + flipped (data gradient)
+        self.wpt = None
+        if not self.stem6:
+            nbt = L.lib().upa_conv_packed_weight_bytes(self.cin, self.cout, self.k, code)
+            self.wpt = torch.empty(nbt, dtype=torch.uint8, device=dev)    # transposed + flipped (data gradient)
         if bn is not None:
             self.mean = torch.empty(self.cout, dtype=torch.float32, device=dev)
             self.var = torch.empty(self.cout, dtype=torch.float32, device=dev)
@@ -140,7 +146,9 @@ class ConvT:
         w = self.conv.weight
         L.check(lib.upa_pack_conv_weight_dev(w.data_ptr(), self.cout, self.cin, self.k, c.code, 0, self.wp.data_ptr(),
                                              _s(c.device)), "pack_dev")
-        if self.phase is None:
+        if self.wpt is None:
+            pass
+        elif self.phase is None:
             L.check(lib.upa_pack_conv_weight_dev(w.data_ptr(), self.cout, self.cin, self.k, c.code, 1, self.wpt.data_ptr(),
                                                  _s(c.device)), "pack_dev_t")
         else:
@@ -155,7 +163,9 @@ class ConvT:
         `pack_phase_weights()` must have refreshed first."""
         c, w = self.ctx, self.conv.weight
         d = [(w.data_ptr(), self.wp.data_ptr(), self.cout, self.cin, self.k, c.code, 0)]
-        if self.phase is None:
+        if self.wpt is None:
+            pass
+        elif self.phase is None:
             d.append((w.data_ptr(), self.wpt.data_ptr(), self.cout, self.cin, self.k, c.code, 1))
         else:
             d.append((self.phase_v.data_ptr(), self.phase.data_ptr(), 4 * self.cin, self.cout, 2, c.code, 0))
@@ -215,6 +225,8 @@ class ConvT:
     def backward(self, dy, dx=None, accumulate=False):
         """dy: gradient of this layer's output (NHWC view). dx: view receiving / accumulating the input gradient."""
         c, lib = self.ctx, L.lib()
+        if dx is not None and self.wpt is None:
+            raise L.UpaError(f"{self.name}: the 6x6 stride-2 stem has no data gradient on HIP (first layer only)")
         vdy = R.view_of(dy)
         npix = vdy.n * vdy.h * vdy.w
         st = _s(c.device)
@@ -425,11 +437,12 @@ class C3T(_Seq):
         self.cv2 = ConvT(ctx, m.cv2.conv, m.cv2.bn, m.cv2._act_code(), name + ".cv2")
         self.cv3 = ConvT(ctx, m.cv3.conv, m.cv3.bn, m.cv3._act_code(), name + ".cv3")
         self.c_ = self.cv1.cout
-        self.m = []
-        for i, b in enumerate(m.m):
-            if not isinstance(b, B.Bottleneck):
-                raise L.UpaError(f"{name}.m.{i}: {type(b).__name__} inside a C3 has no training path on HIP")
-            self.m.append(BottleneckT(ctx, b, f"{name}.m.{i}"))
+        self.m = [self._inner(ctx, b, f"{name}.m.{i}") for i, b in enumerate(m.m)]
+
+    def _inner(self, ctx, b, name):
+        if not isinstance(b, B.Bottleneck):
+            raise L.UpaError(f"{name}: {type(b).__name__} inside a C3 has no training path on HIP")
+        return BottleneckT(ctx, b, name)
 
     def convs(self):
         return [self.cv1, self.cv2, self.cv3] + [cv for b in self.m for cv in b.convs()]
@@ -457,6 +470,114 @@ class C3T(_Seq):
             gt = gp
         self.cv1.backward(gt, dx, accumulate)
         self.cv2.backward(g[:, k:], dx, True)
+
+
+MHSA_HEAD_DIMS = (4, 8, 16, 32, 64)  # the head widths upa_mhsa / upa_mhsa_train_fwd / upa_mhsa_bwd build
+
+
+class MHSAT(_Seq):
+    """Train-mode MHSA (block.py:6020-6062): softmax(q^T k) applied to v, unscaled, (+ BottleneckTransformer's residual in the epilogue).
+    forward:  query / key / value = three plain ConvT (bias, no BN) writing the channel slices [q | k | v] of one buffer ->
+              upa_mhsa_train_fwd (y, lse).
+    backward: upa_mhsa_bwd writes [dq | dk | dv] -> the three convs' backward, their data gradients accumulated into one dx.
+    Saved: qkv and lse (D is recomputed by the kernel, so the output is not kept)."""
+
+    def __init__(self, ctx, m: B.MHSA, name):
+        super().__init__(ctx)
+        if getattr(m, "pos", False):
+            raise L.UpaError(f"{name}: MHSA(pos_emb=True) has no training path on HIP")
+        self.c, self.heads = m.query.out_channels, int(m.heads)
+        self.d = self.c // self.heads
+        if self.c % self.heads or self.d not in MHSA_HEAD_DIMS:
+            raise L.UpaError(f"{name}: MHSA with {self.c} channels over {self.heads} heads: the attention kernels build head widths "
+                             f"{MHSA_HEAD_DIMS}")
+        self.qkv = [ConvT(ctx, cv, None, L.ACT_NONE, f"{name}.{tag}") for tag, cv in (("query", m.query), ("key", m.key), ("value", m.value))]
+        self.name = name
+
+    def convs(self):
+        return list(self.qkv)
+
+    def _rows(self, t):
+        """(q, k, v pointers, pitch) of a [q | k | v] buffer."""
+        v = R.view_of(t)
+        step = self.c * self.ctx.es
+        return v.ptr, v.ptr + step, v.ptr + 2 * step, v.ld
+
+    def forward(self, x, out=None, residual=None):
+        c, lib = self.ctx, L.lib()
+        dev, st = c.device, _s(c.device)
+        n, _, h, w = x.shape
+        ch = self.c
+        qkv = _new(n, 3 * ch, h, w, c.dtype, dev, (id(self), "qkv"))
+        for i, cv in enumerate(self.qkv):
+            cv.forward(x, out=qkv[:, i * ch:(i + 1) * ch])
+        y = out if out is not None else _new(n, ch, h, w, c.dtype, dev, (id(self), "y"))
+        lse = R.alloc_plain((n * self.heads * h * w,), torch.float32, dev, (id(self), "lse"))
+        vy = R.view_of(y)
+        rp, rld = (None, 0)
+        if residual is not None:
+            vr = R.view_of(residual)
+            rp, rld = vr.ptr, vr.ld
+        qp, kp, vp, ld = self._rows(qkv)
+        L.check(lib.upa_mhsa_train_fwd(qp, kp, vp, ld, n, h * w, self.heads, self.d, 1.0, rp, rld, vy.ptr, vy.ld, lse.data_ptr(), c.code, st),
+                f"mhsa_train_fwd[{self.name}]")
+        self.qkv_y, self.lse = qkv, lse
+        return y
+
+    def backward(self, dy, dx, accumulate):
+        c, lib = self.ctx, L.lib()
+        dev, st = c.device, _s(c.device)
+        n, _, h, w = self.qkv_y.shape
+        ch = self.c
+        dqkv = _new(n, 3 * ch, h, w, c.dtype, dev, (id(self), "dqkv"))
+        nws = lib.upa_mhsa_bwd_workspace_bytes(n, h * w, self.heads)
+        ws = R.alloc_plain((nws,), torch.uint8, dev, (id(self), "bwd_ws"))
+        qp, kp, vp, ld = self._rows(self.qkv_y)
+        dqp, dkp, dvp, ldd = self._rows(dqkv)
+        vdy = R.view_of(dy)
+        L.check(lib.upa_mhsa_bwd(qp, kp, vp, ld, self.lse.data_ptr(), vdy.ptr, vdy.ld, dqp, dkp, dvp, ldd, n, h * w, self.heads, self.d, 1.0,
+                                 ws.data_ptr(), nws, c.code, st), f"mhsa_bwd[{self.name}]")
+        for i, cv in enumerate(self.qkv):
+            cv.backward(dqkv[:, i * ch:(i + 1) * ch], dx, accumulate or i > 0)
+
+
+class BottleneckTransformerT(_Seq):
+    """Train-mode BottleneckTransformer (block.py:6065-6092): x + MHSA(cv1(x)); the add is the attention kernel's epilogue, its gradient
+    goes through `add_into` as in BottleneckT.  `fc1` is not part of the function (`DetectionTrainer._dead_parameters`)."""
+
+    def __init__(self, ctx, m: B.BottleneckTransformer, name):
+        super().__init__(ctx)
+        cv1 = getattr(m, "cv1", None)
+        if not (isinstance(m, B.BottleneckTransformer) and isinstance(cv1, CV.Conv) and len(m.cv2) == 1 and isinstance(m.cv2[0], B.MHSA)
+                and cv1.conv.kernel_size == (1, 1) and cv1.conv.stride == (1, 1)):
+            raise L.UpaError(f"{name}: {type(m).__name__} outside the BoT3 configuration (1x1 cv1, one MHSA, stride 1) has no training path "
+                             "on HIP")
+        self.cv1 = ConvT(ctx, cv1.conv, cv1.bn, cv1._act_code(), name + ".cv1")
+        self.attn = MHSAT(ctx, m.cv2[0], name + ".cv2.0")
+        self.add = bool(m.shortcut)
+
+    def convs(self):
+        return [self.cv1] + self.attn.convs()
+
+    def forward(self, x, out=None):
+        return self.attn.forward(self.cv1.forward(x), out=out, residual=x if self.add else None)
+
+    def backward(self, dy, dx, accumulate):
+        """dx must not be dy's buffer (the shortcut adds dy after dx is written)."""
+        c = self.ctx
+        vt = R.view_of(self.attn.qkv[0].x)
+        dt = _new(vt.n, vt.c, vt.h, vt.w, c.dtype, c.device, (id(self), "dt"))
+        self.attn.backward(dy, dt, False)
+        self.cv1.backward(dt, dx, accumulate)
+        if self.add:
+            add_into(c, dy, dx)
+
+
+class BoT3T(C3T):
+    """Train-mode BoT3 (block.py:6095-6109): C3's graph and concat buffer with BottleneckTransformers inside."""
+
+    def _inner(self, ctx, b, name):
+        return BottleneckTransformerT(ctx, b, name)
 
 
 class C3k2T(C2fT):
@@ -783,7 +904,31 @@ class DetectionTrainer:
         """Flat f32 buffers [biases | decayed weights | norm weights] with model.parameters() viewing into them."""
         from ..parallel import flat_parameter_layout
         layout, meta = flat_parameter_layout(self.model)
-        total = sum(n for _, n, _ in layout)
+        dead = self._dead_parameters()
+        if dead:
+            # parameters outside the function get no place in the three optimizer groups: they are laid out BEHIND the last group, where no
+            # optimizer launch, no gradient norm and no all-reduce reaches (all of them end at the last group's end).  The live parameters
+            # keep their relative order, so a model without dead parameters has exactly the layout it always had.
+            live = [row for row in meta if id(row[3]) not in dead]
+            gone = [row for row in meta if id(row[3]) in dead]
+            layout2, meta2, off = [], [], 0
+            for start, n, wd in layout:
+                rows = [r for r in meta if start <= r[1] < start + n and id(r[3]) not in dead]
+                g0 = off
+                for name, _, cnt, p in rows:
+                    meta2.append((name, off, cnt, p))
+                    off += cnt
+                layout2.append((g0, off - g0, wd))
+            self._dead_meta = []
+            for name, _, cnt, p in gone:
+                self._dead_meta.append((name, off, cnt, p))
+                off += cnt
+            assert len(meta2) == len(live)
+            layout, meta = layout2, meta2
+            total = off
+        else:
+            self._dead_meta = []
+            total = sum(n for _, n, _ in layout)
         dev = self.device
         self.P = torch.empty(total, dtype=torch.float32, device=dev)
         self.G = torch.zeros(total, dtype=torch.float32, device=dev)
@@ -792,7 +937,7 @@ class DetectionTrainer:
         if self.adam:  # exp_avg_sq and the step count (torch's state["step"]), device-side: see upa_adam_step_advance
             self.V = torch.zeros(total, dtype=torch.float32, device=dev)
             self.opt_step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-        for _name, off, n, p in meta:
+        for _name, off, n, p in list(meta) + self._dead_meta:
             self.P[off:off + n].copy_(p.detach().reshape(-1))  # plumbing: one-time gather of the initial weights
             p.data = self.P[off:off + n].view(p.shape)
             p.grad = self.G[off:off + n].view(p.shape)
@@ -814,6 +959,13 @@ class DetectionTrainer:
         self.sumsq_ws = torch.zeros(L.lib().upa_sumsq_workspace_bytes() // 8, dtype=torch.float64, device=dev)
         self.ema_d_dev = torch.zeros(1, dtype=torch.float32, device=dev)
 
+    def _dead_parameters(self):
+        """ids of the parameters the model's forward never reads: `BottleneckTransformer.fc1` (block.py:6088, kept for the state_dict).
+        Under autograd their `.grad` stays None and the reference's optimizer skips them - no weight decay, no momentum, and the EMA copy
+        stays equal to them.  Here they live behind the optimizer groups of the flat buffers (`_flatten_parameters`), so every step leaves
+        them, and their EMA copies, bit-unchanged."""
+        return {id(p) for m in self.model.modules() if isinstance(m, B.BottleneckTransformer) for p in m.fc1.parameters()}
+
     # ---- graph --------------------------------------------------------------------------------------------------------
     def _build_graph(self):
         ctx = self.ctx
@@ -831,10 +983,14 @@ class DetectionTrainer:
                 op, kind = C2PSAT(ctx, m, name), "c2f"
             elif isinstance(m, B.C2f):
                 op, kind = C2fT(ctx, m, name), "c2f"
+            elif isinstance(m, B.BoT3):
+                op, kind = BoT3T(ctx, m, name), "c3"
+            elif isinstance(m, B.C3) and not isinstance(m, B.C3k):  # (C3k: a C3 subclass that only lives inside a C3k2)
+                op, kind = C3T(ctx, m, name), "c3"
             elif isinstance(m, B.SPPF):
                 op, kind = SPPFT(ctx, m, name), "sppf"
             elif isinstance(m, CV.Conv):
-                op, kind = ConvT(ctx, m.conv, m.bn, m._act_code(), name), "conv"
+                op, kind = ConvT(ctx, m.conv, m.bn, m._act_code(), name, no_dgrad=(m.i == 0 and m.f == -1)), "conv"
             elif isinstance(m, CV.Concat):
                 op, kind = None, "concat"
             elif isinstance(m, RS.Upsample):
@@ -866,6 +1022,8 @@ class DetectionTrainer:
                 cout[nd.i] = nd.op.cout
             elif nd.kind in ("c2f", "sppf"):
                 cout[nd.i] = nd.op.cv2.cout
+            elif nd.kind == "c3":
+                cout[nd.i] = nd.op.cv3.cout
             elif nd.kind == "upsample":
                 cout[nd.i] = cout[src(nd.f)]
             elif nd.kind == "concat":
@@ -878,7 +1036,7 @@ class DetectionTrainer:
             c0 = 0
             for j in idx:
                 if j not in self._cat_slot and idx.count(j) == 1 and self.nodes[j].i == j and \
-                        self.nodes[j].kind in ("conv", "c2f", "sppf", "upsample"):
+                        self.nodes[j].kind in ("conv", "c2f", "c3", "sppf", "upsample"):
                     self._cat_slot[j] = (nd.i, c0, cout[j], cout[nd.i])
                 c0 += cout[j]
 
@@ -944,7 +1102,7 @@ class DetectionTrainer:
                     elif nd.kind == "upsample":
                         h, w = 2 * h, 2 * w
                     out = _new(n, ctot, h, w, ctx.dtype, dev, (id(self.nodes[cat_i]), "y"))[:, c0:c0 + cj]
-                if nd.kind in ("conv", "c2f", "sppf"):
+                if nd.kind in ("conv", "c2f", "c3", "sppf"):
                     y = nd.op.forward(xin, out=out)
                 elif nd.kind == "upsample":
                     n, c, h, w = xin.shape
@@ -976,7 +1134,7 @@ class DetectionTrainer:
                     self._bucket_hook(nd.i)
                     continue  # output unused by the loss
                 dy = nd.g
-                if nd.kind in ("conv", "c2f", "sppf"):
+                if nd.kind in ("conv", "c2f", "c3", "sppf"):
                     if nd.i == 0:
                         nd.op.backward(dy, None, False)
                     else:
