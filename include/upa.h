@@ -428,6 +428,32 @@ int upa_dwconv2d_train_fwd(const void* x, int n, int h, int w, int c, int ldx, c
 size_t upa_dwconv2d_bwd_workspace_bytes(int c);
 int upa_dwconv2d_bwd(const void* x, const void* dz, int n, int h, int w, int c, int ldx, int lddz, const float* w_c133, void* dx, int lddx,
                      int accumulate_dx, float* dw_c133, int accumulate_dw, void* ws, size_t ws_bytes, int dtype, void* stream);
+/* DWConv in train mode as ONE call each way: depthwise 3x3 (stride 1, pad 1, no bias) + BatchNorm2d on batch statistics + SiLU | none
+ * (conv.py:411-425 = Conv(c, c, 3, g=c), conv.py:177-186) - the class branch of the non-legacy Detect head (head.py:98-110).  The argument
+ * order and conventions of upa_conv2d_bn_act_fwd / upa_conv_bn_act_bwd: NHWC views with pitches (channel slices allowed), f32 | bf16
+ * storage, w_c133 the module's (C, 1, 3, 3) f32 weight, every sum an f32 fmaf chain in an order fixed by (n, h, w, c), no atomics (two
+ * calls and a graph replay are bit-identical), one rounding at each store.
+ * Forward: z = dwconv(x) (stored: the backward reads it; bit-equal to upa_dwconv2d_train_fwd), the per-channel sums of z and z^2 left by
+ * the convolution's own workgroups as rows of ws and added in workgroup order (no pass over z), mean / biased var / running update as
+ * upa_bn_finalize, y = act(bn(z)) as upa_bn_act_fwd.  A workgroup stages a band of 8 rows x 16 columns with its one-pixel halo in LDS
+ * once and keeps its nine weights per channel in registers.
+ * Backward: the two channel sums of upa_bn_act_bwd (dgamma, dbeta accumulated; red_ws = upa_channel_reduce_workspace_bytes(c)), then one
+ * tiled kernel that recomputes dz = gamma rstd (g - mean(g) - xhat mean(g xhat)) for tile and halo in LDS (f32; dz never reaches global
+ * memory), writes dx (+)= corr(dz, flipped taps) and leaves per-workgroup partials of dw in ws, then a combine in workgroup order:
+ * dw_c133 (+)= sum.  dx may be NULL.
+ * UPA_EINVAL, nothing launched and every buffer untouched: c or a pitch not a multiple of the 16-byte vector, a pitch below c, a view not
+ * 16-byte aligned, x / z / y overlapping (forward), dx overlapping x, z or dy other than as a disjoint channel slice of one buffer
+ * (backward), a workspace too small or misaligned, n*h*w < 2 (train-mode BatchNorm on one value per channel).  UPA_EUNSUPPORTED: a dtype
+ * outside f32 | bf16, an act outside none | SiLU, c > 256 vectors. */
+size_t upa_dwconv2d_bn_act_fwd_workspace_bytes(int n, int h, int w, int c);
+int upa_dwconv2d_bn_act_fwd(const void* x, int n, int h, int w, int c, int ldx, const float* w_c133, void* z, int ldz, float momentum,
+                            float* mean, float* var, float* running_mean, float* running_var, const float* gamma, const float* beta,
+                            float eps, int act, void* y, int ldy, void* ws, size_t ws_bytes, int dtype, void* stream);
+size_t upa_dwconv_bn_act_bwd_workspace_bytes(int n, int h, int w, int c);
+int upa_dwconv_bn_act_bwd(const void* x, int n, int h, int w, int c, int ldx, const void* z, const void* dy, int ldz, int lddy,
+                          const float* mean, const float* var, const float* gamma, const float* beta, float eps, int act, float* dgamma,
+                          float* dbeta, double* red_ws, const float* w_c133, float* dw_c133, int accumulate_dw, void* dx, int lddx,
+                          int accumulate_dx, void* ws, size_t ws_bytes, int dtype, void* stream);
 
 /* ---- RT-DETR decoder head pieces (f32 token rows) -------------------------------------------------------------------
  * nn.Linear: y[m,n] = act(x[m,k] . W[n,k]^T + bias[n]) (+ residual); W packed by upa_pack_conv_weight(k=1, UPA_F32).

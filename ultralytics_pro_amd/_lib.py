@@ -167,6 +167,12 @@ PROTOTYPES = {
     "upa_dwconv2d_train_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "upa_dwconv2d_bwd_workspace_bytes": (_sz, [_i]),
     "upa_dwconv2d_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp, _sz, _i, _vp]),
+    "upa_dwconv2d_bn_act_fwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "upa_dwconv2d_bn_act_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp, _i, _vp, _sz, _i,
+                                      _vp]),
+    "upa_dwconv_bn_act_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "upa_dwconv_bn_act_bwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i,
+                                    _i, _vp, _sz, _i, _vp]),
     "upa_linear": (_i, [_vp, C.c_long, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "upa_linear_bf16": (_i, [_vp, C.c_long, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "upa_linear_mixed": (_i, [_vp, _i, C.c_long, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp]),

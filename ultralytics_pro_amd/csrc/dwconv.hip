@@ -7,6 +7,7 @@
 // wave reads whole pixel rows and the x +- 1 neighbours of one thread are its neighbours' centre reads: the 3x3 neighbourhood is
 // served from L1 / L2, HBM sees each input row about once per output row.  Channel counts that are not a multiple of V (or
 // misaligned views) run the same code with V = 1.
+#include "bn_math.h"
 #include "common.h"
 
 namespace {
@@ -355,5 +356,381 @@ extern "C" int upa_dwconv2d_bwd(const void* x, const void* dz, int n, int h, int
     return dtype == UPA_BF16 ? launch_dwt<bf16_t, 8, true>(dz, n, h, w, c, lddz, w_c133, dx, lddx, accumulate_dx, s)
                              : launch_dwt<float, 4, true>(dz, n, h, w, c, lddz, w_c133, dx, lddx, accumulate_dx, s);
   }
+  return UPA_OK;
+}
+
+// ---- DWConv = depthwise 3x3 + BatchNorm(batch statistics) + SiLU | none, fused for training (conv.py:411-425 in train mode; the class
+// branch of the non-legacy Detect head, head.py:98-110) -------------------------------------------------------------------------------
+// Both kernels tile a map the same way.  A workgroup owns one image, one band of DWB_R rows and one chunk of channel vectors, and walks
+// the band in tiles of DWB_T columns.  Per tile it stages the (DWB_R + 2) x (DWB_T + 2) halo window in LDS once - zeros outside the
+// image - so every input element leaves HBM / L2 once per band it touches (1.25 x for the rows shared by two bands) instead of nine
+// times, and the nine taps are LDS reads.  Thread (slot, g): channel vector g of the chunk, pixels slot, slot + slots, ... of the window;
+// its 9 V weights stay in registers.  Everything a workgroup sums over pixels (the statistics, the weight gradient) is kept per thread
+// in f32, added over the slots in slot order through LDS, and leaves as ONE partial row per workgroup; a second launch adds the rows in
+// workgroup order.  The number of workgroups is n * ceil(h / DWB_R) * chunks: sized by the shape alone.
+//   LDS, forward:  180 window pixels x <= 16 vectors x 16 B                                  = 46080 B
+//   LDS, backward: 180 x <= 40 channels x (4 B dz in f32 + 4 | 2 B x)                        = 57600 B (f32), 43200 B (bf16)
+// A thread's 16-byte vector is one ds_read_b128 / ds_write_b128; consecutive threads of a slot take consecutive vectors.
+constexpr int DWB_T = 16, DWB_R = 8, DWB_WP = DWB_T + 2, DWB_HP = (DWB_R + 2) * DWB_WP;
+constexpr int DWB_FWD_CG = 16;  // channel vectors per workgroup, forward
+constexpr int DWB_BWD_CH = 40;  // channels per workgroup, backward (dz is kept in f32)
+
+namespace {
+
+template <typename T, int V>
+__device__ __forceinline__ void unpack_v(const u32x4& v, float (&o)[V]) {
+  if constexpr (sizeof(T) == 4) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = __uint_as_float(v[j]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      o[2 * j] = __uint_as_float(v[j] << 16);
+      o[2 * j + 1] = __uint_as_float(v[j] & 0xffff0000u);
+    }
+  }
+}
+
+// the value a store of `a` leaves in memory
+template <typename T>
+__device__ __forceinline__ float stored(float a) {
+  if constexpr (sizeof(T) == 4) return a;
+  else return bf16_to_f32(f32_to_bf16(a));
+}
+
+}  // namespace
+
+// z = dwconv(x), the same fmaf chain as dwconv3_train_kernel (tap order ky, kx; a tap outside the image adds fmaf(0, w, acc) = acc),
+// and rows[workgroup][2][c] = the sums and sums of squares of the values it stored.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void dwconv3_bn_fwd_kernel(const T* __restrict__ x, int h, int w, int c, int ldx, const float* __restrict__ wt,
+                                                             T* __restrict__ z, int ldz, float* __restrict__ rows, int CC, int bands) {
+  extern __shared__ __attribute__((aligned(16))) char dwb_sm[];
+  u32x4* tile = reinterpret_cast<u32x4*>(dwb_sm);
+  const int cg = c / V;
+  const int g0 = blockIdx.y * CC, cgl = min(CC, cg - g0), slots = 256 / cgl;
+  const int tid = threadIdx.x, slot = tid / cgl, g = tid - slot * cgl;
+  const bool active = slot < slots;
+  const int c0 = (g0 + g) * V;
+  const int b = blockIdx.x / bands, y0 = (blockIdx.x - b * bands) * DWB_R;
+  float wv[9][V], s0[V], s1[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) s0[j] = s1[j] = 0.f;
+  if (active) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+      for (int j = 0; j < V; ++j) wv[t][j] = wt[(size_t)(c0 + j) * 9 + t];
+  }
+  for (int x0 = 0; x0 < w; x0 += DWB_T) {
+    __syncthreads();  // the previous tile's reads are done
+    if (active) {
+      for (int hp = slot; hp < DWB_HP; hp += slots) {
+        const int hy = hp / DWB_WP, hx = hp - hy * DWB_WP;
+        const int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (iy >= 0 && iy < h && ix >= 0 && ix < w) v = *reinterpret_cast<const u32x4*>(x + (((size_t)b * h + iy) * w + ix) * (size_t)ldx + c0);
+        tile[hp * cgl + g] = v;
+      }
+    }
+    __syncthreads();
+    if (active) {
+      for (int ip = slot; ip < DWB_R * DWB_T; ip += slots) {
+        const int ty = ip / DWB_T, tx = ip - ty * DWB_T;
+        const int oy = y0 + ty, ox = x0 + tx;
+        if (oy >= h || ox >= w) continue;
+        float acc[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) acc[j] = 0.f;
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) {
+            float xv[V];
+            unpack_v<T, V>(tile[((ty + ky) * DWB_WP + tx + kx) * cgl + g], xv);
+#pragma unroll
+            for (int j = 0; j < V; ++j) acc[j] = fmaf(xv[j], wv[ky * 3 + kx][j], acc[j]);
+          }
+        store_v<T, V>(z + (((size_t)b * h + oy) * w + ox) * (size_t)ldz + c0, acc);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          const float r = stored<T>(acc[j]);
+          s0[j] += r;
+          s1[j] = fmaf(r, r, s1[j]);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  float* red = reinterpret_cast<float*>(dwb_sm);  // [slot][g][2][V]
+  if (active) {
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      red[((slot * cgl + g) * 2) * V + j] = s0[j];
+      red[((slot * cgl + g) * 2 + 1) * V + j] = s1[j];
+    }
+  }
+  __syncthreads();
+  if (slot == 0) {
+    float* row = rows + (size_t)blockIdx.x * 2 * c;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      float a0 = s0[j], a1 = s1[j];
+      for (int q = 1; q < slots; ++q) {
+        a0 += red[((q * cgl + g) * 2) * V + j];
+        a1 += red[((q * cgl + g) * 2 + 1) * V + j];
+      }
+      row[c0 + j] = a0;
+      row[c + c0 + j] = a1;
+    }
+  }
+}
+
+struct DwBwdParams {
+  const void* x; const void* z; const void* dy; void* dx;
+  int h, w, c, ldx, ldz, lddy, lddx;
+  const float* wt; const float* mean; const float* var; const float* gamma; const float* beta;
+  const double* s0; const double* s1;  // sum(du), sum(du * xhat) of upa_bn_bwd_sums
+  float eps, inv; int act, accumulate_dx;
+  float* ws;  // [workgroup][c][9] weight-gradient partials
+  int CC, bands;
+};
+
+// dz = gamma rstd (du - (s0 + xhat s1) / npix), du = dy act'(gamma xhat + beta) - the expression of bn_apply_kernel (train.hip) - formed
+// for the whole halo window in LDS and kept in f32; dx (+)= the correlation of dz with the flipped taps (tap order of
+// dwconv3_train_kernel<FLIP>), dw partials = sum over the tile's own pixels of dz * shifted x (tap order of dwconv3_wgrad_partial_kernel).
+template <typename T, int V>
+__global__ __launch_bounds__(256) void dwconv3_bn_bwd_kernel(const DwBwdParams p) {
+  extern __shared__ __attribute__((aligned(16))) char dwb_sm[];
+  const int c = p.c, h = p.h, w = p.w;
+  const int cg = c / V;
+  const int g0 = blockIdx.y * p.CC, cgl = min(p.CC, cg - g0), slots = 256 / cgl;
+  const int tid = threadIdx.x, slot = tid / cgl, g = tid - slot * cgl;
+  const bool active = slot < slots;
+  const int c0 = (g0 + g) * V;
+  const int b = blockIdx.x / p.bands, y0 = (blockIdx.x - b * p.bands) * DWB_R;
+  float* dzs = reinterpret_cast<float*>(dwb_sm);                                              // [window pixel][cgl][V] f32
+  const int dz_bytes = max(DWB_HP * cgl * V * 4, 256 * V * 4);                                // (the reduction below reuses it)
+  u32x4* xs = reinterpret_cast<u32x4*>(dwb_sm + dz_bytes);                                    // [window pixel][cgl] 16 B
+  const T* x = (const T*)p.x; const T* z = (const T*)p.z; const T* dy = (const T*)p.dy; T* dx = (T*)p.dx;
+  float wv[9][V], acc[9][V], mean[V], rstd[V], gam[V], bet[V], k0[V], k1[V];
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int j = 0; j < V; ++j) acc[t][j] = 0.f;
+  if (active) {
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const int ch = c0 + j;
+      mean[j] = p.mean[ch]; rstd[j] = 1.0f / sqrtf(p.var[ch] + p.eps); gam[j] = p.gamma[ch]; bet[j] = p.beta[ch];
+      k0[j] = (float)p.s0[ch]; k1[j] = (float)p.s1[ch];
+#pragma unroll
+      for (int t = 0; t < 9; ++t) wv[t][j] = p.wt[(size_t)ch * 9 + t];
+    }
+  }
+  const bool silu = p.act == UPA_ACT_SILU;
+  for (int x0 = 0; x0 < w; x0 += DWB_T) {
+    __syncthreads();
+    if (active) {
+      for (int hp = slot; hp < DWB_HP; hp += slots) {
+        const int hy = hp / DWB_WP, hx = hp - hy * DWB_WP;
+        const int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
+        u32x4 xr = {0u, 0u, 0u, 0u};
+        float d[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) d[j] = 0.f;
+        if (iy >= 0 && iy < h && ix >= 0 && ix < w) {
+          const size_t px = ((size_t)b * h + iy) * w + ix;
+          xr = *reinterpret_cast<const u32x4*>(x + px * (size_t)p.ldx + c0);
+          float zv[V], gv[V];
+          load_v<T, V>(z + px * (size_t)p.ldz + c0, zv);
+          load_v<T, V>(dy + px * (size_t)p.lddy + c0, gv);
+#pragma unroll
+          for (int j = 0; j < V; ++j) {
+            const float xh = (zv[j] - mean[j]) * rstd[j];
+            float du = gv[j];
+            if (silu) du *= silu_grad<sizeof(T) == 2>(gam[j] * xh + bet[j]);
+            d[j] = gam[j] * rstd[j] * (du - (k0[j] + xh * k1[j]) * p.inv);
+          }
+        }
+        xs[hp * cgl + g] = xr;
+#pragma unroll
+        for (int j = 0; j < V; j += 4) *reinterpret_cast<f32x4*>(dzs + (size_t)(hp * cgl + g) * V + j) = f32x4{d[j], d[j + 1], d[j + 2], d[j + 3]};
+      }
+    }
+    __syncthreads();
+    if (active) {
+      for (int ip = slot; ip < DWB_R * DWB_T; ip += slots) {
+        const int ty = ip / DWB_T, tx = ip - ty * DWB_T;
+        const int oy = y0 + ty, ox = x0 + tx;
+        if (oy >= h || ox >= w) continue;
+        float gz[V], a[V];
+        load_w<V>(dzs + (size_t)(((ty + 1) * DWB_WP + tx + 1) * cgl + g) * V, gz);
+#pragma unroll
+        for (int j = 0; j < V; ++j) a[j] = 0.f;
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) {
+            const int q = ((ty + ky) * DWB_WP + tx + kx) * cgl + g;
+            float dn[V], xn[V];
+            load_w<V>(dzs + (size_t)q * V, dn);
+            unpack_v<T, V>(xs[q], xn);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+              a[j] = fmaf(dn[j], wv[8 - (ky * 3 + kx)][j], a[j]);
+              acc[ky * 3 + kx][j] = fmaf(gz[j], xn[j], acc[ky * 3 + kx][j]);
+            }
+          }
+        if (dx) {
+          T* dp = dx + (((size_t)b * h + oy) * w + ox) * (size_t)p.lddx + c0;
+          if (p.accumulate_dx) {
+            float old[V];
+            load_v<T, V>(dp, old);
+#pragma unroll
+            for (int j = 0; j < V; ++j) a[j] += old[j];
+          }
+          store_v<T, V>(dp, a);
+        }
+      }
+    }
+  }
+  float* red = dzs;  // [thread][V]
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    __syncthreads();
+    if (active) {
+#pragma unroll
+      for (int j = 0; j < V; ++j) red[tid * V + j] = acc[t][j];
+    }
+    __syncthreads();
+    if (slot == 0) {
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        float s = acc[t][j];
+        for (int q = 1; q < slots; ++q) s += red[(q * cgl + g) * V + j];
+        p.ws[((size_t)blockIdx.x * c + c0 + j) * 9 + t] = s;
+      }
+    }
+  }
+}
+
+static int dwb_chunk(int cg, int max_cg) {  // channel vectors per workgroup: the fewest chunks that fit, of equal size
+  const int chunks = cdiv(cg, max_cg);
+  return cdiv(cg, chunks);
+}
+static long long dwb_wgs(int n, int h) { return (long long)n * cdiv(h, DWB_R); }
+
+// The checks the two fused entries share (after dwt_check): npix >= 2 (train-mode BatchNorm needs more than one value per channel), the
+// limits of the element-wise passes they reuse, the workgroup count.
+static int dwb_check(const char* what, int n, int h, int w, int c, int act, int dtype) {
+  if (act != UPA_ACT_NONE && act != UPA_ACT_SILU) {
+    upa_set_error("%s: act %d (none | SiLU)", what, act);
+    return UPA_EUNSUPPORTED;
+  }
+  if ((long long)n * h * w < 2) {
+    upa_set_error("%s: BatchNorm in train mode needs more than one value per channel (n*h*w = %lld)", what, (long long)n * h * w);
+    return UPA_EINVAL;
+  }
+  const int V = 16 / upa_elem_size(dtype);
+  if (c > 256 * V || dwb_wgs(n, h) > 0x7fffffffll / (9ll * c)) {
+    upa_set_error("%s: c = %d / %lld row bands outside the fused form", what, c, dwb_wgs(n, h));
+    return UPA_EUNSUPPORTED;
+  }
+  return UPA_OK;
+}
+
+extern "C" size_t upa_dwconv2d_bn_act_fwd_workspace_bytes(int n, int h, int w, int c) {
+  return n > 0 && h > 0 && w > 0 && c > 0 ? (size_t)dwb_wgs(n, h) * 2 * c * sizeof(float) : 0;
+}
+
+extern "C" int upa_bn_act_fwd(const void* z, long npix, int c, int ldz, const float* mean, const float* var, const float* gamma,
+                              const float* beta, float eps, int act, void* y, int ldy, const void* residual, int ldr, int dtype, void* stream);
+
+extern "C" int upa_dwconv2d_bn_act_fwd(const void* x, int n, int h, int w, int c, int ldx, const float* w_c133, void* z, int ldz, float momentum,
+                                       float* mean, float* var, float* running_mean, float* running_var, const float* gamma, const float* beta,
+                                       float eps, int act, void* y, int ldy, void* ws, size_t ws_bytes, int dtype, void* stream) {
+  UPA_CHECK_ARG(x && w_c133 && z && mean && var && gamma && beta && y && ws, "dwconv2d_bn_act_fwd: null pointer");
+  int rc = dwt_check("dwconv2d_bn_act_fwd", n, h, w, c, dtype);
+  if (rc == UPA_OK) rc = dwb_check("dwconv2d_bn_act_fwd", n, h, w, c, act, dtype);
+  if (rc != UPA_OK) return rc;
+  const int es = upa_elem_size(dtype), V = 16 / es;
+  UPA_CHECK_ARG(dwt_view_ok(x, ldx, c, V) && dwt_view_ok(z, ldz, c, V) && dwt_view_ok(y, ldy, c, V),
+                "dwconv2d_bn_act_fwd: views need ld >= c, ld %% %d == 0 and 16-byte alignment", V);
+  const size_t xb = dwt_view_bytes(n, h, w, c, ldx, es), zb = dwt_view_bytes(n, h, w, c, ldz, es), yb = dwt_view_bytes(n, h, w, c, ldy, es);
+  UPA_CHECK_ARG(!dwt_overlap(x, xb, z, zb) && !dwt_overlap(x, xb, y, yb) && !dwt_overlap(z, zb, y, yb),
+                "dwconv2d_bn_act_fwd: x, z and y must not overlap");
+  const size_t need = upa_dwconv2d_bn_act_fwd_workspace_bytes(n, h, w, c);
+  UPA_CHECK_ARG(((uintptr_t)ws % 16) == 0 && ws_bytes >= need, "dwconv2d_bn_act_fwd: workspace of %zu bytes, %zu needed (16-byte aligned)", ws_bytes, need);
+  hipStream_t s = (hipStream_t)stream;
+  const int cg = c / V, CC = dwb_chunk(cg, DWB_FWD_CG), bands = cdiv(h, DWB_R);
+  const dim3 grid((unsigned)dwb_wgs(n, h), (unsigned)cdiv(cg, CC));
+  const size_t lds = (size_t)(DWB_HP * CC * 16 > 256 * V * 8 ? DWB_HP * CC * 16 : 256 * V * 8);
+  if (dtype == UPA_BF16)
+    hipLaunchKernelGGL((dwconv3_bn_fwd_kernel<bf16_t, 8>), grid, dim3(256), lds, s, (const bf16_t*)x, h, w, c, ldx, w_c133, (bf16_t*)z, ldz, (float*)ws,
+                       CC, bands);
+  else
+    hipLaunchKernelGGL((dwconv3_bn_fwd_kernel<float, 4>), grid, dim3(256), lds, s, (const float*)x, h, w, c, ldx, w_c133, (float*)z, ldz, (float*)ws,
+                       CC, bands);
+  UPA_LAUNCH_CHECK();
+  // The two entries below run after z and ws are written.  Every argument check they make (null pointers, c, ld, alignment, act, dtype,
+  // npix >= 2) is a subset of the ones made above, so they cannot refuse here; a check added to either must be repeated above, or a
+  // refusal would no longer leave every buffer untouched.
+  const long npix = (long)n * h * w;
+  rc = upa_bn_finalize_rows((const float*)ws, (int)grid.x, c, npix, c, momentum, mean, var, running_mean, running_var, stream);
+  if (rc != UPA_OK) return rc;
+  return upa_bn_act_fwd(z, npix, c, ldz, mean, var, gamma, beta, eps, act, y, ldy, nullptr, 0, dtype, stream);
+}
+
+extern "C" size_t upa_dwconv_bn_act_bwd_workspace_bytes(int n, int h, int w, int c) {
+  return n > 0 && h > 0 && w > 0 && c > 0 ? (size_t)dwb_wgs(n, h) * c * 9 * sizeof(float) : 0;
+}
+
+// dx may be another channel slice of a buffer x, z or dy lives in (same pitch, disjoint channels); any other overlap is a race between
+// the workgroup that writes a pixel and the neighbours that read it
+static bool dwb_dx_clash(const void* dx, int lddx, const void* a, int lda, int n, int h, int w, int c, int es) {
+  if (!dwt_overlap(dx, dwt_view_bytes(n, h, w, c, lddx, es), a, dwt_view_bytes(n, h, w, c, lda, es))) return false;
+  if (lddx != lda) return true;
+  const long long pitch = (long long)lda * es, d = (const char*)dx - (const char*)a;
+  const long long r = ((d % pitch) + pitch) % pitch;  // dx's first channel inside a's pixel
+  return !(r >= (long long)c * es && r + (long long)c * es <= pitch);
+}
+
+extern "C" int upa_dwconv_bn_act_bwd(const void* x, int n, int h, int w, int c, int ldx, const void* z, const void* dy, int ldz, int lddy,
+                                     const float* mean, const float* var, const float* gamma, const float* beta, float eps, int act, float* dgamma,
+                                     float* dbeta, double* red_ws, const float* w_c133, float* dw_c133, int accumulate_dw, void* dx, int lddx,
+                                     int accumulate_dx, void* ws, size_t ws_bytes, int dtype, void* stream) {
+  UPA_CHECK_ARG(x && z && dy && mean && var && gamma && beta && dgamma && dbeta && red_ws && w_c133 && dw_c133 && ws,
+                "dwconv_bn_act_bwd: null pointer");
+  int rc = dwt_check("dwconv_bn_act_bwd", n, h, w, c, dtype);
+  if (rc == UPA_OK) rc = dwb_check("dwconv_bn_act_bwd", n, h, w, c, act, dtype);
+  if (rc != UPA_OK) return rc;
+  const int es = upa_elem_size(dtype), V = 16 / es;
+  UPA_CHECK_ARG(dwt_view_ok(x, ldx, c, V) && dwt_view_ok(z, ldz, c, V) && dwt_view_ok(dy, lddy, c, V) && (!dx || dwt_view_ok(dx, lddx, c, V)),
+                "dwconv_bn_act_bwd: views need ld >= c, ld %% %d == 0 and 16-byte alignment", V);
+  UPA_CHECK_ARG(!dx || !(dwb_dx_clash(dx, lddx, x, ldx, n, h, w, c, es) || dwb_dx_clash(dx, lddx, z, ldz, n, h, w, c, es) ||
+                         dwb_dx_clash(dx, lddx, dy, lddy, n, h, w, c, es)),
+                "dwconv_bn_act_bwd: dx overlaps x, z or dy");
+  const size_t need = upa_dwconv_bn_act_bwd_workspace_bytes(n, h, w, c);
+  UPA_CHECK_ARG(((uintptr_t)ws % 16) == 0 && ws_bytes >= need, "dwconv_bn_act_bwd: workspace of %zu bytes, %zu needed (16-byte aligned)", ws_bytes, need);
+  hipStream_t s = (hipStream_t)stream;
+  const long npix = (long)n * h * w;
+  const double* fin = upa_bn_bwd_sums(z, dy, npix, c, ldz, lddy, mean, var, gamma, beta, eps, act, dgamma, dbeta, 1, red_ws, dtype, s);
+  UPA_LAUNCH_CHECK();
+  DwBwdParams p{};
+  p.x = x; p.z = z; p.dy = dy; p.dx = dx; p.h = h; p.w = w; p.c = c; p.ldx = ldx; p.ldz = ldz; p.lddy = lddy; p.lddx = lddx;
+  p.wt = w_c133; p.mean = mean; p.var = var; p.gamma = gamma; p.beta = beta; p.s0 = fin; p.s1 = fin + c; p.eps = eps;
+  p.inv = 1.0f / (float)npix; p.act = act; p.accumulate_dx = accumulate_dx; p.ws = (float*)ws;
+  const int cg = c / V;
+  p.CC = dwb_chunk(cg, DWB_BWD_CH / V); p.bands = cdiv(h, DWB_R);
+  const dim3 grid((unsigned)dwb_wgs(n, h), (unsigned)cdiv(cg, p.CC));
+  const int dzb = DWB_HP * p.CC * V * 4 > 256 * V * 4 ? DWB_HP * p.CC * V * 4 : 256 * V * 4;
+  const size_t lds = (size_t)dzb + (size_t)DWB_HP * p.CC * 16;
+  if (dtype == UPA_BF16) hipLaunchKernelGGL((dwconv3_bn_bwd_kernel<bf16_t, 8>), grid, dim3(256), lds, s, p);
+  else hipLaunchKernelGGL((dwconv3_bn_bwd_kernel<float, 4>), grid, dim3(256), lds, s, p);
+  UPA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(dwconv3_wgrad_combine_kernel, dim3((unsigned)cdiv(c * 9, 256)), dim3(256), 0, s, (const float*)ws, (int)grid.x, c * 9, dw_c133,
+                     accumulate_dw);
+  UPA_LAUNCH_CHECK();
   return UPA_OK;
 }

@@ -15,6 +15,7 @@
 // All HBM-bound except wgrad (f32 MFMA bound).
 #include <stdlib.h>
 
+#include "bn_math.h"
 #include "common.h"
 
 namespace {
@@ -112,18 +113,7 @@ struct ReduceParams {
   double* out0; double* out1;
 };
 
-// FAST (bf16 perf mode): v_exp_f32 / v_rcp_f32, 1 ulp - the operands carry 8 bits; the f32 parity mode keeps ocml expf
-// and the IEEE divide.  (These element-wise passes are VALU-bound, not HBM-bound, with the accurate forms.)
-template <bool FAST>
-__device__ __forceinline__ float sigmoid_t(float u) {
-  if constexpr (FAST) return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(u * -1.44269504088896340736f));
-  else return 1.0f / (1.0f + expf(-u));
-}
-template <bool FAST>
-__device__ __forceinline__ float silu_grad(float u) {
-  const float s = sigmoid_t<FAST>(u);
-  return s * (1.0f + u * (1.0f - s));
-}
+// (sigmoid_t / silu_grad, the activation derivative of MODE 1: bn_math.h)
 
 template <typename T, int MODE>
 __global__ __launch_bounds__(256) void channel_reduce_kernel(const ReduceParams p) {
@@ -1721,6 +1711,21 @@ extern "C" int upa_bn_act_fwd(const void* z, long npix, int c, int ldz, const fl
   return UPA_OK;
 }
 
+// (bn_math.h) the reduction and its combine, without the dz pass: also the first stage of upa_dwconv_bn_act_bwd (dwconv.hip)
+const double* upa_bn_bwd_sums(const void* z, const void* dy, long npix, int c, int ldz, int lddy, const float* mean, const float* var,
+                              const float* gamma, const float* beta, float eps, int act, float* dgamma, float* dbeta, int accumulate,
+                              double* ws, int dtype, hipStream_t s) {
+  ReduceParams r{};
+  r.z = (const char*)z; r.dy = (const char*)dy; r.npix = npix; r.c = c; r.ldz = ldz; r.lddy = lddy;
+  r.mean = mean; r.var = var; r.gamma = gamma; r.beta = beta; r.eps = eps; r.act = act;
+  const int nb = run_channel_reduce(r, 1, dtype, ws, s);
+  double* fin = ws + (size_t)2048 * 2 * c;
+  CombineParams q{};
+  q.part = ws; q.nblocks = nb; q.c = c; q.fin = fin; q.dgamma = dgamma; q.dbeta = dbeta; q.accumulate = accumulate;
+  hipLaunchKernelGGL((combine_finalize_kernel<1>), dim3(c), dim3(256), 0, s, q);
+  return fin;
+}
+
 extern "C" int upa_bn_act_bwd(const void* z, const void* dy, long npix, int c, int ldz, int lddy, const float* mean,
                               const float* var, const float* gamma, const float* beta, float eps, int act, void* dz, int lddz,
                               float* dgamma, float* dbeta, int accumulate, double* ws /* 2*c doubles */, int dtype, void* stream) {
@@ -1730,14 +1735,7 @@ extern "C" int upa_bn_act_bwd(const void* z, const void* dy, long npix, int c, i
   if (int rc = check_pitch(lddy, dtype, "bn_act_bwd", "lddy")) return rc;
   if (int rc = check_pitch(lddz, dtype, "bn_act_bwd", "lddz")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  ReduceParams r{};
-  r.z = (const char*)z; r.dy = (const char*)dy; r.npix = npix; r.c = c; r.ldz = ldz; r.lddy = lddy;
-  r.mean = mean; r.var = var; r.gamma = gamma; r.beta = beta; r.eps = eps; r.act = act;
-  const int nb = run_channel_reduce(r, 1, dtype, ws, s);
-  double* fin = ws + (size_t)2048 * 2 * c;
-  CombineParams q{};
-  q.part = ws; q.nblocks = nb; q.c = c; q.fin = fin; q.dgamma = dgamma; q.dbeta = dbeta; q.accumulate = accumulate;
-  hipLaunchKernelGGL((combine_finalize_kernel<1>), dim3(c), dim3(256), 0, s, q);
+  const double* fin = upa_bn_bwd_sums(z, dy, npix, c, ldz, lddy, mean, var, gamma, beta, eps, act, dgamma, dbeta, accumulate, ws, dtype, s);
   BnApplyParams p{};
   p.z = (const char*)z; p.y = (char*)dz; p.aux = (const char*)dy; p.npix = npix; p.c = c; p.ldz = ldz; p.ldy = lddz; p.ldaux = lddy;
   p.mean = mean; p.var = var; p.gamma = gamma; p.beta = beta; p.s0 = fin; p.s1 = fin + c; p.eps = eps; p.act = act;

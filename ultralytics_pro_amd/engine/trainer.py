@@ -17,8 +17,9 @@ launches of upa_adam_ema behind one upa_adam_step_advance (second-moment buffer 
 `iterations` and the head's class count (`resolve_optimizer`).
 The yolov8 module set is differentiable here (Conv, C2f, Bottleneck, SPPF, nn.Upsample, Concat, Detect), the yolov5-BoT3 set (the 6x6
 stride-2 stem, bare C3, BoT3 = `MHSAT`: upa_mhsa_train_fwd / upa_mhsa_bwd) and, for classification, YOLO11's C3k2 (C3k inside) and C2PSA
-(`AttentionT`: upa_psa_attention_train_fwd / _bwd, upa_dwconv2d_train_fwd / _bwd); other modules raise, and so does the non-legacy
-Detect head.
+(`AttentionT`: upa_psa_attention_train_fwd / _bwd, upa_dwconv2d_train_fwd / _bwd); other modules raise.  The non-legacy Detect head
+of YOLO11 (depthwise class branch: `DWConvT`, upa_dwconv2d_bn_act_fwd / upa_dwconv_bn_act_bwd) trains with `yolo11=True` and raises
+without it.
 
 `ClassificationTrainer` is the same step with another tail (`_tail_op`): `ClassifyT` = the train-mode Classify head, global average
 pool, exact-f32 linear, fused cross-entropy (v8ClassificationLoss, utils/loss.py:873-880) and their backward (include/upa.h, "image
@@ -307,6 +308,121 @@ class ConvT:
                     "dilate2x")
             src = up
         self._conv(src, self.wpt, self.cin, self.k, 1, self.k - 1 - self.p, dx, residual=dx if accumulate else None)
+
+
+class DWConvT:
+    """Train-mode forward/backward of one DWConv (conv.py:411-425: depthwise 3x3, stride 1, pad 1 + BatchNorm2d + SiLU | none) - the class
+    branch of the non-legacy Detect head (head.py:98-110).  The `ConvT` surface; the weight stays the module's (C, 1, 3, 3) f32 master
+    weight, so there is nothing to pack.
+      fused (default): upa_dwconv2d_bn_act_fwd / upa_dwconv_bn_act_bwd - the statistics come out of the convolution's workgroups and dz
+                       lives in LDS only;
+      composed:        upa_dwconv2d_train_fwd, upa_bn_stats, upa_bn_finalize, upa_bn_act_fwd / upa_bn_act_bwd (dz stored), upa_dwconv2d_bwd.
+    A fused entry that answers UPA_EUNSUPPORTED falls through to the composed form.  All workspaces follow the context's per-stream
+    selection (`ctx.ws`, `_dw_ws`): the small Detect levels run on the level stream beside level 0."""
+
+    fused = True  # (False: the composed form.  The A/B of tools/bench_yolo11_train.py, DESIGN section 6: 9.60 against 9.86 ms per step)
+
+    @staticmethod
+    def check(conv: nn.Conv2d, bn, act_code: int, name: str, nc=None):
+        """The refusals, from the module alone (`DetectionTrainer` runs them before anything touches the device)."""
+        c = conv.in_channels
+        if not (conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1)
+                and conv.groups == c == conv.out_channels and conv.bias is None and bn is not None):
+            raise L.UpaError(f"{name}: training supports a depthwise conv with k 3, stride 1, pad 1, groups = cin = cout + BatchNorm only "
+                             f"(got k={tuple(conv.kernel_size)} s={tuple(conv.stride)} cin={c} cout={conv.out_channels} "
+                             f"groups={conv.groups})")
+        if c % 8 != 0:
+            why = "" if nc is None else f" (the head's class-branch width is c3 = max(ch[0], min(nc, 100)) with nc = {nc})"
+            raise L.UpaError(f"{name}: the depthwise training kernels take channel counts that are multiples of 8, got {c}{why}")
+        if act_code not in (L.ACT_NONE, L.ACT_SILU):
+            raise L.UpaError(f"{name}: training supports SiLU or no activation behind a depthwise conv")
+
+    def __init__(self, ctx: _Ctx, conv: nn.Conv2d, bn, act_code: int, name: str, nc=None):
+        self.check(conv, bn, act_code, name, nc)
+        c = conv.in_channels
+        self.ctx, self.conv, self.bn, self.act, self.name = ctx, conv, bn, act_code, name
+        self.k, self.s, self.p = 3, 1, 1
+        self.cin = self.cout = c
+        self.mean = torch.empty(c, dtype=torch.float32, device=ctx.device)
+        self.var = torch.empty(c, dtype=torch.float32, device=ctx.device)
+        self.x = self.z = None
+
+    def convs(self):
+        return [self]
+
+    # the trainer's weight-repack hooks: the kernels read the master weight
+    def pack(self):
+        pass
+
+    def pack_descs(self):
+        return []
+
+    def pack_phase_weights(self):
+        pass
+
+    def _dw_ws(self, nbytes):
+        """`nbytes` of workspace for a launch on the CURRENT stream: one buffer per size and per stream selection of the context."""
+        c = self.ctx
+        return R.alloc_plain((max(int(nbytes), 16),), torch.uint8, c.device, ("dw_ws", c._ws_sel))
+
+    def forward(self, x, out=None):
+        c, lib = self.ctx, L.lib()
+        n, ch, h, w = x.shape
+        st = _s(c.device)
+        self.x = x
+        z = _new(n, ch, h, w, c.dtype, c.device, (id(self), "z"))
+        y = out if out is not None else _new(n, ch, h, w, c.dtype, c.device, (id(self), "y"))
+        vx, vz, vy = R.view_of(x), R.view_of(z), R.view_of(y)
+        bn, wt = self.bn, self.conv.weight
+        self.z = z
+        if self.fused:
+            ws = self._dw_ws(lib.upa_dwconv2d_bn_act_fwd_workspace_bytes(n, h, w, ch))
+            rc = lib.upa_dwconv2d_bn_act_fwd(vx.ptr, n, h, w, ch, vx.ld, wt.data_ptr(), vz.ptr, vz.ld, ConvT._momentum(bn),
+                                             self.mean.data_ptr(), self.var.data_ptr(), bn.running_mean.data_ptr(),
+                                             bn.running_var.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps), self.act,
+                                             vy.ptr, vy.ld, ws.data_ptr(), ws.numel(), vx.dtype, st)
+            if rc != L.UPA_EUNSUPPORTED:
+                L.check(rc, f"dwconv2d_bn_act_fwd[{self.name}]")
+                return y
+        npix = n * h * w
+        L.check(lib.upa_dwconv2d_train_fwd(vx.ptr, n, h, w, ch, vx.ld, wt.data_ptr(), vz.ptr, vz.ld, vx.dtype, st),
+                f"dwconv2d_train_fwd[{self.name}]")
+        L.check(lib.upa_bn_stats(vz.ptr, npix, ch, vz.ld, c.ws.data_ptr(), vz.dtype, st), f"bn_stats[{self.name}]")
+        L.check(lib.upa_bn_finalize(c.ws.data_ptr(), npix, ch, ConvT._momentum(bn), self.mean.data_ptr(), self.var.data_ptr(),
+                                    bn.running_mean.data_ptr(), bn.running_var.data_ptr(), st), f"bn_finalize[{self.name}]")
+        L.check(lib.upa_bn_act_fwd(vz.ptr, npix, ch, vz.ld, self.mean.data_ptr(), self.var.data_ptr(), bn.weight.data_ptr(),
+                                   bn.bias.data_ptr(), float(bn.eps), self.act, vy.ptr, vy.ld, None, 0, vz.dtype, st),
+                f"bn_act_fwd[{self.name}]")
+        return y
+
+    def backward(self, dy, dx=None, accumulate=False):
+        c, lib = self.ctx, L.lib()
+        st = _s(c.device)
+        vx, vz, vdy = R.view_of(self.x), R.view_of(self.z), R.view_of(dy)
+        n, h, w, ch = vz.n, vz.h, vz.w, vz.c
+        vdx = None if dx is None else R.view_of(dx)
+        bn, wt = self.bn, self.conv.weight
+        if self.fused:
+            ws = self._dw_ws(lib.upa_dwconv_bn_act_bwd_workspace_bytes(n, h, w, ch))
+            rc = lib.upa_dwconv_bn_act_bwd(vx.ptr, n, h, w, ch, vx.ld, vz.ptr, vdy.ptr, vz.ld, vdy.ld, self.mean.data_ptr(),
+                                           self.var.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps), self.act,
+                                           bn.weight.grad.data_ptr(), bn.bias.grad.data_ptr(), c.ws.data_ptr(), wt.data_ptr(),
+                                           wt.grad.data_ptr(), 1, None if dx is None else vdx.ptr, 0 if dx is None else vdx.ld,
+                                           int(accumulate), ws.data_ptr(), ws.numel(), vz.dtype, st)
+            if rc != L.UPA_EUNSUPPORTED:
+                L.check(rc, f"dwconv_bn_act_bwd[{self.name}]")
+                return
+        npix = n * h * w
+        dz = _new(n, ch, h, w, c.dtype, c.device, (id(self), "dz"))
+        vdz = R.view_of(dz)
+        L.check(lib.upa_bn_act_bwd(vz.ptr, vdy.ptr, npix, ch, vz.ld, vdy.ld, self.mean.data_ptr(), self.var.data_ptr(),
+                                   bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps), self.act, vdz.ptr, vdz.ld,
+                                   bn.weight.grad.data_ptr(), bn.bias.grad.data_ptr(), 1, c.ws.data_ptr(), vz.dtype, st),
+                f"bn_act_bwd[{self.name}]")
+        ws = self._dw_ws(lib.upa_dwconv2d_bwd_workspace_bytes(ch))
+        L.check(lib.upa_dwconv2d_bwd(vx.ptr, vdz.ptr, n, h, w, ch, vx.ld, vdz.ld, wt.data_ptr(), None if dx is None else vdx.ptr,
+                                     0 if dx is None else vdx.ld, int(accumulate), wt.grad.data_ptr(), 1, ws.data_ptr(), ws.numel(),
+                                     vz.dtype, st), f"dwconv2d_bwd[{self.name}]")
 
 
 class _Seq:
@@ -862,17 +978,21 @@ class DetectionTrainer:
     "auto" with `iterations` (`resolve_optimizer`); `optimizer_name` is the resolved one."""
 
     def __init__(self, model, dtype=torch.bfloat16, hyp=None, device=None, world_size=1, ema=True, wgrad_streams: int = 1,
-                 amp_scaler: bool = False, optimizer: str = "SGD", iterations=None):
+                 amp_scaler: bool = False, optimizer: str = "SGD", iterations=None, yolo11: bool = False):
         self.optimizer_name, opt_hyp, self._auto_optimizer = resolve_optimizer(
             optimizer, iterations, _head_nc(model) if str(optimizer).lower() == "auto" and iterations is not None else 0)
-        # the non-legacy Detect head (YOLO11: depthwise class branch) has no backward here: the graph below would take its DWConv
-        # class branch for the legacy one.  C3k2 / C2PSA train (ClassificationTrainer), but no YOLO11 detection model is enabled by them
+        # the non-legacy Detect head (YOLO11: depthwise class branch, `DWConvT`) trains on request only: `yolo11=True`
         if any(isinstance(m, H.Segment) for m in model.modules()):
             raise L.UpaError("segmentation models (Segment head) have no training path on HIP: v8SegmentationLoss is out of scope")
         for m in model.modules():
             if isinstance(m, H.Detect) and not m.legacy_cls:
-                raise L.UpaError(f"{type(m).__name__} (YOLO11, non-legacy head with a depthwise class branch) has no training path on HIP "
-                                 "yet: YOLO11 detection models do not train")
+                if not yolo11:
+                    raise L.UpaError(f"{type(m).__name__} (YOLO11, non-legacy head with a depthwise class branch) has no training path "
+                                     "on HIP unless it is asked for: pass yolo11=True to train a YOLO11 detection model")
+                for i, seq in enumerate(m.cv3):  # the depthwise convs' refusals, before anything touches the device
+                    for j in (0, 1):
+                        dw = seq[j][0]
+                        DWConvT.check(dw.conv, getattr(dw, "bn", None), dw._act_code(), f"model.{getattr(m, 'i', '?')}.cv3.{i}.{j}.0", nc=m.nc)
         self.model = model
         self.hyp = dict(HYP, **(hyp or {}))
         self.hyp.update(opt_hyp)  # auto ignores lr0 and momentum of the arguments, as the reference does
@@ -1535,6 +1655,15 @@ class DetectT(_Seq):
         for i in range(m.nl):
             row = []
             for tag, seq in (("cv2", m.cv2[i]), ("cv3", m.cv3[i])):
+                if tag == "cv3" and not m.legacy_cls:
+                    # head.py:101-110: Sequential(DWConv, Conv 1x1), Sequential(DWConv, Conv 1x1), Conv2d 1x1
+                    ops = []
+                    for j in (0, 1):
+                        dw, pw = seq[j][0], seq[j][1]
+                        ops.append(DWConvT(ctx, dw.conv, dw.bn, dw._act_code(), f"{name}.{tag}.{i}.{j}.0", nc=m.nc))
+                        ops.append(ConvT(ctx, pw.conv, pw.bn, pw._act_code(), f"{name}.{tag}.{i}.{j}.1"))
+                    row.append(ops + [ConvT(ctx, seq[2], None, L.ACT_NONE, f"{name}.{tag}.{i}.2")])
+                    continue
                 row.append([ConvT(ctx, seq[0].conv, seq[0].bn, seq[0]._act_code(), f"{name}.{tag}.{i}.0"),
                             ConvT(ctx, seq[1].conv, seq[1].bn, seq[1]._act_code(), f"{name}.{tag}.{i}.1"),
                             ConvT(ctx, seq[2], None, L.ACT_NONE, f"{name}.{tag}.{i}.2")])
@@ -1554,8 +1683,10 @@ class DetectT(_Seq):
             n, _, h, w = x.shape
             raw = _new(n, self.no, h, w, c.dtype, dev, (id(self), "raw", i))
             for k, (seq, out) in enumerate(zip(self.br[i], (raw[:, :nb], raw[:, nb:]))):
-                t = seq[1].forward(seq[0].forward(x))
-                seq[2].forward(t, out=out)
+                t = x
+                for op in seq[:-1]:
+                    t = op.forward(t)
+                seq[-1].forward(t, out=out)
             self.raw[i] = raw
             if c.dtype == torch.float32:
                 self.raw32[i] = raw
@@ -1646,12 +1777,13 @@ class DetectT(_Seq):
             src = tr.nodes[self.m.f[i]]
             dx, acc = tr._grad_of(src)
             for k, (seq, dy) in enumerate(zip(self.br[i], (graw[:, :nb], graw[:, nb:]))):
-                vt1, vt0 = R.view_of(seq[2].x), R.view_of(seq[1].x)
-                d1 = _new(vt1.n, vt1.c, vt1.h, vt1.w, c.dtype, dev, (id(self), "d1", i, k))
-                d0 = _new(vt0.n, vt0.c, vt0.h, vt0.w, c.dtype, dev, (id(self), "d0", i, k))
-                seq[2].backward(dy, d1, False)
-                seq[1].backward(d1, d0, False)
-                seq[0].backward(d0, dx, acc or k > 0)
+                g = dy
+                for j in range(len(seq) - 1, 0, -1):  # the chain's inner gradients: one buffer per op input
+                    vt = R.view_of(seq[j].x)
+                    d = _new(vt.n, vt.c, vt.h, vt.w, c.dtype, dev, (id(self), "d", i, k, j))
+                    seq[j].backward(g, d, False)
+                    g = d
+                seq[0].backward(g, dx, acc or k > 0)
 
         # as in the forward pass: the small levels' chains beside the 80 x 80 level's (they write the gradients of different neck outputs)
         self._fork_levels(lambda: level_bwd(0), lambda: [level_bwd(i) for i in range(1, nl)], nl > 1)
