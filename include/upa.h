@@ -726,6 +726,47 @@ int upa_resize_bilinear(const float* x, int planes, int h, int w, int top, int l
  * 16-byte multiples, where upa_copy_view does not apply). */
 int upa_copy_rows(const float* src, long rows, int cols, long lds, float* dst, long ldd, void* stream);
 
+/* ---- segmentation training (Proto backward, v8SegmentationLoss's mask term) ----------------------------------------------------
+ * Backward of upa_conv_transpose2x2 (Proto's upsample, nn/modules/block.py:257-276, under autograd in the reference): with
+ * x NHWC (n, h, w, cin), dy NHWC (n, 2h, 2w, cout) and `weight` the (cin, cout, 2, 2) f32 torch weight,
+ *   dx[n, y, x, ci]      (+)= sum_{co,i,j} dy[n, 2y+i, 2x+j, co] weight[ci, co, i, j]     (dx NULL: not computed; accumulate_dx)
+ *   dweight[ci, co, i, j] (+)= sum_{n,y,x} x[n, y, x, ci] dy[n, 2y+i, 2x+j, co]           (f32, torch layout; accumulate_w)
+ *   dbias[co]            (+)= sum of dy over all pixels                                   (f32; accumulate_w)
+ * bf16 operands (the weight rounded as upa_pack_conv_transpose2x2_weight rounds it) on the bf16 MFMAs, f32 on exact-f32 MFMA; f32
+ * accumulation.  The weight gradient is split over the pixels and the partial sums are combined in split order: two runs agree in
+ * every bit.  cin, cout, ldx, lddy, lddx multiples of 16 bytes, as the forward entry; anything else is UPA_EUNSUPPORTED before the
+ * first launch.  workspace: upa_conv_transpose2x2_bwd_workspace_bytes(cin, cout) bytes. */
+size_t upa_conv_transpose2x2_bwd_workspace_bytes(int cin, int cout);
+int upa_conv_transpose2x2_bwd(const void* x, int n, int h, int w, int cin, int ldx, const void* dy, int cout, int lddy,
+                              const float* weight, void* dx, int lddx, int accumulate_dx, float* dweight, float* dbias,
+                              int accumulate_w, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+/* upa_pack_conv_transpose2x2_weight on the device, from the f32 master weight in device memory (the weights change at every optimizer
+ * step; out: upa_conv_transpose2x2_packed_weight_bytes(cin, cout, dtype) bytes, the same bits as the host packing). */
+int upa_pack_conv_transpose2x2_weight_dev(const float* w, int cin, int cout, int dtype, void* out, void* stream);
+/* The per-anchor assignment inside a workspace that upa_detection_loss / _scaled has filled with (b, n_anchors, max_gt): the address
+ * of anchor (0, 0)'s assigned gt row (-1: background); the next anchor's is 2 words on (assign_stride 2 below). */
+const int32_t* upa_detection_loss_assignment(const void* workspace, int b, int n_anchors, int max_gt);
+/* The mask term of v8SegmentationLoss, forward and gradient (utils/loss.py:622-709 calculate_segmentation_loss + single_mask_loss,
+ * overlap_mask = True; crop_mask's comparison branch, utils/ops.py:510-513).  proto: NHWC (b, mh, mw, nm); coefs[l]: the mask
+ * coefficient map of level l, NHWC (b, hs[l], ws[l], nm), row stride lds[l]; anchors are numbered level by level, row-major, as
+ * upa_detection_loss numbers them.  assign_gt[(b * A + a) * assign_stride] = the gt row of anchor a (-1, or a row >= n_gt[b]:
+ * background); gt / n_gt / max_gt as upa_detection_loss takes them (pixel xyxy); mask_id[b, g] = the value that marks gt row g's
+ * pixels in masks, the (b, mh, mw) uint8 overlap mask (instance ids 0 .. 255, 0 = none).  Per foreground anchor: pred = coef . proto,
+ * BCE-with-logits against masks == mask_id, kept where x >= x1 & x < x2 & y >= y1 & y < y2 for the box in mask units, summed, divided
+ * by mh * mw * (normalised box area); summed over the anchors, divided by the batch's foreground count, times `gain` (hyp.box).
+ * loss_item[0] = that value (0 without a foreground anchor).  dproto (NHWC, row stride lddp) and dcoefs[l] (row stride ldds[l]) are
+ * the gradients of item * b * grad_scale * (*grad_scale_dev, NULL = 1); every element of them is written (rows of background anchors:
+ * zero).  No floating-point atomics: two runs agree in every bit.  A box of zero area divides by zero as the reference does; the
+ * assigner never produces one (an anchor centre must lie strictly inside its box).  nm <= 128, and nm, ldds[l] and the dcoefs[l]
+ * addresses multiples of 16 bytes (background rows are zeroed 16 bytes at a time), else UPA_EUNSUPPORTED before the first launch; proto,
+ * dproto and the coefficient maps are read and written element by element and take any stride >= nm.  dtype: of proto, coefs, dproto, dcoefs. */
+size_t upa_mask_loss_workspace_bytes(int b, int n_anchors);
+int upa_mask_loss(const void* proto, int b, int mh, int mw, int nm, int ldp, const void* const* coefs, void* const* dcoefs,
+                  const int* hs, const int* ws, const int* lds, const int* ldds, int n_levels, const int32_t* assign_gt,
+                  int assign_stride, const float* gt, const int* n_gt, int max_gt, const int32_t* mask_id, const uint8_t* masks,
+                  int imgsz_h, int imgsz_w, float gain, float grad_scale, const float* grad_scale_dev, float* loss_item,
+                  void* dproto, int lddp, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+
 /* ---- segmentation validation: mask IoU and mask true positives on bit masks ----------------------------------------------------
  * Bit layout of every entry below: a mask of mh x mw pixels is words = ceil(mh * mw / 32) uint32, bit k of word w = pixel 32 w + k
  * in row-major order.  Bits past mh * mw in the last word are zero when one of these entries writes them; every reader masks them

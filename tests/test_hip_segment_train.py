@@ -1,0 +1,356 @@
+"""-m gpu: segmentation training.  upa_conv_transpose2x2_bwd and upa_mask_loss through the C ABI against the float64 references of
+tests/segment_train_ref.py (bounds derived from the operands, tests/kernel_check.py; strided views, guard bands, two runs bit for bit);
+whole steps of `SegmentationTrainer` on yolov8n-seg against the imported reference's record (tests/golden/train_yolov8n-seg.npz)."""
+
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from tests import kernel_check as KC
+from tests import segment_train_ref as SR
+from ultralytics_pro_amd.utils import procedural as P
+
+pytestmark = pytest.mark.gpu
+
+BF16, F32 = torch.bfloat16, torch.float32
+U32, U16 = 2.0 ** -24, 2.0 ** -8  # unit roundoffs (half an ulp, relative) of round to nearest: f32 (24-bit significand), bf16 (8-bit)
+CONVT_SHAPES = [(2, 5, 7, 16, 16), (1, 20, 20, 64, 64), (3, 9, 4, 32, 64)]
+
+
+def _es(dtype):
+    return 2 if dtype == BF16 else 4
+
+
+# ---- 1. upa_conv_transpose2x2_bwd -----------------------------------------------------------------------------------------------------
+def _convt_inputs(shape, dtype):
+    n, h, w, cin, cout = shape
+    q = (lambda t: t.to(dtype).float())
+    x = q(P.uniform("ctb:x", (n, h, w, cin), -1.0, 1.0))
+    dy = q(P.uniform("ctb:dy", (n, 2 * h, 2 * w, cout), -1.0, 1.0))
+    wt = q(P.uniform("ctb:w", (cin, cout, 2, 2), -1.0, 1.0))  # representable in bf16: the kernel's rounding of the weight is exact
+    prev = (q(P.uniform("ctb:dx0", (n, h, w, cin), -1.0, 1.0)), P.uniform("ctb:dw0", (cin, cout, 2, 2), -1.0, 1.0),
+            P.uniform("ctb:db0", (cout,), -1.0, 1.0))
+    return x, dy, wt, prev
+
+
+def _convt_run(shape, dtype, accumulate, x, dy, wt, prev):
+    DEV, L, lib, st = KC.env()
+    n, h, w, cin, cout = shape
+    E, es = 16 // _es(dtype), _es(dtype)
+    xb, dyb = KC.slice_buf(x, dtype, E), KC.slice_buf(dy, dtype, E)
+    wd = wt.to(DEV).contiguous()
+    dxb = KC.out_buf((n, h, w), cin + 2 * E, dtype, 1)
+    dwb, dbb = KC.out_buf((1,), wt.numel() + 8, F32, 1), KC.out_buf((1,), cout + 8, F32, 1)
+    if accumulate:
+        dxb[:n, ..., E:E + cin] = prev[0].to(dtype).to(DEV)
+        dwb[0, 4:4 + wt.numel()] = prev[1].reshape(-1).to(DEV)
+        dbb[0, 4:4 + cout] = prev[2].to(DEV)
+    nws = lib.upa_conv_transpose2x2_bwd_workspace_bytes(cin, cout)
+    ws = torch.full((nws + 64,), 0xAB, dtype=torch.uint8, device=DEV)
+    L.check(lib.upa_conv_transpose2x2_bwd(xb.data_ptr() + E * es, n, h, w, cin, cin + 2 * E, dyb.data_ptr() + E * es, cout, cout + 2 * E,
+                                          wd.data_ptr(), dxb.data_ptr() + E * es, cin + 2 * E, int(accumulate), dwb.data_ptr() + 16,
+                                          dbb.data_ptr() + 16, int(accumulate), ws.data_ptr(), nws, L.dtype_code(dtype), st),
+            "conv_transpose2x2_bwd")
+    torch.cuda.synchronize()
+    assert bool((ws[nws:] == 0xAB).all()), "wrote past the workspace"
+    return dxb, dwb, dbb
+
+
+@pytest.mark.parametrize("accumulate", [False, True], ids=["write", "accumulate"])
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("shape", CONVT_SHAPES, ids=lambda s: "x".join(str(v) for v in s))
+@KC.stop_after_fault
+def test_conv_transpose_bwd_matches_float64(shape, dtype, accumulate):
+    """dx, dW, db on strided views with guard bands, two runs bit for bit.  Bounds: products of the (exactly representable) operands are
+    exact in f32; a K-term f32 accumulation in any order errs by at most (K + 8) u32 sum|products| (K = 4 cout for dx, n h w for dW,
+    4 n h w for db; the split-K combine adds at most 64 more terms); plus the rounding of the stored value (bf16 for dx in bf16 mode)
+    and, when accumulating, of the sum with the previous value."""
+    n, h, w, cin, cout = shape
+    x, dy, wt, prev = _convt_inputs(shape, dtype)
+    E = 16 // _es(dtype)
+    (dx, dw, db), (mx, mw_, mb) = SR.convt_bwd_ref(x, dy, wt)
+    runs = [_convt_run(shape, dtype, accumulate, x, dy, wt, prev) for _ in range(2)]
+    got_dx = KC.payload_of_two([r[0] for r in runs], n, cin, "dx", offset=E).double()
+    got_dw = KC.payload_of_two([r[1] for r in runs], 1, wt.numel(), "dw", offset=4).double().reshape(wt.shape)
+    got_db = KC.payload_of_two([r[2] for r in runs], 1, cout, "db", offset=4).double().reshape(-1)
+    p0 = [t.double() if accumulate else torch.zeros_like(t).double() for t in prev]
+    u_out = U16 if dtype == BF16 else U32
+    npix = n * h * w
+    KC.check_bound(got_dx, dx + p0[0], (4 * cout + 8) * U32 * mx + u_out * (dx + p0[0]).abs() + U32 * dx.abs(), f"dx {shape} {dtype}")
+    KC.check_bound(got_dw, dw + p0[1], (npix + 72) * U32 * mw_ + 2 * U32 * (dw.abs() + p0[1].abs()), f"dw {shape} {dtype}")
+    KC.check_bound(got_db, db + p0[2], (4 * npix + 8) * U32 * mb + 2 * U32 * (db.abs() + p0[2].abs()), f"db {shape} {dtype}")
+
+
+@KC.stop_after_fault
+def test_conv_transpose_bwd_refusals_leave_the_outputs_untouched():
+    DEV, L, lib, st = KC.env()
+    n, h, w = 1, 3, 3
+    for dtype, cin, cout, ldx in ((BF16, 12, 16, 16), (BF16, 16, 20, 16), (F32, 16, 16, 18), (F32, 6, 8, 8)):
+        x = torch.zeros(n, h, w, 32, dtype=dtype, device=DEV)
+        dy = torch.zeros(n, 2 * h, 2 * w, 32, dtype=dtype, device=DEV)
+        wt = torch.zeros(cin, cout, 2, 2, device=DEV)
+        dx = KC.out_buf((n, h, w), 32, dtype, 0)
+        dw, db = KC.out_buf((1,), cin * cout * 4, F32, 0), KC.out_buf((1,), cout, F32, 0)
+        ws = torch.zeros(lib.upa_conv_transpose2x2_bwd_workspace_bytes(cin, cout) + 16, dtype=torch.uint8, device=DEV)
+        rc = lib.upa_conv_transpose2x2_bwd(x.data_ptr(), n, h, w, cin, ldx, dy.data_ptr(), cout, 32, wt.data_ptr(), dx.data_ptr(), 32, 0,
+                                           dw.data_ptr(), db.data_ptr(), 0, ws.data_ptr(), ws.numel(), L.dtype_code(dtype), st)
+        torch.cuda.synchronize()
+        assert rc == L.UPA_EUNSUPPORTED, (dtype, cin, cout, ldx, rc)
+        assert all(bool(torch.isnan(t.float()).all()) for t in (dx, dw, db))
+
+
+# ---- 2. upa_mask_loss -----------------------------------------------------------------------------------------------------------------
+def _mask_run(case, dtype, stride=1, nm_arg=None, dev_scale=None):
+    """One call on strided views with guard bands; returns (rc, item buffer, dproto buffer, [dcoef buffers])."""
+    DEV, L, lib, st = KC.env()
+    E, es = 16 // _es(dtype), _es(dtype)
+    proto, coefs = case["proto"], case["coefs"]
+    b, mh, mw, nm = proto.shape
+    nl = len(coefs)
+    pb = KC.slice_buf(proto, dtype, E)
+    cbs = [KC.slice_buf(c, dtype, E) for c in coefs]
+    dpb = KC.out_buf((b, mh, mw), nm + 2 * E, dtype, 1)
+    dcbs = [KC.out_buf(tuple(c.shape[:3]), nm + 2 * E, dtype, 1) for c in coefs]
+    A = sum(c.shape[1] * c.shape[2] for c in coefs)
+    asg = torch.full((b * A * stride + 4,), -7, dtype=torch.int32)
+    asg[:b * A * stride:stride] = case["assign"].reshape(-1)
+    asg = asg.to(DEV)
+    gt, ngt, mid = case["gt"].contiguous().to(DEV), case["n_gt"].to(DEV), case["mask_id"].contiguous().to(DEV)
+    masks = case["masks"].contiguous().to(DEV)
+    item = KC.out_buf((1,), 9, F32, 1)
+    nws = lib.upa_mask_loss_workspace_bytes(b, A)
+    ws = torch.full((nws + 64,), 0xAB, dtype=torch.uint8, device=DEV)
+    FP, IA = C.c_void_p * nl, C.c_int * nl
+    ld = nm + 2 * E
+    gsd = None if dev_scale is None else torch.tensor([dev_scale], dtype=F32, device=DEV)
+    rc = lib.upa_mask_loss(pb.data_ptr() + E * es, b, mh, mw, nm if nm_arg is None else nm_arg, ld,
+                           C.cast(FP(*[t.data_ptr() + E * es for t in cbs]), C.c_void_p),
+                           C.cast(FP(*[t.data_ptr() + E * es for t in dcbs]), C.c_void_p),
+                           C.cast(IA(*[c.shape[1] for c in coefs]), C.c_void_p), C.cast(IA(*[c.shape[2] for c in coefs]), C.c_void_p),
+                           C.cast(IA(*[ld] * nl), C.c_void_p), C.cast(IA(*[ld] * nl), C.c_void_p), nl, asg.data_ptr(), stride,
+                           gt.data_ptr(), ngt.data_ptr(), int(gt.shape[1]), mid.data_ptr(), masks.data_ptr(), case["imgsz_h"],
+                           case["imgsz_w"], case["gain"], case["scale"], None if gsd is None else gsd.data_ptr(), item.data_ptr() + 16, dpb.data_ptr() + E * es, ld,
+                           ws.data_ptr(), nws, L.dtype_code(dtype), st)
+    torch.cuda.synchronize()
+    assert bool((ws[nws:] == 0xAB).all()), "wrote past the workspace"
+    return rc, item, dpb, dcbs
+
+
+def _mask_check(case, dtype, runs, dev_scale=1.0):
+    E = 16 // _es(dtype)
+    b, mh, mw, nm = case["proto"].shape
+    ref = SR.mask_loss_ref(**dict(case, scale=case["scale"] * dev_scale))
+    u_out = U16 if dtype == BF16 else U32
+    item = KC.payload_of_two([r[1] for r in runs], 1, 1, "item", offset=4).double().reshape(())
+    KC.check_bound(item, torch.tensor(ref["item"], dtype=torch.float64), torch.tensor(ref["item_err"] + U32 * abs(ref["item"]),
+                                                                                       dtype=torch.float64), f"item {dtype}")
+    dp = KC.payload_of_two([r[2] for r in runs], b, nm, "dproto", offset=E).double()
+    KC.check_bound(dp, ref["dproto"], ref["dproto_err"] + (u_out + 4 * U32) * ref["dproto"].abs(), f"dproto {dtype}", exact_where_zero=True)
+    for l, want in enumerate(ref["dcoefs"]):
+        dc = KC.payload_of_two([r[3][l] for r in runs], b, nm, f"dcoef[{l}]", offset=E).double()
+        KC.check_bound(dc, want, ref["dcoefs_err"][l] + (u_out + 4 * U32) * want.abs(), f"dcoef[{l}] {dtype}", exact_where_zero=True)
+    return ref
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@KC.stop_after_fault
+def test_mask_loss_matches_float64(dtype):
+    """proto 12 x 20, nm 32, levels 4 x 5 / 2 x 3 / 1 x 2, b = 3 (tests/segment_train_ref.mask_case: an image without foreground, an
+    image with n_gt = 0, two anchors on one gt, a box past the mask edge, a sub-pixel box whose term is exactly 0, mask ids that are not
+    row + 1, overpainted instance ids).  Two runs bit for bit, guard bands intact, bounds from the reference's error model; elements the
+    reference decides to be 0 (background rows, images without foreground, pixels outside every box) are exactly 0."""
+    case = SR.mask_case(dtype=dtype)
+    runs = [_mask_run(case, dtype) for _ in range(2)]
+    assert runs[0][0] == 0 and runs[1][0] == 0
+    ref = _mask_check(case, dtype, runs)
+    assert ref["n_fg"] == 5 and ref["item"] > 0
+    # the assignment read through a stride of 2 words (the detection loss's records): the same bits
+    other = _mask_run(case, dtype, stride=2)
+    assert other[0] == 0 and KC.same_bits(other[1], runs[0][1]) and KC.same_bits(other[2], runs[0][2])
+    assert all(KC.same_bits(a, b) for a, b in zip(other[3], runs[0][3]))
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@KC.stop_after_fault
+def test_mask_loss_gradients_carry_both_scales_and_the_item_neither(dtype):
+    """grad_scale = 3 (a world size) and *grad_scale_dev = 0.375 (a GradScaler's scale, device memory): the gradients are those of
+    item * b * 3 * 0.375 within the same bounds (the extra multiply's rounding is inside the 4 u32 of the stored value), the item is
+    the unscaled one bit for bit."""
+    case = SR.mask_case(dtype=dtype)
+    plain = _mask_run(case, dtype)
+    scaled = dict(case, scale=3.0)
+    runs = [_mask_run(scaled, dtype, dev_scale=0.375) for _ in range(2)]
+    assert plain[0] == 0 and runs[0][0] == 0
+    _mask_check(scaled, dtype, runs, dev_scale=0.375)
+    assert KC.same_bits(runs[0][1], plain[1]) and not KC.same_bits(runs[0][2], plain[2])
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@KC.stop_after_fault
+def test_device_weight_packing_gives_the_host_packing_bits(dtype):
+    """upa_pack_conv_transpose2x2_weight_dev against upa_pack_conv_transpose2x2_weight (host code): every byte, the zero fill of the
+    padded depth included, for a depth that is a multiple of the MFMA depth and one that is not; nothing past the buffer."""
+    DEV, L, lib, st = KC.env()
+    for cin, cout in ((64, 64), (24, 16)):
+        w = P.uniform("ctb:pack", (cin, cout, 2, 2), -1.0, 1.0).contiguous()
+        nb = lib.upa_conv_transpose2x2_packed_weight_bytes(cin, cout, L.dtype_code(dtype))
+        host = torch.full((nb,), 0xCD, dtype=torch.uint8)
+        L.check(lib.upa_pack_conv_transpose2x2_weight(w.data_ptr(), cin, cout, L.dtype_code(dtype), host.data_ptr()), "pack host")
+        dev = torch.full((nb + 64,), 0xCD, dtype=torch.uint8, device=DEV)
+        wd = w.to(DEV)
+        L.check(lib.upa_pack_conv_transpose2x2_weight_dev(wd.data_ptr(), cin, cout, L.dtype_code(dtype), dev.data_ptr(), st), "pack dev")
+        torch.cuda.synchronize()
+        got = dev.cpu()
+        assert torch.equal(got[:nb], host), (cin, cout, dtype)
+        assert bool((got[nb:] == 0xCD).all())
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@KC.stop_after_fault
+def test_mask_loss_without_foreground_is_exactly_zero(dtype):
+    case = SR.mask_case_no_foreground(dtype=dtype)
+    rc, item, dpb, dcbs = _mask_run(case, dtype)
+    E = 16 // _es(dtype)
+    b, _, _, nm = case["proto"].shape
+    assert rc == 0 and float(KC.payload(item, 1, 1, "item", offset=4)) == 0.0
+    assert float(KC.payload(dpb, b, nm, "dproto", offset=E).abs().max()) == 0.0
+    assert all(float(KC.payload(t, b, nm, "dcoef", offset=E).abs().max()) == 0.0 for t in dcbs)
+
+
+@KC.stop_after_fault
+def test_mask_loss_refuses_depths_it_does_not_build():
+    _, L, _, _ = KC.env()
+    case = SR.mask_case(dtype=BF16)
+    for nm_arg in (12, 136):  # not a multiple of 16 bytes in bf16; past 128
+        rc, item, dpb, dcbs = _mask_run(case, BF16, nm_arg=nm_arg)
+        assert rc in (L.UPA_EUNSUPPORTED, L.UPA_EINVAL), (nm_arg, rc)
+        assert all(bool(torch.isnan(t.float()).all()) for t in [item, dpb] + dcbs)
+
+
+# ---- 3. whole steps ---------------------------------------------------------------------------------------------------------------------
+NAME = "yolov8n-seg"
+RAW_KEYS = ["model.22.proto.upsample.weight", "model.22.proto.upsample.bias", "model.22.cv4.0.2.weight"]
+# With the procedural weights the class term dominates the step (item 3417 against 15.7 for seg), so of the new branches only the four
+# widest weights pass the 1e-3-of-the-largest line of the live set; the narrower ones are held by the raw-gradient check (RAW_KEYS,
+# element by element) and by a norm check of their own (SEG_KEYS, the live gate's 2e-2).
+LIVE_SEG = ["model.22.proto.cv1.conv.weight", "model.22.proto.cv2.conv.weight", "model.22.cv4.0.0.conv.weight", "model.22.cv4.0.1.conv.weight"]
+SEG_KEYS = RAW_KEYS + LIVE_SEG + ["model.22.proto.cv3.conv.weight", "model.22.cv4.1.0.conv.weight", "model.22.cv4.1.2.weight"]
+
+
+def _trainer(dtype, **kw):
+    from tests.hip_utils import DEV
+    from ultralytics_pro_amd.engine.trainer import SegmentationTrainer
+    from ultralytics_pro_amd.nn.tasks import SegmentationModel
+    m = SegmentationModel(NAME + ".yaml")
+    P.apply_procedural_weights(m, family=NAME)
+    return m, SegmentationTrainer(m, dtype=dtype, device=DEV, **kw)
+
+
+def _batch(G, step=0):
+    from tests.hip_utils import DEV
+    from tests import segment_train_oracle as ST
+    bs, imgsz, _ = (int(v) for v in G["a_shape"])
+    x, lab = P.synthetic_images(bs, h=imgsz, w=imgsz, seed=step), P.synthetic_labels(bs, seed=step)
+    lab["masks"] = ST.overlap_masks(lab, bs, imgsz // 4, imgsz // 4)
+    return x.to(DEV), lab
+
+
+def _golden_step(golden_dir, dtype):
+    """One step at bs 4, 160 x 160 on the HIP trainer beside the imported reference's record; a dict of figures, nothing asserted."""
+    G = np.load(golden_dir / "train_yolov8n-seg.npz")
+    m, tr = _trainer(dtype)
+    keys = [str(k) for k in G["a_param_keys"]]
+    named = dict(m.named_parameters())
+    assert set(keys) == set(named) - {"model.22.dfl.conv.weight"}
+    x, lab = _batch(G)
+    items = tr.forward_backward(x, lab)
+    norm = tr.grad_norm()
+    torch.cuda.synchronize()
+    f = dict(items=items.cpu().numpy(), ref_items=G["a_loss_items_0"], norm=norm, ref_norm=float(G["a_grad_norm_0"][0]))
+    coef = min(1.0, 10.0 / (f["ref_norm"] + 1e-6))
+    l2 = np.array([float(named[k].grad.double().norm()) * coef for k in keys])
+    ref_l2 = G["a_grad_l2_0"]
+    big = ref_l2 > 1e-3 * ref_l2.max()
+    f["live"] = [k for k, v in zip(keys, big) if v]
+    f["l2"], f["ref_l2"] = l2[big], ref_l2[big]
+    f["l2_rel"] = np.abs(l2[big] - ref_l2[big]) / ref_l2[big]
+    at = {k: i for i, k in enumerate(keys)}
+    f["seg_l2"], f["ref_seg_l2"] = np.array([l2[at[k]] for k in SEG_KEYS]), np.array([ref_l2[at[k]] for k in SEG_KEYS])
+    f["raw"] = {}
+    for k in RAW_KEYS:
+        want = G[f"a_grad[{k}]_0"]
+        f["raw"][k] = float(np.abs(named[k].grad.cpu().numpy() * coef - want).max() / np.abs(want).max())
+    tr.optimizer_step()
+    torch.cuda.synchronize()
+    sd = m.state_dict()
+    f["w_stem"], f["ref_w_stem"] = sd["model.0.conv.weight"].cpu().numpy(), G["a_w_stem_0"]
+    fk = [str(k) for k in G["a_state_keys"]]
+    ema = tr.ema_state_dict()
+    f["ema_sum"], f["ref_ema_sum"] = np.array([float(ema[k].double().sum()) for k in fk]), G["a_ema_sum_0"]
+    items_rel = np.abs(f["items"] - f["ref_items"]) / np.abs(f["ref_items"])
+    f["items_rel"] = items_rel
+    print(f"golden a {dtype}: items {f['items']} vs {f['ref_items']} (rel {items_rel.max():.3e}), norm {norm:.5f} vs {f['ref_norm']:.5f} "
+          f"(rel {abs(norm - f['ref_norm']) / f['ref_norm']:.3e}), per-parameter norm error max {f['l2_rel'].max():.3e} median "
+          f"{np.median(f['l2_rel']):.3e}, raw gradients elementwise max {max(f['raw'].values()):.3e}")
+    return f
+
+
+@KC.stop_after_fault
+def test_training_step_matches_reference_golden_f32(golden_dir):
+    """One step at bs 4, 160 x 160 against the imported reference's record, f32, the gates of tests/test_hip_yolo11_train.py: items
+    2e-3, norm 3e-3, per-parameter norms 2e-2 on the live parameters, raw gradients 5e-3 of the largest element, stem weight 2e-5, EMA
+    sums 1e-3 / 1e-2; the live set holds Proto and cv4 parameters (LIVE_SEG), so the gates do look at the new branches, and the narrower
+    seg parameters get the same norm gate (SEG_KEYS)."""
+    f = _golden_step(golden_dir, F32)
+    np.testing.assert_allclose(f["items"], f["ref_items"], rtol=2e-3)
+    assert abs(f["norm"] - f["ref_norm"]) <= 3e-3 * f["ref_norm"]
+    assert set(LIVE_SEG) <= set(f["live"]), sorted(set(LIVE_SEG) - set(f["live"]))
+    np.testing.assert_allclose(f["l2"], f["ref_l2"], rtol=2e-2)
+    assert bool((f["ref_seg_l2"] > 0).all())
+    np.testing.assert_allclose(f["seg_l2"], f["ref_seg_l2"], rtol=2e-2)
+    assert max(f["raw"].values()) <= 5e-3, f["raw"]
+    np.testing.assert_allclose(f["w_stem"], f["ref_w_stem"], rtol=0, atol=2e-5)
+    np.testing.assert_allclose(f["ema_sum"], f["ref_ema_sum"], rtol=1e-3, atol=1e-2)
+
+
+# bf16 whole step against the imported reference's f32 record (never against the f32 HIP run).  Measured on one MI355X, the same figures
+# in two runs: loss items box 2.84e-3, seg 5.85e-2, cls 9.25e-2, dfl 8.17e-3; gradient norm 1.250e-1; median
+# per-parameter norm error 8.45e-2; the seg parameters' norms (SEG_KEYS) 1.98e-1 at worst; the raw ConvTranspose / cv4.0.2 gradients
+# element by element 4.90e-1 of the largest element.  Every gate is twice its own measured figure, the margin of every bf16 whole-step
+# gate in this project - each loss item has its own, so the seg item is not gated at the class term's distance.  With the class term at
+# 3417 against 15.7 the norm and median gates barely see the new branches: the seg item, the seg norms and the raw gradients do.
+# No assignment tie at this shape: the f32 run follows the record to 2e-6 with label seed 0.
+BF16_GOLDEN = dict(items=np.array([5.7e-3, 1.17e-1, 1.85e-1, 1.64e-2]), norm=2.5e-1, median=1.69e-1, seg_l2=3.96e-1, raw=9.8e-1)
+
+
+@KC.stop_after_fault
+def test_training_step_matches_reference_golden_bf16(golden_dir):
+    f = _golden_step(golden_dir, BF16)
+    assert bool((f["items_rel"] <= BF16_GOLDEN["items"]).all()), f["items_rel"]
+    assert abs(f["norm"] - f["ref_norm"]) <= BF16_GOLDEN["norm"] * f["ref_norm"], (f["norm"], f["ref_norm"])
+    assert np.median(f["l2_rel"]) <= BF16_GOLDEN["median"], np.median(f["l2_rel"])
+    assert set(LIVE_SEG) <= set(f["live"])
+    seg_rel = np.abs(f["seg_l2"] - f["ref_seg_l2"]) / f["ref_seg_l2"]
+    assert seg_rel.max() <= BF16_GOLDEN["seg_l2"], dict(zip(SEG_KEYS, seg_rel))
+    assert max(f["raw"].values()) <= BF16_GOLDEN["raw"], f["raw"]
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@KC.stop_after_fault
+def test_compiled_step_equals_eager(golden_dir, dtype):
+    """The hipGraph replay follows the eager step bit for bit in the loss items, the flat gradient buffer and the parameters."""
+    G = np.load(golden_dir / "train_yolov8n-seg.npz")
+    x, lab = _batch(G)
+    runs = []
+    for mode in ("eager", "compiled"):
+        m, tr = _trainer(dtype)
+        tr.step(x, lab)
+        if mode == "compiled":
+            tr.compile(x, lab, warm_steps=0)
+        items = tr.step(x, lab).cpu().clone()
+        torch.cuda.synchronize()
+        runs.append((items, tr.G.cpu().clone(), tr.P.cpu().clone()))
+    assert tuple(runs[0][0].shape) == (4,) and bool(torch.isfinite(runs[0][0]).all()) and float(runs[0][0][1]) > 0
+    assert all(KC.same_bits(a, b) for a, b in zip(runs[0], runs[1]))

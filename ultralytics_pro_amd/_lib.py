@@ -235,6 +235,13 @@ PROTOTYPES = {
     "upa_crop_mask": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "upa_resize_bilinear": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "upa_copy_rows": (_i, [_vp, C.c_long, _i, C.c_long, _vp, C.c_long, _vp]),
+    "upa_pack_conv_transpose2x2_weight_dev": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "upa_conv_transpose2x2_bwd_workspace_bytes": (_sz, [_i, _i]),
+    "upa_conv_transpose2x2_bwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _sz, _i, _vp]),
+    "upa_detection_loss_assignment": (_vp, [_vp, _i, _i, _i]),
+    "upa_mask_loss_workspace_bytes": (_sz, [_i, _i]),
+    "upa_mask_loss": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _vp,
+                           _vp, _vp, _i, _vp, _sz, _i, _vp]),
     "upa_pack_mask_bits": (_i, [_vp, _i, _i, C.c_long, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "upa_mask_iou_bits": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _f, _vp, _vp]),
     "upa_segment_match_workspace_bytes": (_sz, [_i, _i]),

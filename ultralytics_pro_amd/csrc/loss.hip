@@ -491,9 +491,42 @@ __global__ void loss_finish_kernel(const double* sums, const double* tss, float 
 
 }  // namespace
 
+// The one statement of the workspace's layout: scalars ([0] tss, [1..3] sums f64, then n_fg) in the first 64 bytes, pbox (B*A*4 f32),
+// cand (B*max_gt*TOPK i32), assign (B*A records), count (B*A i32).  Returns the size; fills `out` when a base is given.
+struct LossWs {
+  double* scal;
+  int* n_fg;
+  float* pbox;
+  int* cand;
+  Assign* asg;
+  int* count;
+};
+static size_t loss_ws_layout(int b, int a, int max_gt, char* base, LossWs* out) {
+  size_t off = 64;
+  const size_t o_pbox = off;  off += (size_t)b * a * 4 * sizeof(float);
+  const size_t o_cand = off;  off += (size_t)b * max_gt * TOPK * sizeof(int);
+  const size_t o_asg = off;   off += (size_t)b * a * sizeof(Assign);
+  const size_t o_count = off; off += (size_t)b * a * sizeof(int);
+  if (out) {
+    out->scal = (double*)base; out->n_fg = (int*)(out->scal + 4);
+    out->pbox = (float*)(base + o_pbox); out->cand = (int*)(base + o_cand); out->asg = (Assign*)(base + o_asg);
+    out->count = (int*)(base + o_count);
+  }
+  return off;
+}
+
 extern "C" size_t upa_detection_loss_workspace_bytes(int b, int a, int max_gt) {
-  // pbox (B*A*4 f32) + cand (B*max_gt*TOPK i32) + assign (B*A*8) + count (B*A i32) + scalars (tss, sums[3] f64, n_fg)
-  return (size_t)b * a * 16 + (size_t)b * max_gt * TOPK * 4 + (size_t)b * a * 8 + (size_t)b * a * 4 + 64;
+  return loss_ws_layout(b, a, max_gt, nullptr, nullptr);
+}
+
+// The per-anchor assignment inside a workspace upa_detection_loss* has filled: [b][a] records {int gt (-1: background); float score},
+// returned as the address of the first record's `gt` (a stride of 2 words) - what upa_mask_loss reads in place.
+extern "C" const int32_t* upa_detection_loss_assignment(const void* workspace, int b, int a, int max_gt) {
+  static_assert(sizeof(Assign) == 8 && offsetof(Assign, gt) == 0, "upa_detection_loss_assignment: stride 2, gt first");
+  if (!workspace || b <= 0 || a <= 0 || max_gt <= 0) return nullptr;
+  LossWs W;
+  loss_ws_layout(b, a, max_gt, (char*)workspace, &W);
+  return (const int32_t*)W.asg;
 }
 
 extern "C" int upa_detection_loss_scaled(const float* const* feats, float* const* grads, const int* hs, const int* ws, const int* lds_,
@@ -541,12 +574,14 @@ extern "C" int upa_detection_loss_scaled(const float* const* feats, float* const
     return UPA_ELAUNCH;
   }
   char* wsb = (char*)workspace;
-  double* scal = (double*)wsb;                // [0] tss, [1..3] sums, then n_fg
-  int* n_fg = (int*)(scal + 4);
-  float* pbox = (float*)(wsb + 64);
-  int* cand = (int*)(pbox + (size_t)b * a * 4);
-  Assign* asg = (Assign*)(cand + (size_t)b * max_gt * TOPK);
-  int* count = (int*)(asg + (size_t)b * a);
+  LossWs W;
+  loss_ws_layout(b, a, max_gt, wsb, &W);
+  double* scal = W.scal;
+  int* n_fg = W.n_fg;
+  float* pbox = W.pbox;
+  int* cand = W.cand;
+  Assign* asg = W.asg;
+  int* count = W.count;
   hipStream_t s = (hipStream_t)stream;
   upa_zero_words(wsb, 16, s);  // not hipMemsetAsync: see upa_zero_words (common.h)
   const long total = (long)b * a;

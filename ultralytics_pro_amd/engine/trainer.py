@@ -24,6 +24,11 @@ without it.
 `ClassificationTrainer` is the same step with another tail (`_tail_op`): `ClassifyT` = the train-mode Classify head, global average
 pool, exact-f32 linear, fused cross-entropy (v8ClassificationLoss, utils/loss.py:873-880) and their backward (include/upa.h, "image
 classification training").
+
+`SegmentationTrainer` is the detection step with the tail `SegmentT` = `DetectT` + the cv4 mask-coefficient chains + `ProtoT` (`ConvTransposeT`:
+upa_conv_transpose2x2 / upa_conv_transpose2x2_bwd) and the mask term of v8SegmentationLoss (utils/loss.py:531-709) as upa_mask_loss on the
+detection loss's per-anchor assignment (include/upa.h, "segmentation training"); the labels carry the overlap mask and `pack_mask_ids` maps the
+kept gt rows to the values that mark them in it.
 """
 
 from __future__ import annotations
@@ -977,13 +982,16 @@ class DetectionTrainer:
     `optimizer`: "SGD" (default: SGD-Nesterov), "Adam", "AdamW" (lr and beta1 = `momentum` from `hyp`, plus `beta2`, `adam_eps`) or
     "auto" with `iterations` (`resolve_optimizer`); `optimizer_name` is the resolved one."""
 
+    _segment_ok = False  # (SegmentationTrainer: True)
+
     def __init__(self, model, dtype=torch.bfloat16, hyp=None, device=None, world_size=1, ema=True, wgrad_streams: int = 1,
                  amp_scaler: bool = False, optimizer: str = "SGD", iterations=None, yolo11: bool = False):
         self.optimizer_name, opt_hyp, self._auto_optimizer = resolve_optimizer(
             optimizer, iterations, _head_nc(model) if str(optimizer).lower() == "auto" and iterations is not None else 0)
         # the non-legacy Detect head (YOLO11: depthwise class branch, `DWConvT`) trains on request only: `yolo11=True`
-        if any(isinstance(m, H.Segment) for m in model.modules()):
-            raise L.UpaError("segmentation models (Segment head) have no training path on HIP: v8SegmentationLoss is out of scope")
+        if not self._segment_ok and any(isinstance(m, H.Segment) for m in model.modules()):
+            raise L.UpaError("segmentation models (Segment head) have no training path on HIP in DetectionTrainer (v8DetectionLoss only): "
+                             "train them with SegmentationTrainer")
         for m in model.modules():
             if isinstance(m, H.Detect) and not m.legacy_cls:
                 if not yolo11:
@@ -1192,8 +1200,8 @@ class DetectionTrainer:
         L.check(L.lib().upa_pack_conv_weights_batched(self._pack_table.data_ptr(), self._pack_n, _s(self.device)), "pack_batched")
 
     def forward_backward(self, img, labels):
-        """img: (N,3,H,W) float32 NCHW on the device; labels: the reference's batch dict (batch_idx, cls, bboxes).
-        Fills the flat gradient buffer; returns loss_items (3,) on the device."""
+        """img: (N,3,H,W) float32 NCHW on the device; labels: the reference's batch dict (batch_idx, cls, bboxes; `SegmentationTrainer`: masks
+        as well).  Fills the flat gradient buffer; returns loss_items on the device ((3,) box, cls, dfl; `SegmentationTrainer`: (4,) box, seg, cls, dfl)."""
         ctx, dev = self.ctx, self.device
         L.require_gpu(img, "train")
         self.model.train()
@@ -1696,6 +1704,7 @@ class DetectT(_Seq):
                 L.check(L.lib().upa_cast_view(vs.ptr, vs.dtype, vs.ld, vd.ptr, vd.dtype, vd.ld, vs.n * vs.h * vs.w, vs.c,
                                               _s(dev)), "cast_view")
                 self.raw32[i] = r32
+            self._level_more(i, x)
 
         # The levels are independent chains (head.py:116-126).  The 40 x 40 / 20 x 20 levels are strings of 5-15 us launches (a few
         # hundred workgroups each): on a second stream they run beside the 80 x 80 level's chip-filling launches instead of after them.
@@ -1725,6 +1734,17 @@ class DetectT(_Seq):
         main.wait_event(done)
 
     fork_levels = True  # (False: every level on the main stream, as before round 5 - the A/B switch)
+
+    # the hooks of a head with more branches on the same level inputs (`SegmentT`)
+    def _level_more(self, i, x):
+        """Further train-mode branches of level i's input x, run on that level's stream."""
+
+    def _more_losses(self, items, wsb, batch_size, n_anchors, max_gt):
+        """Further loss terms on the detection loss's workspace (its per-anchor assignment); returns the step's loss items."""
+        return items
+
+    def _level_more_bwd(self, i, dx):
+        """Backward of `_level_more`'s branches, accumulated into dx (level i's input gradient, already written)."""
 
     def loss_backward(self, labels, batch_size):
         """v8DetectionLoss (utils/loss.py:471-528) + gradient; then backward through the head into the neck outputs."""
@@ -1761,6 +1781,7 @@ class DetectT(_Seq):
                                               batch_size, self.nc, self.reg_max, gt_d.data_ptr(), ngt_d.data_ptr(), max_gt,
                                               h["box"], h["cls"], h["dfl"], 1.0, tr.scaler.ptr(), items.data_ptr(), wsb.data_ptr(),
                                               nbytes, _s(dev)), "detection_loss")
+        items = self._more_losses(items, wsb, batch_size, A, max_gt)
         nb = 4 * self.reg_max
 
         def level_bwd(i):
@@ -1784,10 +1805,23 @@ class DetectT(_Seq):
                     seq[j].backward(g, d, False)
                     g = d
                 seq[0].backward(g, dx, acc or k > 0)
+            self._level_more_bwd(i, dx)
 
         # as in the forward pass: the small levels' chains beside the 80 x 80 level's (they write the gradients of different neck outputs)
         self._fork_levels(lambda: level_bwd(0), lambda: [level_bwd(i) for i in range(1, nl)], nl > 1)
         return items
+
+
+def _pixel_boxes(labels, imgsz_h, imgsz_w):
+    """(image index (n,), pixel xyxy (n, 4), keep (n,)) of a batch's labels: keep = the boxes whose xyxy coordinates do not sum to zero,
+    the reference's `mask_gt` (loss.py:489).  The one statement of that rule for `pack_targets` and `pack_mask_ids`."""
+    bi = labels["batch_idx"].view(-1).cpu().long()
+    bb = labels["bboxes"].view(-1, 4).cpu().float()
+    scale = torch.tensor([imgsz_w, imgsz_h, imgsz_w, imgsz_h], dtype=torch.float32)
+    xywh = bb * scale
+    xy, wh = xywh[:, :2], xywh[:, 2:] / 2
+    xyxy = torch.cat([xy - wh, xy + wh], 1)
+    return bi, xyxy, xyxy.sum(1) > 0
 
 
 def pack_targets(labels, batch_size, imgsz_h, imgsz_w, min_rows=MAX_GT, nc=None):
@@ -1797,14 +1831,8 @@ def pack_targets(labels, batch_size, imgsz_h, imgsz_w, min_rows=MAX_GT, nc=None)
     whose xyxy coordinates sum to zero are dropped: the reference masks them (`mask_gt = gt_bboxes.sum(2) > 0`,
     loss.py:489), so they never take part in the assignment.  With `nc` given, a class id outside [0, nc) is refused here: the
     kernels index the class logits with it unchecked (the reference fails on the host with an index error)."""
-    bi = labels["batch_idx"].view(-1).cpu().long()
     cls = labels["cls"].view(-1).cpu().float()
-    bb = labels["bboxes"].view(-1, 4).cpu().float()
-    scale = torch.tensor([imgsz_w, imgsz_h, imgsz_w, imgsz_h], dtype=torch.float32)
-    xywh = bb * scale
-    xy, wh = xywh[:, :2], xywh[:, 2:] / 2
-    xyxy = torch.cat([xy - wh, xy + wh], 1)
-    keep = xyxy.sum(1) > 0
+    bi, xyxy, keep = _pixel_boxes(labels, imgsz_h, imgsz_w)
     if nc is not None and bool(((cls < 0) | (cls >= nc)).any()):
         bad = cls[(cls < 0) | (cls >= nc)]
         raise L.UpaError(f"label class {float(bad[0]):g} is outside [0, {nc}) of the model's classes")
@@ -1822,6 +1850,178 @@ def pack_targets(labels, batch_size, imgsz_h, imgsz_w, min_rows=MAX_GT, nc=None)
             gt[j, :k, 1:] = xyxy[ix]
         ngt[j] = k
     return gt, ngt
+
+
+def pack_mask_ids(labels, batch_size, imgsz_h, imgsz_w, rows):
+    """The sibling of `pack_targets` for the overlap mask: (B, rows) int32, for every gt row `pack_targets` keeps the value that marks
+    its instance in `batch["masks"]` = the label's position within its image + 1 (0 in the unused rows).  The reference keeps the boxes
+    `pack_targets` drops as rows of zeros and only masks them (loss.py:445-461, :563), so its `target_gt_idx + 1` (loss.py:696) is the
+    ORIGINAL position; a row index of the compacted rows would be off by the number of dropped boxes in front of it."""
+    bi, _, keep = _pixel_boxes(labels, imgsz_h, imgsz_w)
+    mid = torch.zeros(batch_size, rows, dtype=torch.int32)
+    for j in range(batch_size):
+        pos = (bi == j).nonzero().view(-1)          # the image's labels in batch order: position p <-> mask value p + 1
+        kept = keep[pos].nonzero().view(-1)
+        if kept.numel() > rows:
+            raise L.UpaError(f"image {j} keeps {int(kept.numel())} boxes but the gt rows hold {rows}")
+        mid[j, :kept.numel()] = (kept + 1).to(torch.int32)
+    return mid
+
+
+MASK_ID_MAX = 255  # upa_mask_loss reads the overlap mask as uint8 (the reference's dataset builds it as uint8 as well, data/utils.py)
+
+
+class ConvTransposeT:
+    """Train-mode nn.ConvTranspose2d(c_, c_, 2, 2, 0, bias=True), Proto's upsample (block.py:257-276): upa_conv_transpose2x2 with the
+    weight packed on the device from the f32 master weight (`pack_phase_weights`, once per step with every other repack), and
+    upa_conv_transpose2x2_bwd (dx, dW, db).  The `ConvT` surface for the trainer's repack hooks."""
+
+    @staticmethod
+    def check(m, name):
+        if not (isinstance(m, nn.ConvTranspose2d) and m.kernel_size == (2, 2) and m.stride == (2, 2) and m.padding == (0, 0)
+                and m.output_padding == (0, 0) and m.groups == 1 and m.dilation == (1, 1) and m.bias is not None):
+            raise L.UpaError(f"{name}: training supports ConvTranspose2d(k 2, stride 2, pad 0, groups 1, bias=True) only")
+
+    def __init__(self, ctx: _Ctx, m: nn.ConvTranspose2d, name: str):
+        self.check(m, name)
+        self.ctx, self.m, self.name = ctx, m, name
+        self.cin, self.cout = m.in_channels, m.out_channels
+        lib = L.lib()
+        self.wp = torch.empty(lib.upa_conv_transpose2x2_packed_weight_bytes(self.cin, self.cout, ctx.code), dtype=torch.uint8, device=ctx.device)
+        self.nws = lib.upa_conv_transpose2x2_bwd_workspace_bytes(self.cin, self.cout)
+        self.ws = torch.empty(self.nws, dtype=torch.uint8, device=ctx.device)
+        self.x = None
+
+    def convs(self):
+        return [self]
+
+    def pack(self):
+        c = self.ctx
+        L.check(L.lib().upa_pack_conv_transpose2x2_weight_dev(self.m.weight.data_ptr(), self.cin, self.cout, c.code, self.wp.data_ptr(),
+                                                              _s(c.device)), f"pack_conv_transpose[{self.name}]")
+
+    pack_phase_weights = pack  # (the per-step hook `_pack_weights` calls on every op before the batched repack)
+
+    def pack_descs(self):
+        return []
+
+    def forward(self, x, out=None):
+        c = self.ctx
+        n, _, h, w = x.shape
+        self.x = x
+        y = out if out is not None else _new(n, self.cout, 2 * h, 2 * w, c.dtype, c.device, (id(self), "y"))
+        vx, vy = R.view_of(x), R.view_of(y)
+        L.check(L.lib().upa_conv_transpose2x2(vx.ptr, vx.n, vx.h, vx.w, vx.c, vx.ld, self.wp.data_ptr(), self.m.bias.data_ptr(), vy.ptr,
+                                              self.cout, vy.ld, vx.dtype, _s(c.device)), f"conv_transpose2x2[{self.name}]")
+        return y
+
+    def backward(self, dy, dx=None, accumulate=False):
+        c = self.ctx
+        vx, vdy = R.view_of(self.x), R.view_of(dy)
+        vdx = None if dx is None else R.view_of(dx)
+        L.check(L.lib().upa_conv_transpose2x2_bwd(vx.ptr, vx.n, vx.h, vx.w, vx.c, vx.ld, vdy.ptr, self.cout, vdy.ld, self.m.weight.data_ptr(),
+                                                  None if dx is None else vdx.ptr, 0 if dx is None else vdx.ld, int(accumulate),
+                                                  self.m.weight.grad.data_ptr(), self.m.bias.grad.data_ptr(), 1, self.ws.data_ptr(), self.nws,
+                                                  vx.dtype, _s(c.device)), f"conv_transpose2x2_bwd[{self.name}]")
+
+
+class ProtoT(_Seq):
+    """Train-mode Proto (block.py:257-276): cv3(cv2(upsample(cv1(x))))."""
+
+    def __init__(self, ctx, m: B.Proto, name):
+        super().__init__(ctx)
+        self.cv1 = ConvT(ctx, m.cv1.conv, m.cv1.bn, m.cv1._act_code(), name + ".cv1")
+        self.up = ConvTransposeT(ctx, m.upsample, name + ".upsample")
+        self.cv2 = ConvT(ctx, m.cv2.conv, m.cv2.bn, m.cv2._act_code(), name + ".cv2")
+        self.cv3 = ConvT(ctx, m.cv3.conv, m.cv3.bn, m.cv3._act_code(), name + ".cv3")
+
+    def convs(self):
+        return [self.cv1, self.up, self.cv2, self.cv3]
+
+    def forward(self, x, out=None):
+        return self.cv3.forward(self.cv2.forward(self.up.forward(self.cv1.forward(x))), out=out)
+
+    def backward(self, dy, dx, accumulate):
+        c = self.ctx
+        g = dy
+        for i, op in ((3, self.cv3), (2, self.cv2), (1, self.up)):
+            vt = R.view_of(op.x)
+            d = _new(vt.n, vt.c, vt.h, vt.w, c.dtype, c.device, (id(self), "d", i))
+            op.backward(g, d, False)
+            g = d
+        self.cv1.backward(g, dx, accumulate)
+
+
+class SegmentT(DetectT):
+    """Train-mode Segment (head.py:790-837 returns the raw maps, the mask coefficients and the prototypes) + v8SegmentationLoss
+    (utils/loss.py:531-709) + its gradient: `DetectT` with, per level, the cv4 chain (Conv 3x3, Conv 3x3, Conv2d 1x1 -> nm) and, on
+    level 0's input, `ProtoT`.  The mask term is upa_mask_loss on the detection loss's workspace (the per-anchor assignment is read in
+    place); cv4 and Proto backpropagate into the same neck gradients as cv2 / cv3.  Loss items: (box, seg, cls, dfl)."""
+
+    def __init__(self, ctx, m: H.Segment, name, trainer):
+        super().__init__(ctx, m, name, trainer)
+        self.nm = m.nm
+        self.cv4 = [[ConvT(ctx, seq[0].conv, seq[0].bn, seq[0]._act_code(), f"{name}.cv4.{i}.0"),
+                     ConvT(ctx, seq[1].conv, seq[1].bn, seq[1]._act_code(), f"{name}.cv4.{i}.1"),
+                     ConvT(ctx, seq[2], None, L.ACT_NONE, f"{name}.cv4.{i}.2")] for i, seq in enumerate(m.cv4)]
+        self.proto = ProtoT(ctx, m.proto, name + ".proto")
+        self.mc = [None] * m.nl
+        self.p = None
+
+    def convs(self):
+        return super().convs() + [cv for seq in self.cv4 for cv in seq] + self.proto.convs()
+
+    def _level_more(self, i, x):
+        t = x
+        for op in self.cv4[i]:
+            t = op.forward(t)
+        self.mc[i] = t
+        if i == 0:
+            self.p = self.proto.forward(x)
+
+    def _more_losses(self, items, wsb, batch_size, n_anchors, max_gt):
+        c, tr, lib = self.ctx, self.tr, L.lib()
+        dev = c.device
+        nl = self.nl
+        vp = R.view_of(self.p)
+        self.dmc = [_new(*[int(v) for v in t.shape], c.dtype, dev, (id(self), "dmc", i)) for i, t in enumerate(self.mc)]
+        self.dp = _new(vp.n, vp.c, vp.h, vp.w, c.dtype, dev, (id(self), "dproto"))
+        vdp = R.view_of(self.dp)
+        vm, vd = [R.view_of(t) for t in self.mc], [R.view_of(t) for t in self.dmc]
+        FP, IA = C.c_void_p * nl, C.c_int * nl
+        coefs, dcoefs = FP(*[v.ptr for v in vm]), FP(*[v.ptr for v in vd])
+        hs, ws = IA(*[v.h for v in vm]), IA(*[v.w for v in vm])
+        lds, ldds = IA(*[v.ld for v in vm]), IA(*[v.ld for v in vd])
+        masks_d, mid_d = tr.masks_d, tr.mid_d
+        if tuple(masks_d.shape) != (batch_size, vp.h, vp.w) or tuple(mid_d.shape) != (batch_size, max_gt):
+            raise L.UpaError(f"mask buffers {tuple(masks_d.shape)} / {tuple(mid_d.shape)} do not match the step: prototypes "
+                             f"{(batch_size, vp.h, vp.w)}, gt rows {(batch_size, max_gt)}")
+        asg = lib.upa_detection_loss_assignment(wsb.data_ptr(), batch_size, n_anchors, max_gt)
+        nws = lib.upa_mask_loss_workspace_bytes(batch_size, n_anchors)
+        mws = tr.pool.get(("mask_loss_ws", batch_size, n_anchors), (nws,), torch.uint8, dev)
+        items4 = tr.pool.get(("loss_items4",), (4,), torch.float32, dev)
+        imgsz_h, imgsz_w = tr._imgsz
+        L.check(lib.upa_mask_loss(vp.ptr, batch_size, vp.h, vp.w, self.nm, vp.ld, C.cast(coefs, C.c_void_p), C.cast(dcoefs, C.c_void_p),
+                                  C.cast(hs, C.c_void_p), C.cast(ws, C.c_void_p), C.cast(lds, C.c_void_p), C.cast(ldds, C.c_void_p), nl,
+                                  asg, 2, tr.gt_d.data_ptr(), tr.ngt_d.data_ptr(), max_gt, mid_d.data_ptr(), masks_d.data_ptr(),
+                                  imgsz_h, imgsz_w, tr.hyp["box"], 1.0, tr.scaler.ptr(), items4.data_ptr() + 4, vdp.ptr, vdp.ld,
+                                  mws.data_ptr(), nws, c.code, _s(dev)), "mask_loss")
+        # (box, seg, cls, dfl), loss.py:541: box and [cls, dfl] of the detection items around the seg item written above
+        L.check(lib.upa_copy_rows(items.data_ptr(), 1, 1, 3, items4.data_ptr(), 4, _s(dev)), "copy_rows")
+        L.check(lib.upa_copy_rows(items.data_ptr() + 4, 1, 2, 3, items4.data_ptr() + 8, 4, _s(dev)), "copy_rows")
+        return items4
+
+    def _level_more_bwd(self, i, dx):
+        c = self.ctx
+        seq, g = self.cv4[i], self.dmc[i]
+        for j in range(len(seq) - 1, 0, -1):
+            vt = R.view_of(seq[j].x)
+            d = _new(vt.n, vt.c, vt.h, vt.w, c.dtype, c.device, (id(self), "d4", i, j))
+            seq[j].backward(g, d, False)
+            g = d
+        seq[0].backward(g, dx, True)
+        if i == 0:
+            self.proto.backward(self.dp, dx, True)
 
 
 class ClassifyT(_Seq):
@@ -2007,3 +2207,99 @@ class ClassificationTrainer(DetectionTrainer):
         self.cls_d.copy_(ent[0], non_blocking=True)
         ent[1] = torch.cuda.Event()
         ent[1].record(torch.cuda.current_stream(self.device))
+
+
+class SegmentationTrainer(DetectionTrainer):
+    """One-process-per-GPU trainer for a SegmentationModel (reference: models/yolo/segment/train.py on engine/trainer.py's loop; the loss
+    is v8SegmentationLoss, utils/loss.py:531-709).  Everything but the tail and the labels is DetectionTrainer's: the graph walk, `step`,
+    `compile` / replay, `set_schedule`, every optimizer, GradScaler, EMA and the multi-rank path.  The tail is `SegmentT`; the labels
+    additionally carry `"masks"`, the (B, mh, mw) overlap mask at prototype resolution (instance p of an image painted as p + 1, later
+    instances over earlier ones - what the reference's dataset delivers with overlap_mask=True, mask_ratio=4).  `step()` returns the
+    (4,) loss items (box, seg, cls, dfl).
+    Refused, by the constructor or the label upload, before any launch: overlap_mask=False (per-instance mask stacks); masks that are not
+    at prototype resolution (the reference's F.interpolate fallback, loss.py:604-605, is not built); instance ids above 255 (the mask is
+    read as uint8); a YOLO11 Segment head (depthwise class branch), with or without yolo11=True."""
+
+    _segment_ok = True
+
+    def __init__(self, model, dtype=torch.bfloat16, hyp=None, device=None, world_size=1, ema=True, wgrad_streams: int = 1,
+                 amp_scaler: bool = False, optimizer: str = "SGD", iterations=None, yolo11: bool = False, overlap_mask: bool = True):
+        tail = model.model[-1] if hasattr(model, "model") and len(model.model) else None
+        if not isinstance(tail, H.Segment):
+            raise L.UpaError(f"SegmentationTrainer needs a model that ends in a Segment head, got {type(tail).__name__}")
+        if not overlap_mask:
+            raise L.UpaError("overlap_mask=False (one mask plane per instance) has no training path on HIP: the mask loss reads the "
+                             "overlap mask (overlap_mask=True, the reference's default)")
+        if not tail.legacy_cls:
+            if not yolo11:
+                raise L.UpaError("Segment (YOLO11, non-legacy head with a depthwise class branch) has no training path on HIP unless it is "
+                                 "asked for with yolo11=True - and SegmentationTrainer does not build it yet")
+            raise L.UpaError("Segment (YOLO11, non-legacy head with a depthwise class branch): SegmentationTrainer builds the yolov8 "
+                             "Segment head only")
+        ConvTransposeT.check(tail.proto.upsample, f"model.{getattr(tail, 'i', '?')}.proto.upsample")
+        self.masks_d = self.mid_d = None
+        super().__init__(model, dtype=dtype, hyp=hyp, device=device, world_size=world_size, ema=ema, wgrad_streams=wgrad_streams,
+                         amp_scaler=amp_scaler, optimizer=optimizer, iterations=iterations, yolo11=yolo11)
+
+    def _tail_op(self, m, name):
+        if isinstance(m, H.Segment):
+            return SegmentT(self.ctx, m, name, self), "detect"
+        return None
+
+    @staticmethod
+    def check_masks(labels, batch_size, mh, mw):
+        """The refusals of the label upload, on the host: returns the (B, mh, mw) uint8 overlap mask."""
+        if not isinstance(labels, dict) or "masks" not in labels:
+            raise L.UpaError('segmentation labels need "masks": the (B, mh, mw) overlap mask at prototype resolution')
+        masks = torch.as_tensor(labels["masks"]).detach().cpu()
+        if masks.dim() != 3 or masks.shape[0] != batch_size:
+            raise L.UpaError(f"masks of shape {tuple(masks.shape)} for a batch of {batch_size} images: the overlap mask is (B, mh, mw) "
+                             "(overlap_mask=False stacks, one plane per instance, are not built)")
+        if tuple(masks.shape[-2:]) != (mh, mw):
+            raise L.UpaError(f"masks are {tuple(masks.shape[-2:])} but the prototypes are {(mh, mw)}: masks must come at prototype "
+                             "resolution (mask_ratio=4, the reference's dataset default); the F.interpolate fallback is not built")
+        if masks.numel():
+            lo, hi = float(masks.min()), float(masks.max())
+            if lo < 0 or hi > MASK_ID_MAX or (masks.dtype.is_floating_point and bool((masks != masks.round()).any())):
+                raise L.UpaError(f"mask values span [{lo:g}, {hi:g}]: instance ids must be integers in [0, {MASK_ID_MAX}] (the mask loss "
+                                 "reads the overlap mask as uint8)")
+        return masks.to(torch.uint8).contiguous()
+
+    def _upload_labels(self, labels, batch_size):
+        imgsz_h, imgsz_w = self._imgsz
+        s0 = float(self.detect.m.stride[0])
+        mh, mw = int(imgsz_h / s0) * 2, int(imgsz_w / s0) * 2  # Proto doubles level 0's map
+        masks = self.check_masks(labels, batch_size, mh, mw)
+        # every refusal comes before anything is uploaded: the ids are packed (into as many rows as the image with the most labels has)
+        # and checked first, then the gt rows go up, then the ids are laid out in the gt buffer's row count
+        bi = labels["batch_idx"].view(-1).cpu().long()
+        most = max([int((bi == j).sum()) for j in range(batch_size)] + [1])
+        mid0 = pack_mask_ids(labels, batch_size, imgsz_h, imgsz_w, most)
+        if int(mid0.max()) > MASK_ID_MAX:
+            raise L.UpaError(f"an image has a label at position {int(mid0.max())}: instance ids above {MASK_ID_MAX} do not fit the uint8 "
+                             "overlap mask")
+        super()._upload_labels(labels, batch_size)
+        rows = int(self.gt_d.shape[1])
+        mid = torch.zeros(batch_size, rows, dtype=torch.int32)
+        mid[:, :min(rows, most)] = mid0[:, :rows]
+        if self.masks_d is None or tuple(self.masks_d.shape) != tuple(masks.shape) or tuple(self.mid_d.shape) != tuple(mid.shape):
+            if self._graphs is not None or self._capturing:
+                raise L.UpaError(f"masks {tuple(masks.shape)} / {rows} gt rows do not match the compiled step's buffers")
+            self.masks_d = torch.zeros(tuple(masks.shape), dtype=torch.uint8, device=self.device)
+            self.mid_d = torch.zeros(tuple(mid.shape), dtype=torch.int32, device=self.device)
+        # through a ring of pinned staging buffers, each guarded by the event of its last copy, as the gt rows go
+        ring = self.__dict__.setdefault("_mask_ring", [None] * 4)
+        self._mask_slot = (self.__dict__.get("_mask_slot", -1) + 1) % len(ring)
+        ent = ring[self._mask_slot]
+        if ent is None or ent[0].shape != masks.shape or ent[1].shape != mid.shape:
+            ent = [torch.zeros(tuple(masks.shape), dtype=torch.uint8).pin_memory(), torch.zeros(tuple(mid.shape), dtype=torch.int32).pin_memory(),
+                   None]
+            ring[self._mask_slot] = ent
+        if ent[2] is not None:
+            ent[2].synchronize()
+        ent[0].copy_(masks)
+        ent[1].copy_(mid)
+        self.masks_d.copy_(ent[0], non_blocking=True)
+        self.mid_d.copy_(ent[1], non_blocking=True)
+        ent[2] = torch.cuda.Event()
+        ent[2].record(torch.cuda.current_stream(self.device))

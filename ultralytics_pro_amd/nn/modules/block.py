@@ -597,7 +597,8 @@ class Proto(nn.Module):
 
     def forward(self, x, out=None):
         if self.training:
-            raise L.UpaError("training-mode Proto is not on the HIP path (segmentation training is out of scope)")
+            raise L.UpaError("training-mode Proto.forward is not on the HIP path: train a segmentation model with engine.trainer.SegmentationTrainer (its ProtoT op "
+                             "holds the train-mode layer)")
         x = R.to_nhwc(x, x.dtype)
         t = hip_conv_transpose2x2(self.cv1(x), self, self.upsample, key=(id(self), "up"))
         return self.cv3(self.cv2(t), out=out)

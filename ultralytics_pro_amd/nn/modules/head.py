@@ -575,7 +575,8 @@ class Segment(Detect):
 
     def forward(self, x):
         if self.training:
-            raise L.UpaError("training-mode Segment is not on the HIP path (segmentation training is out of scope)")
+            raise L.UpaError("training-mode Segment.forward is not on the HIP path: train a segmentation model with engine.trainer.SegmentationTrainer (its "
+                             "SegmentT op holds the train-mode head)")
         det = super().forward(x)
         y, raw = (det, None) if self.export else det
         tag = R.current_tag()
