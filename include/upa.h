@@ -819,6 +819,42 @@ int upa_segment_match_bits(const uint32_t* det_bits, const int32_t* det_area, in
                            const int32_t* ngt, int max_gt, const float* iou_thresholds, int n_thr, unsigned char* tp_m, float* iou_out,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- pose estimation (csrc/pose.hip) ----------------------------------------------------------------------------------------------
+ * Pose.kpts_decode of one level (nn/modules/head.py:1264-1273): x = the level's cv4 output as an NHWC view (n, h, w, c >= nk), pixel
+ * stride ldx, f32 | bf16, nk = nkpt * ndim; out = (n, nk, a_total) f32,
+ *   out[b, j, a0 + y * w + x] = (v * 2 + x) * stride_px      j % ndim == 0       (x, y: the integer cell coordinates - the reference's
+ *                               (v * 2 + y) * stride_px      j % ndim == 1        anchor - 0.5 exactly; stride_px a power of two: one
+ *                               sigmoid(v)                   j % ndim == 2        rounding, bit-equal to torch in f32)
+ * with v = x[b, y, x, j].  raw (NULL = not written): the undecoded v in the same layout, the reference's `kpt` (head.py:1247).  The
+ * channel-to-anchor transpose is staged in LDS: 16-byte loads where x and ldx allow them, 16-byte stores where out (raw), a0 and
+ * a_total allow them, element loads / stores otherwise - any a_total, a0 and c are accepted.
+ * UPA_EINVAL: null x / out, a non-positive size, ldx < c, c < nk, a0 + h w > a_total, n > 65535.  UPA_EUNSUPPORTED: dtype outside
+ * f32 | bf16, ndim outside 2 | 3, nk > 128.  A refused call launches nothing and leaves out and raw untouched. */
+int upa_kpt_decode_rows(const void* x, int n, int h, int w, int c, int ldx, int dtype, int nkpt, int ndim, float stride_px, float* out,
+                        int a_total, int a0, float* raw, void* stream);
+/* scale_coords(normalize = False) + clip_coords (utils/ops.py:586-618, :180-201) in place on the keypoints of NMS rows: rows =
+ * (b, max_det) rows of row_stride floats with nkpt x ndim keypoint values from column col0; x -= pad_x, y -= pad_y (when `padding`),
+ * both /= gain, x clipped to [0, w0], y to [0, h0]; a third value per keypoint (the visibility) is untouched.  Only rows
+ * j < counts[i] of image i are touched (counts read on the device: no host sync, graph-capturable); counts = NULL: every row.
+ * UPA_EINVAL: null rows, nkpt <= 0, ndim < 2, keypoints past the row stride, gain <= 0. */
+int upa_scale_coords(float* rows, int b, int max_det, int row_stride, int col0, int nkpt, int ndim, const int32_t* counts, float gain,
+                     float pad_x, float pad_y, int padding, float w0, float h0, void* stream);
+/* The pose half of PoseValidator._process_batch for one batch (models/yolo/pose/val.py:169-197) fused with kpt_iou (utils/metrics.py:
+ * 164-184) and match_predictions (engine/validator.py:267-308): per (detection d, label l of the same class)
+ *   area = (x2 - x1)(y2 - y1) 0.53,  e_k = d_k / ((2 sigma_k)^2 (area + eps) 2),  OKS = sum_k exp(-e_k) [vis_k != 0] / (sum_k [vis_k != 0] + eps)
+ * in f32, the sums over k ascending (a replay is bit-identical), eps = 1e-7; the matching is upa_match_predictions' (best same-class
+ * label per detection, ties to the larger label index; per (label, threshold) the smallest claiming detection index wins).
+ *   rows: (b, max_det) rows of ld >= 6 + nkpt ndim floats [box, conf, cls, keypoints] as upa_nms_gather_extra writes them; counts (b,);
+ *   gt (b, max_gt, 5) rows [cls, x1, y1, x2, y2]; ngt (b,); gt_kpt (b, max_gt, nkpt, 3) [x, y, visibility]: all on the device and read
+ *   there (no host sync, no memset node: graph-capturable).  sigma: nkpt floats, iou_thresholds: 10 floats, both HOST arrays.
+ *   tp_p: (b, max_det, 10) bytes, rows past counts zero.  oks_out (NULL = not written): (b, max_det, max_gt) f32; class-unequal pairs,
+ *   rows past counts and columns past ngt are 0.  No workspace.
+ * UPA_EINVAL: a null required pointer, a non-positive size, ld < 6 + nkpt ndim, n_thr != 10, label tables past the LDS of a
+ * workgroup.  UPA_EUNSUPPORTED: ndim outside 2 | 3, nkpt > 64.  A refused call launches nothing. */
+int upa_pose_match(const float* rows, int ld, int b, int max_det, const int32_t* counts, const float* gt, const int32_t* ngt, int max_gt,
+                   const float* gt_kpt, int nkpt, int ndim, const float* sigma, const float* iou_thresholds, int n_thr,
+                   unsigned char* tp_p, float* oks_out, void* stream);
+
 /* ---- image classification head (csrc/classify.hip) -----------------------------------------------------------------------------
  * Classify.forward in eval (nn/modules/head.py:1523-1531): linear(drop(pool(conv(x)).flatten(1))) then softmax(1).  Three launches:
  * upa_classify_pool, upa_linear (exact f32 in both modes), upa_softmax_topk.

@@ -248,6 +248,9 @@ PROTOTYPES = {
     "upa_segment_match": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp,
                                _vp, _sz, _vp]),
     "upa_segment_match_bits": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "upa_kpt_decode_rows": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _i, _vp, _vp]),
+    "upa_scale_coords": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _f, _f, _f, _i, _f, _f, _vp]),
+    "upa_pose_match": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "upa_classify_pool": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _op, _vp]),
     "upa_softmax_topk": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "upa_global_avgpool_fwd": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),

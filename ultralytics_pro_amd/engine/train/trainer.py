@@ -43,6 +43,8 @@ class DetectionTrainer:
         if not self._segment_ok and any(isinstance(m, H.Segment) for m in model.modules()):
             raise L.UpaError("segmentation models (Segment head) have no training path on HIP in DetectionTrainer (v8DetectionLoss only): "
                              "train them with SegmentationTrainer")
+        if any(isinstance(m, H.Pose) for m in model.modules()):
+            raise L.UpaError("pose models (Pose head) have no training path on HIP: pose training (v8PoseLoss) is not built")
         for m in model.modules():
             if isinstance(m, H.Detect) and not m.legacy_cls:
                 if not yolo11:

@@ -1,4 +1,4 @@
-"""Validation loop of the detect and segment paths on the HIP kernels, one process per GPU (reference: engine/validator.py:195-260 and
+"""Validation loop of the detect, segment and pose paths on the HIP kernels, one process per GPU (reference: engine/validator.py:195-260 and
 models/yolo/detect/val.py:168-288).
 
 Per batch shard: model forward -> `non_max_suppression` with the validator's defaults (conf 0.001, iou 0.7, multi_label,
@@ -21,10 +21,13 @@ from ..utils.nms import nms_raw
 
 class DetectionValidator:
     accepts_segment = False  # a Segment head needs mask statistics next to the box ones: SegmentationValidator below
+    accepts_pose = False  # a Pose head needs keypoint (OKS) statistics next to the box ones: PoseValidator below
 
     def __init__(self, model=None, conf: float = 0.001, iou: float = 0.7, max_det: int = 300, max_gt: int = 64):
         if model is not None and not self.accepts_segment and any(type(m).__name__ == "Segment" for m in model.modules()):
             raise L.UpaError("segmentation models (Segment head) cannot be validated here: mask mAP is out of scope")
+        if model is not None and not self.accepts_pose and any(type(m).__name__ == "Pose" for m in model.modules()):
+            raise L.UpaError(f"pose models (Pose head) cannot be validated by {type(self).__name__}: use PoseValidator (box and pose mAP)")
         self.model, self.conf, self.iou, self.max_det, self.max_gt = model, conf, iou, max_det, max_gt
         self.reset()
 
@@ -249,6 +252,94 @@ class SegmentationValidator(DetectionValidator):
         stats = dict(tp=allr[:, 2:12].astype(bool), tp_m=allr[:, 12:22].astype(bool), conf=allr[:, 0], pred_cls=allr[:, 1], target_cls=tcls)
         stats.update(self._class_metrics(stats["tp"], stats["conf"], stats["pred_cls"], tcls))
         stats["seg"] = self._class_metrics(stats["tp_m"], stats["conf"], stats["pred_cls"], tcls)
+        return stats
+
+
+class PoseValidator(DetectionValidator):
+    """Validation of a Pose model: box AND pose P / R / mAP50 / mAP50-95 (models/yolo/pose/val.py:106-197, utils/metrics.py
+    PoseMetrics).  Per batch, all on the device with fixed shapes and no host sync: val-mode NMS -> the kept anchors' keypoints
+    (`upa_nms_gather_extra`) -> box true positives (`upa_match_predictions`) -> pose true positives (`upa_pose_match`: OKS of every
+    detection against the labels of its class and the claim step, one launch).  The statistics rows are 22 wide: conf | cls | tp | tp_p.
+
+    Scope: `save_json` / `save_txt`, flip-index TTA and plots are not provided."""
+
+    accepts_pose = True
+    stat_cols = 22
+
+    def __init__(self, model=None, conf: float = 0.001, iou: float = 0.7, max_det: int = 300, max_gt: int = 64, kpt_shape=None):
+        if kpt_shape is None:
+            kpt_shape = getattr(model, "kpt_shape", None) or (17, 3)
+        self.kpt_shape = tuple(int(v) for v in kpt_shape)
+        nkpt = self.kpt_shape[0]
+        self.sigma = M.OKS_SIGMA if self.kpt_shape == (17, 3) else np.ones(nkpt) / nkpt  # pose/val.py:114-116
+        super().__init__(model, conf, iou, max_det, max_gt)
+
+    def reset(self):
+        super().reset()
+        self._tpp = []
+
+    # ---- per batch ------------------------------------------------------------------------------------------------------
+    def pack_keypoints(self, labels: dict, batch_size: int, device, imgsz_hw=None):
+        """labels["keypoints"] (n, nkpt, 2 | 3) -> padded (B, max_gt, nkpt, 3) [x, y, visibility] for the labels `pack_labels` packs
+        (same order, same padded width).  The keypoints are in network-input pixels; with `imgsz_hw` they are normalised ones and
+        are multiplied by (w, h) as PoseValidator._prepare_batch does (pose/val.py:161-166).  Two-value keypoints count as visible."""
+        nkpt = self.kpt_shape[0]
+        bi = labels["batch_idx"].view(-1).long().cpu()
+        kp = labels["keypoints"].float().cpu().reshape(-1, nkpt, labels["keypoints"].shape[-1])
+        if kp.shape[-1] == 2:
+            kp = torch.cat([kp, torch.ones(kp.shape[0], nkpt, 1)], 2)
+        if imgsz_hw is not None:
+            kp = kp * torch.tensor([float(imgsz_hw[1]), float(imgsz_hw[0]), 1.0])
+        per = [(bi == j).nonzero().view(-1) for j in range(batch_size)]
+        cap = max(self.max_gt, max([int(ix.numel()) for ix in per] + [1]))
+        out = torch.zeros(batch_size, cap, nkpt, 3)
+        for j, ix in enumerate(per):
+            out[j, :int(ix.numel())] = kp[ix]
+        return out.to(device)
+
+    def update(self, preds, gt: torch.Tensor, ngt: torch.Tensor, gt_kpt: torch.Tensor, key=None, record: bool = True):
+        """preds: the Pose model's eval output; gt / ngt from `pack_labels`, gt_kpt from `pack_keypoints` of the same images.  `key`
+        names the step's static buffers and `record = False` leaves the statistics to a later `add_batch_stats` when the call is
+        captured into a graph.  Returns the step's device tensors (rows, counts, tp, tp_p)."""
+        from ..utils import ops
+        rows, counts, _ = ops.pose_postprocess_raw(preds, self.conf, self.iou, max_det=self.max_det, key=key, multi_label=True)
+        return self.update_detections(rows, counts, gt, ngt, gt_kpt, key=key, record=record)
+
+    def update_detections(self, rows: torch.Tensor, counts: torch.Tensor, gt: torch.Tensor, ngt: torch.Tensor, gt_kpt: torch.Tensor,
+                          key=None, record: bool = True):
+        """Already post-processed detections - rows (B, max_det, 6 + nk) with the keypoints, counts: match boxes and keypoints and
+        keep the batch's statistics."""
+        from ..engine import runtime as R
+        b, max_det, ld = rows.shape
+        dev = rows.device
+        out = R.alloc_plain((b, max_det, 6), torch.float32, dev, key=(key, "pose_det") if key is not None else None)
+        L.check(L.lib().upa_copy_rows(rows.data_ptr(), b * max_det, 6, ld, out.data_ptr(), 6, L.current_stream(dev)), "copy_rows")
+        tp = R.alloc_plain((b, max_det, 10), torch.uint8, dev, key=(key, "tp")) if key is not None else None
+        tp = M.match_predictions_batched(out, counts, gt, ngt, out=tp)
+        tp_p = M.match_keypoints_batched(rows, counts, gt, ngt, gt_kpt, self.kpt_shape, self.sigma, key=key)
+        if record:
+            self.add_batch_stats(out, counts, tp, gt, ngt, tp_p)
+        return rows, counts, tp, tp_p
+
+    def add_batch_stats(self, out: torch.Tensor, counts: torch.Tensor, tp: torch.Tensor, gt: torch.Tensor, ngt: torch.Tensor,
+                        tp_p: torch.Tensor):
+        """Statistics of a batch whose matching already ran (e.g. inside a captured step); `out`: (B, max_det, >= 6) rows."""
+        super().add_batch_stats(out[:, :, :6], counts, tp, gt, ngt)
+        self._tpp.append(tp_p.clone())
+
+    # ---- end of run -----------------------------------------------------------------------------------------------------
+    def local_stats(self):
+        """As DetectionValidator.local_stats with (I, max_det, 22) rows: conf | cls | tp | tp_p."""
+        rows, cnt, gcls, ngt = super().local_stats()
+        return torch.cat([rows, torch.cat(self._tpp, 0).float()], 2).contiguous(), cnt, gcls, ngt
+
+    def get_stats(self):
+        """What DetectionValidator.get_stats returns for the boxes, plus "tp_p" and "pose" = {p, r, f1, ap, classes, mean} of the
+        keypoints: the same `ap_per_class` on the pose true positives, as PoseMetrics.process does (utils/metrics.py)."""
+        allr, tcls = self._gathered()
+        stats = dict(tp=allr[:, 2:12].astype(bool), tp_p=allr[:, 12:22].astype(bool), conf=allr[:, 0], pred_cls=allr[:, 1], target_cls=tcls)
+        stats.update(self._class_metrics(stats["tp"], stats["conf"], stats["pred_cls"], tcls))
+        stats["pose"] = self._class_metrics(stats["tp_p"], stats["conf"], stats["pred_cls"], tcls)
         return stats
 
 

@@ -3,7 +3,7 @@
 
 from .block import C2f, C2PSA, C3, C3k, C3k2, DFL, MHSA, SPPF, BoT3, Bottleneck, BottleneckTransformer, PSABlock, Proto, v10_Attention
 from .conv import Concat, Conv, DWConv, autopad
-from .head import Classify, Detect, Segment
+from .head import Classify, Detect, Pose, Segment
 
 __all__ = ("Conv", "DWConv", "Concat", "autopad", "C2f", "C3", "DFL", "SPPF", "Bottleneck", "MHSA", "BottleneckTransformer",
-           "BoT3", "C3k", "C3k2", "v10_Attention", "PSABlock", "C2PSA", "Proto", "Detect", "Segment", "Classify")
+           "BoT3", "C3k", "C3k2", "v10_Attention", "PSABlock", "C2PSA", "Proto", "Detect", "Segment", "Pose", "Classify")

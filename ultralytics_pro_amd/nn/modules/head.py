@@ -10,9 +10,9 @@ import torch.nn as nn
 from ... import _lib as L
 from ...engine import runtime as R
 from .block import DFL, Proto
-from .conv import Conv, DWConv, PackedConv, _HipConvMixin, hip_conv2d, version_key
+from .conv import Conv, DWConv, PackedConv, _HipConvMixin, fold_bn, hip_conv2d, version_key
 
-__all__ = ("Detect", "Segment", "Classify")
+__all__ = ("Detect", "Segment", "Pose", "Classify")
 
 
 def _magic_exact(xmax: int, d: int) -> bool:
@@ -599,12 +599,13 @@ class Segment(Detect):
         """(B, 4+nc+nm, A) = cat([y, mc], 1) with two strided copies: `upa_copy_view` over one 'pixel' per image when every row is
         a 16-byte multiple, else `upa_copy_rows` (any A)."""
         n, cy, a = y.shape
-        ct = cy + self.nm
+        ne = int(mc.shape[1])  # nm (Segment) or nk (Pose, which shares this method)
+        ct = cy + ne
         cat = R.alloc_plain((n, ct, a), torch.float32, y.device, key=(id(self), "cat"))
         stream = L.current_stream(y.device)
         lib = L.lib()
-        for src, c, dst in ((y, cy, cat), (mc, self.nm, cat[:, cy:])):
-            if (cy * a) % 4 == 0 and (self.nm * a) % 4 == 0:
+        for src, c, dst in ((y, cy, cat), (mc, ne, cat[:, cy:])):
+            if (cy * a) % 4 == 0 and (ne * a) % 4 == 0:
                 L.check(lib.upa_copy_view(src.data_ptr(), n, 1, 1, c * a, c * a, dst.data_ptr(), ct * a, L.UPA_F32, stream), "copy_view")
             else:
                 L.check(lib.upa_copy_rows(src.data_ptr(), n, c * a, c * a, dst.data_ptr(), ct * a, stream), "copy_rows")
@@ -613,6 +614,147 @@ class Segment(Detect):
 
     def train(self, mode: bool = True):
         self.__dict__.pop("_seg", None)
+        return super().train(mode)
+
+
+class Pose(Detect):
+    """YOLO Pose head (head.py:1208-1273): Detect + per-level keypoint branches `cv4[l] = Conv3x3 -> Conv3x3 -> nn.Conv2d(c4, nk, 1)`,
+    nk = kpt_shape[0] * kpt_shape[1], c4 = max(ch[0] // 4, nk).
+
+    Eval forward returns the reference's `(cat([y, pred_kpt], 1), (raw, kpt))`: y = Detect's (B, 4+nc, A) output, untouched,
+    pred_kpt = (B, nk, A) f32 decoded keypoints and kpt the undecoded ones (None with `keep_raw = False`): one `upa_kpt_decode_rows`
+    launch per level writes both into the level's anchor range.  With `cat_out = False` the concatenated copy is not made and the first
+    element is y itself (`utils.ops.pose_postprocess_raw` reads the parts either way); the concatenated tensor carries
+    `_upa_parts = (y, pred_kpt)`, so `utils.nms` runs on y and gathers the keypoints of the kept rows.
+
+    51 channels: nk = 17 * 3 (and c4, for the n / s / m scales) is no multiple of the convolutions' 16-byte channel rule.  The
+    state_dict keeps the reference's shapes; the PACKED weights are padded to multiples of 8 channels (`_packed_pad`): padded output
+    channels have zero filters and zero folded bias (SiLU(0) = 0, so they stay zero), the next conv's padded input channels have zero
+    filters (their products add exact zeros: the real channels are bit-identical to an unpadded convolution).
+
+    Scheduling follows Segment: a level's cv4 branch runs when `start_level` is called for it, the rest in `forward`.  Inference only:
+    a train-mode forward raises (pose training, v8PoseLoss, is not built)."""
+
+    cat_out = True
+    PAD = 8  # channels per 16 bytes of bf16; a multiple of f32's 4, so one padded layout serves both dtypes
+
+    def __init__(self, nc: int = 80, kpt_shape: tuple = (17, 3), ch: tuple = ()):
+        try:
+            nkpt, ndim = (int(v) for v in kpt_shape)
+        except (TypeError, ValueError):
+            raise L.UpaError(f"Pose: kpt_shape must be (keypoints, 2 | 3), got {kpt_shape!r}") from None
+        if ndim not in (2, 3):
+            raise L.UpaError(f"Pose: kpt_shape[1] = {ndim} - a keypoint is (x, y) or (x, y, visibility)")
+        if nkpt < 1:
+            raise L.UpaError(f"Pose: kpt_shape[0] = {nkpt} - at least one keypoint is needed")
+        if nkpt * ndim > 128:
+            raise L.UpaError(f"Pose: {nkpt * ndim} keypoint values per anchor are past upa_kpt_decode_rows' 128")
+        super().__init__(nc, ch)
+        self.kpt_shape = kpt_shape
+        self.nk = nkpt * ndim
+        c4 = max(ch[0] // 4, self.nk)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.nk, 1)) for x in ch)
+
+    def _packed_pad(self, conv: nn.Conv2d, bn, device, dtype, pad_cin: int, pad_cout: int) -> PackedConv:
+        """`_packed` with zero input channels appended up to `pad_cin` and zero filters / biases up to `pad_cout`."""
+        cache = self.__dict__.setdefault("_pk_cache", {})
+        key = (id(conv), str(device), dtype, "pose", pad_cin, pad_cout)
+        ver = version_key(conv.weight, conv.bias, *(() if bn is None else (bn.weight, bn.bias, bn.running_mean,
+                                                                           bn.running_var))) + ((bn.eps,) if bn is not None else ())
+        hit = cache.get(key)
+        if hit is not None and hit[0] == ver:
+            return hit[1]
+        w, b = fold_bn(conv, bn)
+        co, ci, k, _ = w.shape
+        wp = torch.zeros(max(pad_cout, co), max(pad_cin, ci), k, k)
+        wp[:co, :ci] = w
+        bp = torch.zeros(wp.shape[0])
+        bp[:co] = b
+        pk = PackedConv(wp, bp, k, device, dtype, False)
+        cache[key] = (ver, pk)
+        return pk
+
+    def kpt_chain(self, i: int, x: torch.Tensor):
+        """cv4[i] on the padded layout: (t0, t1, c) = the two 3x3 outputs (c4 rounded up to 8 channels) and the 1x1 output (nk rounded
+        up to 8), NHWC views; channels past c4 / nk are zero."""
+        x = R.to_nhwc(x, x.dtype)
+        seq = self.cv4[i]
+        for m in seq[:2]:
+            if m.training:
+                raise L.UpaError("Pose: a cv4 Conv is in train mode")
+        up = lambda v: (v + self.PAD - 1) // self.PAD * self.PAD  # noqa: E731
+        c4p, nkp = up(seq[0].conv.out_channels), up(self.nk)
+        dev, dt = x.device, x.dtype
+        pk0 = self._packed_pad(seq[0].conv, seq[0].bn, dev, dt, 0, c4p)
+        pk1 = self._packed_pad(seq[1].conv, seq[1].bn, dev, dt, c4p, c4p)
+        pk2 = self._packed_pad(seq[2], None, dev, dt, c4p, nkp)
+        t0 = hip_conv2d(x, pk0, seq[0].conv.stride[0], seq[0].conv.padding[0], seq[0]._act_code(), key=(id(self), "kpt_t0", i))
+        t1 = hip_conv2d(t0, pk1, seq[1].conv.stride[0], seq[1].conv.padding[0], seq[1]._act_code(), key=(id(self), "kpt_t1", i))
+        c = hip_conv2d(t1, pk2, 1, 0, L.ACT_NONE, key=(id(self), "kpt_map", i))
+        return t0, t1, c
+
+    def _pose_plans(self):
+        return self.__dict__.setdefault("_pose", {})
+
+    def begin(self, n: int, level_hw, dtype, device) -> None:
+        super().begin(n, level_hw, dtype, device)
+        self._pose_begin(n, level_hw, device)
+
+    def _pose_begin(self, n, level_hw, device):
+        a0, tot = [], 0
+        for (h, w) in level_hw:
+            a0.append(tot)
+            tot += int(h) * int(w)
+        pk = R.alloc_plain((int(n), self.nk, tot), torch.float32, device, key=(id(self), "pred_kpt"))
+        kpt = R.alloc_plain((int(n), self.nk, tot), torch.float32, device, key=(id(self), "kpt")) if self.keep_raw else None
+        self._pose_plans()[R.current_tag()] = dict(pk=pk, kpt=kpt, a0=a0, a_total=tot, n=int(n), hw=[(int(h), int(w)) for h, w in level_hw],
+                                                   done=set())
+
+    def start_level(self, i: int, x: torch.Tensor, defer_ok: bool = True) -> None:
+        super().start_level(i, x, defer_ok)
+        plan = self._pose_plans().get(R.current_tag())
+        if plan is not None and i not in plan["done"] and self._pose_fits(plan, i, x):
+            self._pose_level(plan, i, x)
+
+    @staticmethod
+    def _pose_fits(plan, i, x) -> bool:
+        return plan["n"] == int(x.shape[0]) and plan["hw"][i] == (int(x.shape[2]), int(x.shape[3])) and plan["pk"].device == x.device
+
+    def _pose_level(self, plan, i: int, x: torch.Tensor) -> None:
+        """cv4[i] decoded into pred_kpt[:, :, a0_i : a0_i + H_i W_i] (and the undecoded values into kpt)."""
+        _, _, c = self.kpt_chain(i, x)
+        vc = R.view_of(c)
+        kpt = plan["kpt"]
+        nkpt, ndim = (int(v) for v in self.kpt_shape)
+        L.check(L.lib().upa_kpt_decode_rows(vc.ptr, vc.n, vc.h, vc.w, vc.c, vc.ld, vc.dtype, nkpt, ndim, float(self.stride[i]),
+                                            plan["pk"].data_ptr(), plan["a_total"], plan["a0"][i],
+                                            None if kpt is None else kpt.data_ptr(), L.current_stream(x.device)), "kpt_decode_rows")
+        plan["done"].add(i)
+
+    def forward(self, x):
+        if self.training:
+            raise L.UpaError("training-mode Pose.forward is not on the HIP path: pose training (v8PoseLoss) is not built")
+        det = super().forward(x)
+        y, raw = (det, None) if self.export else det
+        tag = R.current_tag()
+        plan = self._pose_plans().get(tag)
+        if plan is None or not all(self._pose_fits(plan, i, x[i]) for i in range(self.nl)):
+            self._pose_begin(x[0].shape[0], [(t.shape[2], t.shape[3]) for t in x], x[0].device)
+            plan = self._pose_plans()[tag]
+        for i in range(self.nl):
+            if i not in plan["done"]:
+                self._pose_level(plan, i, x[i])
+        self._pose_plans().pop(tag, None)
+        pk, kpt = plan["pk"], plan["kpt"]
+        out = self._cat(y, pk) if (self.cat_out or self.export) else y
+        if out is y:
+            y._upa_pose = pk  # the parts travel with y: pose_postprocess_raw needs no second return value
+        return out if self.export else (out, (raw, kpt))
+
+    _cat = Segment._cat
+
+    def train(self, mode: bool = True):
+        self.__dict__.pop("_pose", None)
         return super().train(mode)
 
 

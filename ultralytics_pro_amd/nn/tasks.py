@@ -19,7 +19,7 @@ import yaml
 
 from .. import _lib as L
 from ..engine import runtime as R
-from .modules import (C2f, C2PSA, C3, C3k2, SPPF, BoT3, Bottleneck, Classify, Concat, Conv, Detect, Segment)
+from .modules import (C2f, C2PSA, C3, C3k2, SPPF, BoT3, Bottleneck, Classify, Concat, Conv, Detect, Pose, Segment)
 from .modules.conv import VirtualUpsample
 from .modules.resample import MaxPool2d, Upsample, ZeroPad2d
 
@@ -29,7 +29,7 @@ _NN_STANDINS = {"Upsample": Upsample, "MaxPool2d": MaxPool2d, "ZeroPad2d": ZeroP
 
 
 def _registry():
-    reg = {m.__name__: m for m in (Conv, C2f, C3, SPPF, BoT3, Bottleneck, Concat, Detect, Segment, C3k2, C2PSA, Classify)}
+    reg = {m.__name__: m for m in (Conv, C2f, C3, SPPF, BoT3, Bottleneck, Concat, Detect, Segment, Pose, C3k2, C2PSA, Classify)}
     try:
         from .modules.rtdetr import RTDETRDecoder
         reg["RTDETRDecoder"] = RTDETRDecoder
@@ -49,19 +49,22 @@ def make_divisible(x, divisor):
 
 
 def yaml_model_load(path):
-    """Load a model YAML; 'yolov8n.yaml' resolves to yolov8.yaml with scale 'n', 'yolov8n-seg.yaml' to yolov8-seg.yaml
-    and 'yolov8n-cls.yaml' to yolov8-cls.yaml (tasks.py:3147-3185)."""
+    """Load a model YAML; 'yolov8n.yaml' resolves to yolov8.yaml with scale 'n', 'yolov8n-seg.yaml' to yolov8-seg.yaml,
+    'yolov8n-cls.yaml' to yolov8-cls.yaml and 'yolov8n-pose.yaml' to yolov8-pose.yaml (tasks.py:3147-3185)."""
     path = Path(path)
     stem, scale = path.stem, ""
     m = re.match(r"^(yolo(?:v)?\d+)([nslmx])$", stem)
     seg = re.match(r"^(yolo(?:v)?\d+)([ntslmx])-seg$", stem)
     cls = re.match(r"^(yolo(?:v)?\d+)([nslmx])-cls$", stem)
+    pose = re.match(r"^(yolo(?:v)?\d+)([nslmx])-pose$", stem)
     if m:
         stem, scale = m.group(1), m.group(2)
     elif seg:
         stem, scale = seg.group(1) + "-seg", seg.group(2)
     elif cls:
         stem, scale = cls.group(1) + "-cls", cls.group(2)
+    elif pose:
+        stem, scale = pose.group(1) + "-pose", pose.group(2)
     cands = [path] if path.is_file() else sorted(CFG_DIR.rglob(stem + ".yaml"))
     if not cands:
         raise FileNotFoundError(f"model YAML '{path}' not found under {CFG_DIR}")
@@ -99,7 +102,7 @@ def parse_model(d, ch, verbose=False):
         for j, a in enumerate(args):
             if isinstance(a, str):
                 with contextlib.suppress(ValueError):
-                    args[j] = nc if a == "nc" else ast.literal_eval(a)
+                    args[j] = nc if a == "nc" else d.get("kpt_shape") if a == "kpt_shape" else ast.literal_eval(a)
         n = n_ = max(round(n * depth), 1) if n > 1 else n
         if mname in BASE_MODULES:
             c1, c2 = ch[f], args[0]
@@ -115,7 +118,7 @@ def parse_model(d, ch, verbose=False):
                     args[3] = True
         elif mname == "Concat":
             c2 = sum(ch[x] for x in f)
-        elif mname in ("Detect", "Segment"):
+        elif mname in ("Detect", "Segment", "Pose"):
             args.append([ch[x] for x in f])
             if mname == "Segment":  # npr (tasks.py:2990-2991)
                 args[2] = make_divisible(min(args[2], max_channels) * width, 8)
@@ -124,7 +127,12 @@ def parse_model(d, ch, verbose=False):
             args.insert(1, [ch[x] for x in f])
         else:
             c2 = ch[f]
-        m_ = HipSequential(*(m(*args) for _ in range(n))) if n > 1 else m(*args)
+        try:
+            m_ = HipSequential(*(m(*args) for _ in range(n))) if n > 1 else m(*args)
+        except L.UpaError as e:  # a refused Pose row names its layer (every other module's message stays as it was)
+            if mname != "Pose":
+                raise
+            raise L.UpaError(f"layer {i} ({mname}{args!s}): {e}") from None
         t = f"{m.__module__}.{m.__name__}"
         m.np = sum(x.numel() for x in m_.parameters())
         m_.np = m.np
@@ -540,6 +548,21 @@ class SegmentationModel(DetectionModel):
         super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
         if not isinstance(self.model[-1], Segment):
             raise L.UpaError(f"SegmentationModel needs a Segment head, {cfg} ends in {type(self.model[-1]).__name__}")
+
+
+class PoseModel(DetectionModel):
+    """YOLO pose model (tasks.py:1368-1395): a DetectionModel whose head is `Pose`.  `data_kpt_shape` overrides the YAML's `kpt_shape`
+    as in the reference.  Inference and validation (`engine.validator.PoseValidator`); pose training (v8PoseLoss) is not built."""
+
+    def __init__(self, cfg="yolov8n-pose.yaml", ch=3, nc=None, data_kpt_shape=(None, None), verbose=False):
+        if not isinstance(cfg, dict):
+            cfg = yaml_model_load(cfg)
+        if any(data_kpt_shape) and list(data_kpt_shape) != list(cfg["kpt_shape"]):
+            cfg["kpt_shape"] = data_kpt_shape
+        super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
+        if not isinstance(self.model[-1], Pose):
+            raise L.UpaError(f"PoseModel needs a Pose head, {cfg.get('yaml_file', 'the given dict')} ends in {type(self.model[-1]).__name__}")
+        self.kpt_shape = tuple(int(v) for v in self.model[-1].kpt_shape)
 
 
 RTDETRDetectionModel = DetectionModel  # eval path differs only in the head module (tasks.py:1608)

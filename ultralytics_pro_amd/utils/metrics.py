@@ -290,3 +290,62 @@ def process_cls_preds(preds, targets, nc: int) -> np.ndarray:
     matrix = np.zeros((nc, nc), dtype=np.int64)
     np.add.at(matrix, (p, t), 1)
     return matrix
+
+
+# ---- pose: object keypoint similarity and pose true positives (csrc/pose.hip) -------------------------------------------------------------
+# the 17 COCO keypoint constants (utils/metrics.py:17-20)
+OKS_SIGMA = np.array([0.26, 0.25, 0.25, 0.35, 0.35, 0.79, 0.79, 0.72, 0.72, 0.62, 0.62, 1.07, 1.07, 0.87, 0.87, 0.89, 0.89]) / 10.0
+
+
+def match_keypoints_batched(rows: torch.Tensor, counts: torch.Tensor, gt: torch.Tensor, ngt: torch.Tensor, gt_kpt: torch.Tensor,
+                            kpt_shape, sigma, iouv=IOUV, out: torch.Tensor | None = None, oks_out: torch.Tensor | None = None,
+                            key=None) -> torch.Tensor:
+    """Pose true-positive matrices of a whole batch on the GPU (`upa_pose_match`; models/yolo/pose/val.py:169-197): rows
+    (B, max_det, 6 + nk) [box, conf, cls, keypoints] + counts (B,) as `pose_postprocess_raw` returns them, gt (B, max_gt, 5) label
+    rows [cls, x1, y1, x2, y2] + ngt (B,), gt_kpt (B, max_gt, nkpt, 3) [x, y, visibility] in the same pixels -> (B, max_det, 10)
+    uint8, no host sync.  `oks_out` (B, max_det, max_gt) f32 receives the OKS matrix."""
+    from ..engine import runtime as R
+    L.require_gpu(rows, "match_keypoints")
+    b, max_det, ld = rows.shape
+    nkpt, ndim = int(kpt_shape[0]), int(kpt_shape[1])
+    max_gt = int(gt.shape[1])
+    for t, shape, what in ((gt, (b, max_gt, 5), "gt"), (gt_kpt, (b, max_gt, nkpt, 3), "gt_kpt"), (rows, (b, max_det, ld), "rows")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise L.UpaError(f"match_keypoints: {what} must be a contiguous float32 {shape} tensor, got {tuple(t.shape)} {t.dtype}")
+    if oks_out is not None and (oks_out.dtype != torch.float32 or not oks_out.is_contiguous() or tuple(oks_out.shape) != (b, max_det, max_gt)):
+        raise L.UpaError(f"match_keypoints: oks_out must be a contiguous float32 {(b, max_det, max_gt)} tensor")
+    sg = np.ascontiguousarray(np.asarray(sigma, dtype=np.float32))
+    if sg.shape != (nkpt,):
+        raise L.UpaError(f"match_keypoints: {sg.shape[0] if sg.ndim else 0} sigmas for {nkpt} keypoints")
+    thr = np.ascontiguousarray(np.asarray(iouv, dtype=np.float32))
+    tp = out if out is not None else R.alloc_plain((b, max_det, thr.shape[0]), torch.uint8, rows.device,
+                                                   key=(key, "tp_p") if key is not None else None)
+    L.check(L.lib().upa_pose_match(rows.data_ptr(), int(ld), int(b), int(max_det), counts.data_ptr(), gt.data_ptr(), ngt.data_ptr(), max_gt,
+                                   gt_kpt.data_ptr(), nkpt, ndim, sg.ctypes.data, thr.ctypes.data, int(thr.shape[0]), tp.data_ptr(),
+                                   None if oks_out is None else oks_out.data_ptr(), L.current_stream(rows.device)), "pose_match")
+    return tp
+
+
+def kpt_iou(kpt1: torch.Tensor, kpt2: torch.Tensor, area: torch.Tensor, sigma, eps: float = 1e-7) -> torch.Tensor:
+    """Object keypoint similarity (utils/metrics.py:164-184) on the GPU: kpt1 (N, nkpt, 3) label keypoints, kpt2 (M, nkpt, 2 | 3)
+    predicted ones, area (N,) label areas -> (N, M) f32.  One image of `upa_pose_match` with every pair in one class: the kernel
+    derives the area from a label box, so each label gets the box (0, 0, area / 0.53, 1)."""
+    L.require_gpu(kpt1, "kpt_iou")
+    if eps != 1e-7:
+        raise L.UpaError("kpt_iou: eps is fixed at 1e-7 on the HIP path")
+    n, m, nkpt, ndim = int(kpt1.shape[0]), int(kpt2.shape[0]), int(kpt1.shape[1]), int(kpt2.shape[2])
+    dev = kpt1.device
+    if n == 0 or m == 0:
+        return torch.zeros((n, m), dtype=torch.float32, device=dev)
+    if kpt1.shape[2] != 3 or int(kpt2.shape[1]) != nkpt:
+        raise L.UpaError(f"kpt_iou: label keypoints {tuple(kpt1.shape)} and predicted keypoints {tuple(kpt2.shape)}")
+    rows = torch.zeros((1, m, 6 + nkpt * ndim), dtype=torch.float32, device=dev)
+    rows[0, :, 6:] = kpt2.float().reshape(m, -1)
+    gt = torch.zeros((1, n, 5), dtype=torch.float32, device=dev)
+    gt[0, :, 3] = area.float().to(dev) / 0.53
+    gt[0, :, 4] = 1.0
+    cnt = torch.tensor([m], dtype=torch.int32, device=dev)
+    ng = torch.tensor([n], dtype=torch.int32, device=dev)
+    oks = torch.empty((1, m, n), dtype=torch.float32, device=dev)
+    match_keypoints_batched(rows, cnt, gt, ng, kpt1.float().reshape(1, n, nkpt, 3).contiguous(), (nkpt, ndim), sigma, oks_out=oks)
+    return oks[0].t().contiguous()

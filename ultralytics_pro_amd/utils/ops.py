@@ -228,3 +228,93 @@ def segment_postprocess(preds, conf_thres: float = 0.25, iou_thres: float = 0.7,
         res.append((det, masks))
         base += k
     return res
+
+
+# ---- pose: keypoints of the kept rows (models/yolo/pose/predict.py, utils/ops.py:586-618 scale_coords) on `upa_scale_coords` ------------
+
+def _coords_geometry(img1_shape, img0_shape, ratio_pad):
+    """(gain, pad_x, pad_y) of scale_coords, host floats as `scale_boxes` computes its own.  The reference's scale_coords does NOT
+    round the padding (ops.py:603-604), unlike its scale_boxes (:126-127): restated as it is."""
+    if ratio_pad is None:
+        gain = min(img1_shape[0] / img0_shape[0], img1_shape[1] / img0_shape[1])
+        return gain, (img1_shape[1] - img0_shape[1] * gain) / 2, (img1_shape[0] - img0_shape[0] * gain) / 2
+    return ratio_pad[0][0], ratio_pad[1][0], ratio_pad[1][1]
+
+
+def scale_coords(img1_shape, coords: torch.Tensor, img0_shape, ratio_pad=None, normalize: bool = False, padding: bool = True):
+    """Rescale (..., >= 2) float32 coordinates (x, y[, visibility]) in place on the GPU from the letterboxed `img1_shape` (h, w) to
+    the original `img0_shape` and clip them (utils/ops.py:586-618 + clip_coords :180-201); a third value is untouched."""
+    if normalize:
+        raise L.UpaError("scale_coords(normalize=True) is outside the hot-path scope")
+    L.require_gpu(coords, "scale_coords")
+    if coords.dtype != torch.float32 or coords.dim() < 1 or coords.shape[-1] < 2 or (coords.numel() and not coords.is_contiguous()):
+        raise L.UpaError("scale_coords expects contiguous float32 (..., >= 2) coordinates")
+    gain, pad_x, pad_y = _coords_geometry(img1_shape, img0_shape, ratio_pad)
+    nd = int(coords.shape[-1])
+    n = coords.numel() // nd
+    if n:
+        L.check(L.lib().upa_scale_coords(coords.data_ptr(), 1, n, nd, 0, 1, nd, None, float(gain), float(pad_x), float(pad_y),
+                                         int(bool(padding)), float(img0_shape[1]), float(img0_shape[0]),
+                                         L.current_stream(coords.device)), "scale_coords")
+    return coords
+
+
+def _pose_parts(preds, nc: int):
+    """(y (B, 4+nc, A), pred_kpt (B, nk, A)) from a Pose head's eval output `(y | cat([y, pred_kpt], 1), (raw, kpt))` or its first
+    element."""
+    first = preds[0] if isinstance(preds, (list, tuple)) else preds
+    parts = getattr(first, "_upa_parts", None)
+    if parts is not None:
+        return parts
+    pk = getattr(first, "_upa_pose", None)
+    if pk is not None:
+        return first, pk
+    if not nc or first.dim() != 3 or first.shape[1] <= 4 + nc:
+        raise L.UpaError("pose postprocess expects a Pose head's eval output (or a (B, 4+nc+nk, A) tensor with nc given)")
+    return first[:, :4 + nc].contiguous(), first[:, 4 + nc:].contiguous()
+
+
+def pose_postprocess_raw(preds, conf_thres: float = 0.25, iou_thres: float = 0.7, classes=None, agnostic: bool = False,
+                         max_det: int = 300, nc: int = 0, key=None, multi_label: bool = False):
+    """Device-side pose postprocess with no host synchronisation (capturable in `compile(post=...)` and `PipelinedRunner`): NMS ->
+    keypoint gather (`upa_nms_gather_extra`).  Returns (rows (B, max_det, 6 + nk) [box, conf, cls, keypoints], counts (B,), keep
+    (B, max_det)): in network-input pixels, rows past counts zero."""
+    from ..engine import runtime as R
+    from .nms import nms_raw
+    y, pk = _pose_parts(preds, nc)
+    b, nk, a = pk.shape
+    out, counts, keep = nms_raw(y, conf_thres, iou_thres, classes, agnostic, multi_label, max_det, int(y.shape[1]) - 4, key=key)
+    rows = R.alloc_plain((b, max_det, 6 + nk), torch.float32, y.device, key=(key, "pose_rows"))
+    L.check(L.lib().upa_nms_gather_extra(pk.data_ptr(), b, nk, a, keep.data_ptr(), counts.data_ptr(), int(max_det), out.data_ptr(),
+                                         rows.data_ptr(), 6 + nk, L.current_stream(y.device)), "nms_gather_extra")
+    return rows, counts, keep
+
+
+def scale_pose_rows(rows: torch.Tensor, counts: torch.Tensor, imgsz, orig_shape, kpt_shape, ratio_pad=None, padding: bool = True):
+    """scale_boxes + scale_coords in place on (B, max_det, 6 + nk) pose rows (one `orig_shape` for the batch), the first counts[i]
+    rows of every image, counts read on the device."""
+    b, max_det, ld = rows.shape
+    scale_boxes(imgsz, rows, orig_shape, ratio_pad=ratio_pad, padding=padding)
+    gain, pad_x, pad_y = _coords_geometry(imgsz, orig_shape, ratio_pad)
+    L.check(L.lib().upa_scale_coords(rows.data_ptr(), int(b), int(max_det), int(ld), 6, int(kpt_shape[0]), int(kpt_shape[1]),
+                                     counts.data_ptr(), float(gain), float(pad_x), float(pad_y), int(bool(padding)),
+                                     float(orig_shape[1]), float(orig_shape[0]), L.current_stream(rows.device)), "scale_coords")
+    return rows
+
+
+def pose_postprocess(preds, conf_thres: float = 0.25, iou_thres: float = 0.7, classes=None, agnostic: bool = False, max_det: int = 300,
+                     nc: int = 0, kpt_shape=(17, 3), imgsz=(640, 640), orig_shapes=None):
+    """Per image (boxes (n, 6) [x1, y1, x2, y2, conf, cls], keypoints (n, nkpt, ndim)), both scaled to the image's `orig_shapes[i]`
+    (h, w) when given, as PosePredictor.construct_result does (models/yolo/pose/predict.py)."""
+    rows, counts, _ = pose_postprocess_raw(preds, conf_thres, iou_thres, classes, agnostic, max_det, nc)
+    nkpt, ndim = int(kpt_shape[0]), int(kpt_shape[1])
+    if rows.shape[2] != 6 + nkpt * ndim:
+        raise L.UpaError(f"pose_postprocess: rows of {int(rows.shape[2]) - 6} keypoint values for kpt_shape {tuple(kpt_shape)}")
+    n = counts.tolist()
+    res = []
+    for i, k in enumerate(n):
+        r = rows[i, :k].contiguous()
+        if orig_shapes is not None and k:
+            scale_pose_rows(r[None], counts[i:i + 1], imgsz, orig_shapes[i], (nkpt, ndim))
+        res.append((r[:, :6], r[:, 6:].reshape(k, nkpt, ndim)))
+    return res

@@ -102,12 +102,17 @@ ATTN_GAIN2 = 1.0  # MHSA q/k/v 1x1 convs (block.py:6020-6062): energy = q^T k is
 # gain^2 of the YOLO11 attention's qkv 1x1 conv (attn.qkv) per family: at CONV_GAIN2 the softmax over 400 tokens is flat (max probability
 # 0.003 ~ 1/400); 100 makes it neither flat nor one-hot (median max probability 0.017, ~7x uniform) while the f32 model stays
 # reproducible: larger gains make the head so sensitive that the f32 reference itself sits 8e-3 px from its float64 run
-PSA_QKV_GAIN2 = {"yolov11n": 100.0, "smooth:yolov11n": 100.0, "yolov11n-seg": 100.0, "smooth:yolov11n-seg": 100.0}
+PSA_QKV_GAIN2 = {"yolov11n": 100.0, "smooth:yolov11n": 100.0, "yolov11n-seg": 100.0, "smooth:yolov11n-seg": 100.0,
+                 "yolov11n-pose": 100.0, "smooth:yolov11n-pose": 100.0}
 # Mean bias of the Segment head's final coefficient 1x1 convs (cv4.l.2, head.py:790-837) per family, U(m - 0.1, m + 0.1).  The protos
 # leave their SiLU mostly positive, and with the default U(-0.1, 0.1) biases the yolov11n-seg coefficients of the kept anchors weight
 # them so that coefficients . protos is negative over almost every box: every stored instance mask came out empty.  A positive bias
 # adds a positive multiple of the proto mass; these values fill roughly 25-60 % of a kept box (none empty, none full).
 MASK_COEF_BIAS = {"yolov11n-seg": 10.0, "smooth:yolov11n-seg": 1.0}
+# Gain of the Pose head's final keypoint 1x1 convs (cv4.l.2, head.py:1208-1273) per family.  yolov11n's neck features are ~10x yolov8n's
+# (see HEAD_RECIPE) and one unit of that conv's output is 2 x stride pixels: at the plain draw the yolov11n-pose keypoints spread over
+# thousands of pixels, where f32 rounding alone is 1e-2 px.  0.02 keeps them within a few hundred pixels of their anchors.
+POSE_KPT_GAIN = {"yolov11n-pose": 0.02, "smooth:yolov11n-pose": 0.02}
 RES_GAIN2 = 0.3  # last conv of a residual branch (Bottleneck.cv2 with add=True): damped, else x + f(x) chains explode
 CLS_BIAS_SPREAD = 0.5
 # Detect-head recipe per model family: (final cls 1x1 weight gain, mean final cls bias, final box 1x1 weight gain).
@@ -124,6 +129,9 @@ HEAD_RECIPE = {
     # segmentation: the detection graphs with a Segment head - the box / class branches are the detection ones, same gains
     "yolov8n-seg": (5.0, -4.4, 5.0),
     "yolov11n-seg": (0.1, -6.8, 0.1),
+    # pose: the detection graphs with a Pose head, same gains (yolov8n-pose has one class: its best scores sit below 0.25)
+    "yolov8n-pose": (5.0, -4.4, 5.0),
+    "yolov11n-pose": (0.1, -6.8, 0.1),
 }
 # Classification families: gain of the Classify head's `model.N.linear.weight` draw (head.py:1521) on top of sqrt(3 / fan_in).  With the
 # plain draw the logits of 1000 classes are nearly flat (spread ~0.3) and no top-5 is decidable; these gains spread them over several
@@ -164,6 +172,8 @@ SMOOTH_RECIPE = {
     "yolov11n": (6.5, 0.1, -2.66, 0.05),
     "yolov8n-seg": (6.5, 4.0, -4.09, 1.5),
     "yolov11n-seg": (6.5, 0.1, -2.66, 0.05),
+    "yolov8n-pose": (6.5, 4.0, -4.09, 1.5),
+    "yolov11n-pose": (6.5, 0.1, -2.66, 0.05),
 }
 
 
@@ -216,6 +226,8 @@ def procedural_tensor(key: str, ref: torch.Tensor, kind: str, seed: int = 0, res
         gain = 1.0
         if det_final:
             gain = box_w_gain if parts[-4] == "cv2" else cls_w_gain
+        if len(parts) >= 5 and parts[-4] == "cv4" and parts[-2] == "2" and parts[-3].isdigit():
+            gain = POSE_KPT_GAIN.get(family, gain)
         if "score_head" in key:
             gain = RTDETR_SCORE_GAIN
         if "sampling_offsets" in key:
