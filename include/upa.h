@@ -767,6 +767,41 @@ int upa_mask_loss(const void* proto, int b, int mh, int mw, int nm, int ldp, con
                   int imgsz_h, int imgsz_w, float gain, float grad_scale, const float* grad_scale_dev, float* loss_item,
                   void* dproto, int lddp, void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
+/* ---- pose training (v8PoseLoss's keypoint terms; the pad staging of convs whose channels are no 16-byte multiple) -----------------
+ * The keypoint-location and keypoint-visibility terms of v8PoseLoss, forward and gradient (utils/loss.py:396-412 KeypointLoss,
+ * :791-870 kpts_decode + calculate_keypoints_loss), on the anchors the detection loss has assigned.  kpts[l]: the raw cv4 map of level
+ * l, NHWC (b, hs[l], ws[l], c), c >= nk = nkpt * ndim, row stride lds[l]; dkpts[l] its gradient, row stride ldds[l].  assign_gt /
+ * assign_stride / gt / n_gt / max_gt as upa_mask_loss takes them (a row < 0 or >= n_gt[b]: background); gt_kpt: (b, max_gt, nkpt, 3)
+ * f32 [x, y, visibility] in pixels, in gt's rows; strides (n_levels) and sigma (nkpt) are HOST arrays.  For a foreground anchor at
+ * cell (x, y) of a level with stride s and gt row g:
+ *   px = 2 vx + x, py = 2 vy + y;  gx = gt_kpt.x / s, gy = gt_kpt.y / s;  area = (x2 / s - x1 / s) (y2 / s - y1 / s);
+ *   m_k = [vis_k != 0] (ndim 2: 1);  e_k = ((px - gx)^2 + (py - gy)^2) / ((2 sigma_k)^2 (area + 1e-9) 2);  factor = nkpt / (sum m_k + 1e-9)
+ *   loss_items[0] = gain_pose * sum_fg factor sum_k (1 - exp(-e_k)) m_k / (n_fg nkpt)
+ *   loss_items[1] = gain_kobj * sum_fg sum_k BCEWithLogits(v_vis_k, m_k) / (n_fg nkpt)      (ndim 3, else 0)
+ * with n_fg the batch's foreground count (0: both items 0).  dkpts are the gradients of (items[0] + items[1]) * b * grad_scale *
+ * (*grad_scale_dev, NULL = 1); EVERY element of every row is written over the full c columns: background rows and the columns nk..c
+ * are zero.  No floating-point atomics: two runs agree in every bit.  UPA_EUNSUPPORTED before the first launch: ndim outside {2, 3},
+ * nk > 128, dtype outside f32 | bf16, c / ldds[l] / a dkpts[l] address that is no 16-byte multiple. */
+size_t upa_kpt_loss_workspace_bytes(int b, int n_anchors);
+int upa_kpt_loss(const void* const* kpts, void* const* dkpts, const int* hs, const int* ws, const int* lds, const int* ldds,
+                 int n_levels, int b, int c, int nkpt, int ndim, const int32_t* assign_gt, int assign_stride, const float* gt,
+                 const int* n_gt, int max_gt, const float* gt_kpt, const float* strides, const float* sigma, float gain_pose,
+                 float gain_kobj, float grad_scale, const float* grad_scale_dev, float* loss_items, void* workspace,
+                 size_t workspace_bytes, int dtype, void* stream);
+/* Zero-padded f32 copies of parameter tensors, for every padded conv of a model in one launch per direction.  A tensor is
+ * (rows, cols, inner) (a weight: cout, cin, k * k; a vector: c, 1, 1) and its padded copy (prows >= rows, pcols >= cols, inner).
+ *   scatter = 0: padded = master inside (rows, cols) and 0 in the pad (UPA_PAD_GATHER), or 0 everywhere (no UPA_PAD_GATHER: a gradient
+ *                that the step's backward accumulates into);
+ *   scatter = 1: master = padded's real rows (UPA_PAD_SCATTER_COPY: running statistics) or master += them (UPA_PAD_SCATTER_ADD:
+ *                gradients); descriptors with neither flag are skipped. */
+enum { UPA_PAD_GATHER = 1, UPA_PAD_SCATTER_COPY = 2, UPA_PAD_SCATTER_ADD = 4 };
+typedef struct UpaPadDesc {
+  float* master;
+  float* padded;
+  int rows, cols, inner, prows, pcols, flags;
+} UpaPadDesc;
+int upa_pad_copy_batched(const UpaPadDesc* descs_dev, int n, int scatter, void* stream);
+
 /* ---- segmentation validation: mask IoU and mask true positives on bit masks ----------------------------------------------------
  * Bit layout of every entry below: a mask of mh x mw pixels is words = ceil(mh * mw / 32) uint32, bit k of word w = pixel 32 w + k
  * in row-major order.  Bits past mh * mw in the last word are zero when one of these entries writes them; every reader masks them

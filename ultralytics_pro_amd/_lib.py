@@ -17,6 +17,7 @@ UPA_F32, UPA_BF16, UPA_U8_BGR_HWC = 0, 1, 2
 UPA_EINVAL = -1
 UPA_EUNSUPPORTED = -2
 ACT_NONE, ACT_SILU, ACT_RELU = 0, 1, 2
+UPA_PAD_GATHER, UPA_PAD_SCATTER_COPY, UPA_PAD_SCATTER_ADD = 1, 2, 4  # UpaPadDesc.flags (upa_pad_copy_batched)
 MASKS_PLANES, MASKS_OVERLAP = 0, 1          # upa_pack_mask_bits: source form
 MASK_U8, MASK_F32, MASK_I32 = 0, 1, 2       # ... and source element type
 
@@ -242,6 +243,10 @@ PROTOTYPES = {
     "upa_mask_loss_workspace_bytes": (_sz, [_i, _i]),
     "upa_mask_loss": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _vp,
                            _vp, _vp, _i, _vp, _sz, _i, _vp]),
+    "upa_kpt_loss_workspace_bytes": (_sz, [_i, _i]),
+    "upa_kpt_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp,
+                          _sz, _i, _vp]),
+    "upa_pad_copy_batched": (_i, [_vp, _i, _i, _vp]),
     "upa_pack_mask_bits": (_i, [_vp, _i, _i, C.c_long, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "upa_mask_iou_bits": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _f, _vp, _vp]),
     "upa_segment_match_workspace_bytes": (_sz, [_i, _i]),

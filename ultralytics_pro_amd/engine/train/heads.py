@@ -11,13 +11,14 @@ from ... import _lib as L
 from ...nn.modules import head as H
 from .. import runtime as R
 from .ctx import _new, _s
-from .layers import ConvT, DWConvT, ProtoT
+from .layers import ConvT, DWConvT, PadConvT, ProtoT
 
 
-def _branch(ctx, seq, name):
-    """Conv, Conv, nn.Conv2d: one yolov8 head branch (cv2 / legacy cv3 / cv4 of a level)."""
-    return [ConvT.from_module(ctx, seq[0], name + ".0"), ConvT.from_module(ctx, seq[1], name + ".1"),
-            ConvT(ctx, seq[2], None, L.ACT_NONE, name + ".2")]
+def _branch(ctx, seq, name, op=ConvT, first=None):
+    """Conv, Conv, nn.Conv2d: one yolov8 head branch (cv2 / legacy cv3 / cv4 of a level).  `op`: the conv op's type (`PadConvT` for a
+    chain whose channels are no 16-byte multiple); `first`: keyword arguments of the first op alone (its input is the neck's map)."""
+    return [op.from_module(ctx, seq[0], name + ".0", **(first or {})), op.from_module(ctx, seq[1], name + ".1"),
+            op(ctx, seq[2], None, L.ACT_NONE, name + ".2")]
 
 
 class DetectT:
@@ -29,6 +30,10 @@ class DetectT:
         self.ctx = ctx
         self.m, self.tr = m, trainer
         self.nl, self.nc, self.reg_max, self.no = m.nl, m.nc, m.reg_max, m.no
+        # nc classes that are no 16-byte channel group of the trainer's dtype (a pose model's nc = 1), which the last conv's row stores
+        # refuse: the class branch's last conv runs on `PadConvT` and the raw maps are `nop` channels wide - the loss reads and writes
+        # the first `no` of each row, the rest stays zero.  Every nc the plain `ConvT` takes keeps it (nop = no).
+        self.nop = 4 * m.reg_max + (m.nc + 7) // 8 * 8 if (m.legacy_cls and m.nc % ctx.E) else m.no
         self.br = []
         for i in range(m.nl):
             row = []
@@ -42,7 +47,10 @@ class DetectT:
                         ops.append(ConvT.from_module(ctx, pw, f"{name}.{tag}.{i}.{j}.1"))
                     row.append(ops + [ConvT(ctx, seq[2], None, L.ACT_NONE, f"{name}.{tag}.{i}.2")])
                     continue
-                row.append(_branch(ctx, seq, f"{name}.{tag}.{i}"))
+                ops = _branch(ctx, seq, f"{name}.{tag}.{i}")
+                if tag == "cv3" and self.nop != self.no:
+                    ops[-1] = PadConvT(ctx, seq[2], None, L.ACT_NONE, f"{name}.{tag}.{i}.2", pad_cin=False)
+                row.append(ops)
             self.br.append(row)
 
     def convs(self):
@@ -57,7 +65,7 @@ class DetectT:
 
         def level(i, x):
             n, _, h, w = x.shape
-            raw = _new(n, self.no, h, w, c.dtype, dev, (id(self), "raw", i))
+            raw = _new(n, self.nop, h, w, c.dtype, dev, (id(self), "raw", i))
             for k, (seq, out) in enumerate(zip(self.br[i], (raw[:, :nb], raw[:, nb:]))):
                 t = x
                 for op in seq[:-1]:
@@ -67,7 +75,7 @@ class DetectT:
             if c.dtype == torch.float32:
                 self.raw32[i] = raw
             else:  # the loss reads f32 maps
-                r32 = _new(n, self.no, h, w, torch.float32, dev, (id(self), "raw32", i))
+                r32 = _new(n, self.nop, h, w, torch.float32, dev, (id(self), "raw32", i))
                 vs, vd = R.view_of(raw), R.view_of(r32)
                 L.check(L.lib().upa_cast_view(vs.ptr, vs.dtype, vs.ld, vd.ptr, vd.dtype, vd.ld, vs.n * vs.h * vs.w, vs.c,
                                               _s(dev)), "cast_view")
@@ -129,6 +137,8 @@ class DetectT:
         for i, r in enumerate(self.raw32):
             n, ch, hh, ww = r.shape
             grads32.append(_new(n, ch, hh, ww, torch.float32, dev, (id(self), "graw32", i)))
+            if self.nop != self.no:
+                grads32[-1].zero_()  # the loss writes `no` columns of each row: the pad columns feed the padded conv's backward as zeros
         nl = self.nl
         FP = C.c_void_p * nl
         feats = FP(*[R.view_of(r).ptr for r in self.raw32])
@@ -175,6 +185,11 @@ class DetectT:
 
         # as in the forward pass: the small levels' chains beside the 80 x 80 level's (they write the gradients of different neck outputs)
         self._fork_levels(lambda: level_bwd(0), lambda: [level_bwd(i) for i in range(1, nl)], nl > 1)
+        if tr._pad_table()[1]:
+            # the staged gradients and running statistics of the padded convs go back to the module's tensors once every weight
+            # gradient of the head has been enqueued: behind the side streams, in front of the gradient buckets of the head's layer
+            tr._join_wgrad()
+            tr._pad_scatter()
         return items
 
 
@@ -246,6 +261,73 @@ class SegmentT(DetectT):
         seq[0].backward(g, dx, True)
         if i == 0:
             self.proto.backward(self.dp, dx, True)
+
+
+class PoseT(DetectT):
+    """Train-mode Pose (head.py:1208-1273 returns the raw maps and the raw keypoint maps) + v8PoseLoss (utils/loss.py:712-870) + its
+    gradient: `DetectT` with, per level, the cv4 chain (Conv 3x3, Conv 3x3, Conv2d 1x1 -> nk) on `PadConvT` - c4 and nk (51 for the
+    17 x 3 skeleton) are no 16-byte multiples, the chain runs at the channel counts rounded up to `Pose.PAD` with zero pad channels.
+    The keypoint terms are upa_kpt_loss on the detection loss's workspace (the per-anchor assignment is read in place); it reads the
+    padded raw map in the trainer's dtype and writes zero pad columns, so every pad gradient of the chain is an exact zero.  Loss
+    items: (box, pose, kobj, cls, dfl)."""
+
+    def __init__(self, ctx, m: H.Pose, name, trainer):
+        super().__init__(ctx, m, name, trainer)
+        self.nkpt, self.ndim = (int(v) for v in m.kpt_shape)
+        self.nk = self.nkpt * self.ndim
+        self.cv4 = [_branch(ctx, seq, f"{name}.cv4.{i}", op=PadConvT, first=dict(pad_cin=False)) for i, seq in enumerate(m.cv4)]
+        self.kp = [None] * m.nl
+        from ...utils.metrics import OKS_SIGMA
+        sig = OKS_SIGMA if tuple(m.kpt_shape) == (17, 3) else [1.0 / self.nkpt] * self.nkpt  # loss.py:720-722
+        self.sigma = (C.c_float * self.nkpt)(*[float(v) for v in sig])
+
+    def convs(self):
+        return super().convs() + [cv for seq in self.cv4 for cv in seq]
+
+    def _level_more(self, i, x):
+        t = x
+        for op in self.cv4[i]:
+            t = op.forward(t)
+        self.kp[i] = t
+
+    def _more_losses(self, items, wsb, batch_size, n_anchors, max_gt):
+        c, tr, lib = self.ctx, self.tr, L.lib()
+        dev = c.device
+        nl = self.nl
+        self.dkp = [_new(*[int(v) for v in t.shape], c.dtype, dev, (id(self), "dkp", i)) for i, t in enumerate(self.kp)]
+        vk, vd = [R.view_of(t) for t in self.kp], [R.view_of(t) for t in self.dkp]
+        FP, IA = C.c_void_p * nl, C.c_int * nl
+        kpts, dkpts = FP(*[v.ptr for v in vk]), FP(*[v.ptr for v in vd])
+        hs, ws = IA(*[v.h for v in vk]), IA(*[v.w for v in vk])
+        lds, ldds = IA(*[v.ld for v in vk]), IA(*[v.ld for v in vd])
+        strides = (C.c_float * nl)(*[float(s) for s in self.m.stride])
+        kpt_d = tr.kpt_d
+        if kpt_d is None or tuple(kpt_d.shape) != (batch_size, max_gt, self.nkpt, 3):
+            raise L.UpaError(f"keypoint buffer {None if kpt_d is None else tuple(kpt_d.shape)} does not match the step: "
+                             f"{(batch_size, max_gt, self.nkpt, 3)}")
+        asg = lib.upa_detection_loss_assignment(wsb.data_ptr(), batch_size, n_anchors, max_gt)
+        nws = lib.upa_kpt_loss_workspace_bytes(batch_size, n_anchors)
+        kws = tr.pool.get(("kpt_loss_ws", batch_size, n_anchors), (nws,), torch.uint8, dev)
+        items5 = tr.pool.get(("loss_items5",), (5,), torch.float32, dev)
+        L.check(lib.upa_kpt_loss(C.cast(kpts, C.c_void_p), C.cast(dkpts, C.c_void_p), C.cast(hs, C.c_void_p), C.cast(ws, C.c_void_p),
+                                 C.cast(lds, C.c_void_p), C.cast(ldds, C.c_void_p), nl, batch_size, vk[0].c, self.nkpt, self.ndim, asg, 2,
+                                 tr.gt_d.data_ptr(), tr.ngt_d.data_ptr(), max_gt, kpt_d.data_ptr(), C.cast(strides, C.c_void_p),
+                                 C.cast(self.sigma, C.c_void_p), tr.hyp["pose"], tr.hyp["kobj"], 1.0, tr.scaler.ptr(),
+                                 items5.data_ptr() + 4, kws.data_ptr(), nws, c.code, _s(dev)), "kpt_loss")
+        # (box, pose, kobj, cls, dfl), loss.py:727: box and [cls, dfl] of the detection items around the two items written above
+        L.check(lib.upa_copy_rows(items.data_ptr(), 1, 1, 3, items5.data_ptr(), 5, _s(dev)), "copy_rows")
+        L.check(lib.upa_copy_rows(items.data_ptr() + 4, 1, 2, 3, items5.data_ptr() + 12, 5, _s(dev)), "copy_rows")
+        return items5
+
+    def _level_more_bwd(self, i, dx):
+        c = self.ctx
+        seq, g = self.cv4[i], self.dkp[i]
+        for j in range(len(seq) - 1, 0, -1):
+            vt = R.view_of(seq[j].x)
+            d = _new(vt.n, vt.c, vt.h, vt.w, c.dtype, c.device, (id(self), "d4", i, j))
+            seq[j].backward(g, d, False)
+            g = d
+        seq[0].backward(g, dx, True)
 
 
 class ClassifyT:

@@ -230,6 +230,86 @@ class ConvT(_Block):
         self._conv(src, self.wpt, self.cin, self.k, 1, self.k - 1 - self.p, dx, residual=dx if accumulate else None)
 
 
+class PadConvT(ConvT):
+    """`ConvT` of a conv whose input and / or output channels are no multiple of the kernels' 16-byte channel group (the Pose head's
+    51-channel cv4 chain): the kernels run at the channel counts rounded up to `pad` and the op owns zero-padded f32 STAGING of every
+    tensor they read or write at that width - the weight, gamma, beta, the running statistics (the plain last conv: the bias) and
+    their gradients.  The module's parameters and buffers keep their shapes, so the state_dict and the trainer's flat layout do not
+    change.  Once per step, for every padded op of the model together (`pad_descs`, upa_pad_copy_batched):
+      gather   before the repack: staging = masters, zeros in the pad; gradient staging = zeros;
+      scatter  after the backward: master gradients += the staging's real rows; running statistics copied back.
+    Pad filters, biases and gamma / beta are zero, so pad activations are act(0) = 0 and pad gradients are exact zeros as long as the
+    gradient that enters the chain has zero pad columns (upa_kpt_loss writes them)."""
+
+    def __init__(self, ctx: _Ctx, conv: nn.Conv2d, bn, act_code: int, name: str, pad_cin: bool = True, pad_cout: bool = True, pad: int = 8):
+        from types import SimpleNamespace as NS
+        up = (lambda v, on: (v + pad - 1) // pad * pad if on else v)
+        self.real = (conv.out_channels, conv.in_channels)
+        co, ci = up(conv.out_channels, pad_cout), up(conv.in_channels, pad_cin)
+        kk = conv.kernel_size[0] * conv.kernel_size[1]
+        dev = ctx.device
+        self._descs = []
+
+        def staged(master, shape, real, flags, grad=True):
+            """A zero staging tensor of `shape` for `master` (viewed as `real` = (rows, cols, inner)) with its gradient staging."""
+            t = torch.zeros(shape, dtype=torch.float32, device=dev)
+            prows, pcols = (shape[0], shape[1]) if len(shape) > 1 else (shape[0], 1)
+            self._descs.append((master.data_ptr(), t.data_ptr()) + real + (prows, pcols, flags))
+            if grad:
+                t.grad = torch.zeros(shape, dtype=torch.float32, device=dev)
+                self._descs.append((master.grad.data_ptr(), t.grad.data_ptr()) + real + (prows, pcols, L.UPA_PAD_SCATTER_ADD))
+            return t
+
+        w = staged(conv.weight, (co, ci) + tuple(conv.kernel_size), self.real + (kk,), L.UPA_PAD_GATHER)
+        vec = (lambda p, flags=L.UPA_PAD_GATHER, grad=True: staged(p, (co,), (conv.out_channels, 1, 1), flags, grad))
+        sconv = NS(weight=w, bias=None if conv.bias is None else vec(conv.bias), groups=conv.groups, dilation=conv.dilation,
+                   kernel_size=conv.kernel_size, stride=conv.stride, padding=conv.padding, out_channels=co, in_channels=ci)
+        sbn = None
+        if bn is not None:
+            back = L.UPA_PAD_GATHER | L.UPA_PAD_SCATTER_COPY
+            sbn = NS(weight=vec(bn.weight), bias=vec(bn.bias), running_mean=vec(bn.running_mean, back, False),
+                     running_var=vec(bn.running_var, back, False), eps=bn.eps, momentum=bn.momentum)
+        self.module_conv, self.module_bn = conv, bn
+        super().__init__(ctx, sconv, sbn, act_code, name)
+
+    def pad_descs(self):
+        """(master, padded, rows, cols, inner, padded rows, padded cols, flags) of every staged tensor: the rows of `UpaPadDesc`."""
+        return list(self._descs)
+
+    def staging(self):
+        """{name: (padded tensor, real rows, real columns)} of everything staged, gradients included (tests, debugging)."""
+        co, ci = self.real
+        out = {"weight": (self.conv.weight, co, ci), "weight.grad": (self.conv.weight.grad, co, ci)}
+        vecs = {"bias": self.conv.bias} if self.bn is None else {"bn.weight": self.bn.weight, "bn.bias": self.bn.bias,
+                                                                  "bn.running_mean": self.bn.running_mean,
+                                                                  "bn.running_var": self.bn.running_var}
+        for k, t in vecs.items():
+            out[k] = (t, co, 1)
+            if getattr(t, "grad", None) is not None:
+                out[k + ".grad"] = (t.grad, co, 1)
+        return out
+
+
+def pad_table(ops, device):
+    """The device descriptor table (`UpaPadDesc` rows) of the padded ops among `ops`, and its length; (None, 0) without one."""
+    import numpy as np
+    rows = [d for op in ops if isinstance(op, PadConvT) for d in op.pad_descs()]
+    if not rows:
+        return None, 0
+    t = np.zeros(len(rows), dtype=np.dtype([("master", "<u8"), ("padded", "<u8"), ("rows", "<i4"), ("cols", "<i4"), ("inner", "<i4"),
+                                            ("prows", "<i4"), ("pcols", "<i4"), ("flags", "<i4")]))
+    for i, r in enumerate(rows):
+        t[i] = r
+    return torch.from_numpy(t.view(np.uint8).copy()).to(device), len(rows)
+
+
+def pad_copy(table, n, scatter: bool, device):
+    """One launch over the table: gather (masters -> staging, zeros in the pad and in the gradient staging) or scatter (staged
+    gradients added to the masters', running statistics copied back)."""
+    if n:
+        L.check(L.lib().upa_pad_copy_batched(table.data_ptr(), n, int(scatter), _s(device)), "pad_copy_batched")
+
+
 class DWConvT(_Block):
     """Train-mode forward/backward of one DWConv (conv.py:411-425: depthwise 3x3, stride 1, pad 1 + BatchNorm2d + SiLU | none) - the class
     branch of the non-legacy Detect head (head.py:98-110).  The `ConvT` surface; the weight stays the module's (C, 1, 3, 3) f32 master

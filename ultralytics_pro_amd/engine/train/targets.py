@@ -68,6 +68,29 @@ def pack_mask_ids(labels, batch_size, imgsz_h, imgsz_w, rows):
     return mid
 
 
+def pack_keypoints(labels, batch_size, imgsz_h, imgsz_w, rows, kpt_shape):
+    """The sibling of `pack_targets` for `batch["keypoints"]`, (n, nkpt, ndim) normalised [x, y(, visibility)]: (B, rows, nkpt, 3)
+    float32 [x, y, visibility] in pixels (loss.py:775-777), for every gt row `pack_targets` keeps the keypoints of that label (zeros
+    in the unused rows); ndim 2 gets visibility 1 (loss.py:864).  The boxes `pack_targets` drops are dropped here by the same rule
+    (`_pixel_boxes`), so a zero box in front of a label does not move its keypoints off its gt row."""
+    nkpt, ndim = (int(v) for v in kpt_shape)
+    kp = torch.as_tensor(labels["keypoints"]).detach().cpu().float().view(-1, nkpt, ndim)
+    bi, _, keep = _pixel_boxes(labels, imgsz_h, imgsz_w)
+    if kp.shape[0] != bi.numel():
+        raise UpaError(f"{kp.shape[0]} keypoint rows for {bi.numel()} labels")
+    out = torch.zeros(batch_size, rows, nkpt, 3)
+    for j in range(batch_size):
+        ix = ((bi == j) & keep).nonzero().view(-1)
+        k = int(ix.numel())
+        if k > rows:
+            raise UpaError(f"image {j} keeps {k} boxes but the gt rows hold {rows}")
+        if k:
+            out[j, :k, :, 0] = kp[ix, :, 0] * imgsz_w
+            out[j, :k, :, 1] = kp[ix, :, 1] * imgsz_h
+            out[j, :k, :, 2] = kp[ix, :, 2] if ndim == 3 else 1.0
+    return out
+
+
 def pack_cls_targets(labels, batch_size, nc):
     """`batch["cls"]` of the reference's classification batch - (B,) integer class ids (models/yolo/classify/train.py
     preprocess_batch) - as a host int32 tensor.  A label outside [0, nc) is refused here (torch's cross_entropy fails on the host with

@@ -19,10 +19,10 @@ from .. import runtime as R
 from .attention import BoT3T, C2PSAT
 from .ctx import PinnedRing, _Ctx, _new, _s, add_into, copy_into
 from .graph import _Node, plan_concats
-from .heads import ClassifyT, DetectT, SegmentT
-from .layers import C2fT, C3k2T, C3T, ConvT, ConvTransposeT, DWConvT, SPPFT, UpsampleT
+from .heads import ClassifyT, DetectT, PoseT, SegmentT
+from .layers import C2fT, C3k2T, C3T, ConvT, ConvTransposeT, DWConvT, SPPFT, UpsampleT, pad_copy, pad_table
 from .optim import HYP, SCHED, GradScaler, _head_nc, resolve_optimizer
-from .targets import MASK_ID_MAX, MAX_GT, MAX_GT_CAP, pack_cls_targets, pack_mask_ids, pack_targets
+from .targets import MASK_ID_MAX, MAX_GT, MAX_GT_CAP, pack_cls_targets, pack_keypoints, pack_mask_ids, pack_targets
 
 # (module type, op type) of the composite layers, first match wins: a subclass stands in front of its base (C3k2 is a C2f, BoT3 a C3)
 _BLOCK_OPS = ((B.C3k2, C3k2T), (B.C2PSA, C2PSAT), (B.C2f, C2fT), (B.BoT3, BoT3T), (B.C3, C3T), (B.SPPF, SPPFT))
@@ -34,6 +34,7 @@ class DetectionTrainer:
     "auto" with `iterations` (`resolve_optimizer`); `optimizer_name` is the resolved one."""
 
     _segment_ok = False  # (SegmentationTrainer: True)
+    _pose_ok = False     # (PoseTrainer: True)
 
     def __init__(self, model, dtype=torch.bfloat16, hyp=None, device=None, world_size=1, ema=True, wgrad_streams: int = 1,
                  amp_scaler: bool = False, optimizer: str = "SGD", iterations=None, yolo11: bool = False):
@@ -43,8 +44,9 @@ class DetectionTrainer:
         if not self._segment_ok and any(isinstance(m, H.Segment) for m in model.modules()):
             raise L.UpaError("segmentation models (Segment head) have no training path on HIP in DetectionTrainer (v8DetectionLoss only): "
                              "train them with SegmentationTrainer")
-        if any(isinstance(m, H.Pose) for m in model.modules()):
-            raise L.UpaError("pose models (Pose head) have no training path on HIP: pose training (v8PoseLoss) is not built")
+        if not self._pose_ok and any(isinstance(m, H.Pose) for m in model.modules()):
+            raise L.UpaError("pose models (Pose head) have no training path on HIP in DetectionTrainer (v8DetectionLoss only): pose "
+                             "training (v8PoseLoss) is PoseTrainer's")
         for m in model.modules():
             if isinstance(m, H.Detect) and not m.legacy_cls:
                 if not yolo11:
@@ -79,6 +81,7 @@ class DetectionTrainer:
         self.schedule = None      # set_schedule(): warm-up interpolation + gradient accumulation of the reference's loop
         self.ni = 0               # iteration counter (the reference's `ni = i + nb * epoch`)
         self.last_opt_step = -1   # trainer.py:386
+        self._pad_tab, self._pad_n = None, None  # the descriptor table of the padded convs (`PadConvT`), built at the first step
         self.max_gt = MAX_GT  # rows per image of the padded gt tensor (the reference pads to counts.max(), loss.py:445-461)
         model.to(self.device)
         self._flatten_parameters(ema)
@@ -215,10 +218,23 @@ class DetectionTrainer:
                 "nchw_to_nhwc")
         return buf.permute(0, 3, 1, 2)
 
+    # the padded convs' staging (`PadConvT`: a Pose head's cv4 chains, the class branch of a head whose nc is no 16-byte group): one
+    # launch per direction and step; a model without one launches nothing
+    def _pad_table(self):
+        if self._pad_n is None:
+            self._pad_tab, self._pad_n = pad_table(self.convs, self.device)
+        return self._pad_tab, self._pad_n
+
+    def _pad_scatter(self):
+        tab, n = self._pad_table()
+        pad_copy(tab, n, True, self.device)
+
     def _pack_weights(self):
         """Repack every conv's master weights into the MFMA fragment layouts (forward, data gradient) - one launch for the
         whole model plus one per stride-2 conv (its four phase kernels).  The descriptor table is built once: the master
         weights are views of the flat parameter buffer and the packed buffers are owned by the layers."""
+        tab, n = self._pad_table()
+        pad_copy(tab, n, False, self.device)  # the staging the repack reads; the gradient staging starts the step at zero
         for cv in self.convs:
             cv.pack_phase_weights()
         if self._pack_table is None:
@@ -709,6 +725,77 @@ class ClassificationTrainer(DetectionTrainer):
         h_cls.copy_(cls)
         self.cls_d.copy_(h_cls, non_blocking=True)
         self._label_ring.commit(torch.cuda.current_stream(self.device))
+
+
+class PoseTrainer(DetectionTrainer):
+    """One-process-per-GPU trainer for a PoseModel (reference: models/yolo/pose/train.py on engine/trainer.py's loop; the loss is
+    v8PoseLoss, utils/loss.py:712-870).  Everything but the tail and the labels is DetectionTrainer's: the graph walk, `step`,
+    `compile` / replay, `set_schedule`, every optimizer, GradScaler, EMA and the multi-rank path.  The tail is `PoseT`; the labels
+    additionally carry `"keypoints"`, (n_labels, nkpt, ndim) normalised [x, y(, visibility)] in the rows of `"bboxes"`.  The gains
+    `pose` (12.0) and `kobj` (1.0) join the hyper-parameters here.  `step()` returns the (5,) loss items (box, pose, kobj, cls, dfl).
+    The cv4 chains' 51 channels train on `PadConvT`'s zero-padded staging: one gather launch in front of the weight repack and one
+    scatter launch behind the head's backward, both inside the captured step.
+    Refused, by the constructor or the label upload, before any launch: a model that does not end in Pose; a YOLO11 Pose head
+    (depthwise class branch), with or without yolo11=True - no golden pins it; labels without "keypoints"; a keypoint tensor that is
+    not (n_labels, *kpt_shape); non-finite keypoints."""
+
+    _pose_ok = True
+    POSE_HYP = dict(pose=12.0, kobj=1.0)  # cfg/default.yaml of the reference
+
+    def __init__(self, model, dtype=torch.bfloat16, hyp=None, device=None, world_size=1, ema=True, wgrad_streams: int = 1,
+                 amp_scaler: bool = False, optimizer: str = "SGD", iterations=None, yolo11: bool = False):
+        tail = model.model[-1] if hasattr(model, "model") and len(model.model) else None
+        if not isinstance(tail, H.Pose):
+            raise L.UpaError(f"PoseTrainer needs a model that ends in a Pose head, got {type(tail).__name__}")
+        if not tail.legacy_cls:
+            raise L.UpaError("Pose (YOLO11, non-legacy head with a depthwise class branch): PoseTrainer builds the yolov8 Pose head only, "
+                             "with or without yolo11=True - no golden record pins a YOLO11 pose step")
+        self.kpt_shape = tuple(int(v) for v in tail.kpt_shape)
+        self.kpt_d = None
+        self._kpt_ring = PinnedRing()
+        super().__init__(model, dtype=dtype, hyp=dict(self.POSE_HYP, **(hyp or {})), device=device, world_size=world_size, ema=ema,
+                         wgrad_streams=wgrad_streams, amp_scaler=amp_scaler, optimizer=optimizer, iterations=iterations, yolo11=yolo11)
+
+    def _tail_op(self, m, name):
+        if isinstance(m, H.Pose):
+            return PoseT(self.ctx, m, name, self)
+        return None
+
+    @staticmethod
+    def check_keypoints(labels, kpt_shape):
+        """The refusals of the label upload, on the host: returns the (n_labels, nkpt, ndim) float32 keypoints."""
+        if not isinstance(labels, dict) or "keypoints" not in labels:
+            raise L.UpaError('pose labels need "keypoints": (n_labels, nkpt, ndim) normalised [x, y(, visibility)]')
+        kp = torch.as_tensor(labels["keypoints"]).detach().cpu().float()
+        n = int(labels["bboxes"].view(-1, 4).shape[0])
+        if tuple(kp.shape) != (n,) + tuple(kpt_shape):
+            raise L.UpaError(f"keypoints of shape {tuple(kp.shape)} for {n} labels of a model with kpt_shape {tuple(kpt_shape)}: "
+                             f"expected {(n,) + tuple(kpt_shape)}")
+        if not bool(torch.isfinite(kp).all()):
+            raise L.UpaError("keypoints hold non-finite values")
+        return kp
+
+    def _upload_labels(self, labels, batch_size):
+        imgsz_h, imgsz_w = self._imgsz
+        # every refusal comes before anything is uploaded: the keypoints are checked and packed (into as many rows as the image with
+        # the most labels has) first, then the gt rows go up, then the keypoints are laid out in the gt buffer's row count
+        self.check_keypoints(labels, self.kpt_shape)
+        bi = labels["batch_idx"].view(-1).cpu().long()
+        most = max([int((bi == j).sum()) for j in range(batch_size)] + [1])
+        kp0 = pack_keypoints(labels, batch_size, imgsz_h, imgsz_w, most, self.kpt_shape)
+        super()._upload_labels(labels, batch_size)
+        rows = int(self.gt_d.shape[1])
+        shape = (batch_size, rows, self.kpt_shape[0], 3)
+        if self.kpt_d is None or tuple(self.kpt_d.shape) != shape:
+            if self._graphs is not None or self._capturing:
+                raise L.UpaError(f"keypoints of {rows} gt rows for {batch_size} images do not match the compiled step's buffer "
+                                 f"{None if self.kpt_d is None else tuple(self.kpt_d.shape)}")
+            self.kpt_d = torch.zeros(shape, dtype=torch.float32, device=self.device)
+        (h_kp,) = self._kpt_ring.stage([(shape, torch.float32)])
+        h_kp[:, :min(rows, most)].copy_(kp0[:, :rows])
+        h_kp[:, min(rows, most):].zero_()  # (never read - n_gt bounds the rows - but a reused slot must not carry an earlier batch)
+        self.kpt_d.copy_(h_kp, non_blocking=True)
+        self._kpt_ring.commit(torch.cuda.current_stream(self.device))
 
 
 class SegmentationTrainer(DetectionTrainer):

@@ -633,7 +633,7 @@ class Pose(Detect):
     filters (their products add exact zeros: the real channels are bit-identical to an unpadded convolution).
 
     Scheduling follows Segment: a level's cv4 branch runs when `start_level` is called for it, the rest in `forward`.  Inference only:
-    a train-mode forward raises (pose training, v8PoseLoss, is not built)."""
+    a train-mode forward raises (pose training, v8PoseLoss, is `engine.trainer.PoseTrainer`'s: its `PoseT` op holds the train-mode head)."""
 
     cat_out = True
     PAD = 8  # channels per 16 bytes of bf16; a multiple of f32's 4, so one padded layout serves both dtypes
@@ -733,7 +733,8 @@ class Pose(Detect):
 
     def forward(self, x):
         if self.training:
-            raise L.UpaError("training-mode Pose.forward is not on the HIP path: pose training (v8PoseLoss) is not built")
+            raise L.UpaError("training-mode Pose.forward is not on the HIP path: pose training (v8PoseLoss) goes through "
+                             "engine.trainer.PoseTrainer (its PoseT op holds the train-mode head)")
         det = super().forward(x)
         y, raw = (det, None) if self.export else det
         tag = R.current_tag()
