@@ -184,7 +184,10 @@ def _run_detect(case, d):
     return y.cpu(), keys.cpu(), a0
 
 
-@pytest.mark.parametrize("ci,fam", [p for p in PARAMS if B.CASES[p.values[0]]["form"] == "detect"])
+TWINS_PARAMS = [pytest.param(i, "twins", id=f"{B.CASES[i]['id']}-twins") for i in B.TWINS_CASES]
+
+
+@pytest.mark.parametrize("ci,fam", [p for p in PARAMS if B.CASES[p.values[0]]["form"] == "detect"] + TWINS_PARAMS)
 @KC.stop_after_fault
 def test_detect_level_stream_vs_f64_chain(ci, fam):
     case = B.CASES[ci]
@@ -225,4 +228,11 @@ def test_detect_level_stream_vs_f64_chain(ci, fam):
     clear = (top[:, 0] - top[:, 1]) > es.gather(1, idx).sum(1)
     assert bool((kcls == idx[:, 0])[clear].all()), "best class differs where the reference decides it"
     stats.append(("key class decided", float(clear.float().mean()), 0.0))
+    if fam == "twins":
+        # ties made by construction (block_ref.TWIN_GROUPS / TWIN_SAT): the first index of identical rows, the larger bias of a 2^-14 /
+        # 2^-13 pair, the first of the rows that all score 1.0f
+        want, decided = B.twins_answer(cl, ce)
+        assert bool(decided[:, :3].all()) and bool((want == B.TWIN_SAT[0])[:, :3].all())  # (the dark columns: anchors 0..2 of row 0)
+        assert bool((kcls == want)[decided].all()), "best class differs from the constructed answer"
+        stats.append(("key class constructed", float(decided.float().mean()), 0.0))
     _report(stats, case, fam)

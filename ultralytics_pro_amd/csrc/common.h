@@ -132,13 +132,18 @@ int upa_num_cus();
 // initialisation: thread safe, no API call on later launches, and no launch ever lowers a limit another launch - or a
 // captured graph node - relies on).
 template <auto Kern>
-inline hipError_t upa_full_lds() {
-  static const hipError_t e = [] {
+inline int upa_full_lds_room() {  // the dynamic LDS bytes upa_full_lds<Kern> grants; hosts that size their LDS by an argument check against it
+  static const int room = [] {
     hipFuncAttributes fa;
-    int room = 160 * 1024;
-    if (hipFuncGetAttributes(&fa, (const void*)Kern) == hipSuccess) room -= (int)fa.sharedSizeBytes;  // static __shared__
-    return hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, room);
+    int r = 160 * 1024;
+    if (hipFuncGetAttributes(&fa, (const void*)Kern) == hipSuccess) r -= (int)fa.sharedSizeBytes;  // static __shared__
+    return r;
   }();
+  return room;
+}
+template <auto Kern>
+inline hipError_t upa_full_lds() {
+  static const hipError_t e = hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, upa_full_lds_room<Kern>());
   return e;
 }
 

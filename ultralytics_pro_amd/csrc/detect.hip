@@ -122,22 +122,27 @@ extern "C" int upa_detect_decode(const void* box, int ldb, const void* cls, int 
   UPA_CHECK_ARG(ldb % E == 0 && ldc % E == 0 && nc >= 1, "detect_decode: row strides must be multiples of 16 bytes");
   UPA_CHECK_ARG(ldc >= (nc + E - 1) / E * E, "detect_decode: class row shorter than nc rounded up to 16 bytes");
   UPA_CHECK_ARG(a0 >= 0 && a0 + h * w <= a_total, "detect_decode: level does not fit a_total");
-  UPA_CHECK_ARG(nc <= 512, "detect_decode: nc too large for the LDS row");
   const long total = (long)n * h * w;
   constexpr int WAVES = 2;
-  int gcp = 1;
-  while (gcp < (nc + E - 1) / E) gcp <<= 1;
+  long gcp = 1;
+  while (gcp < ((long)nc + E - 1) / E) gcp <<= 1;
   const int gb = 4 * 16 / E;
+  // the kernel keeps 64 anchors' rows per wave in LDS: f32 fits nc <= 256, bf16 nc <= 512 (the next power of two of groups is 288 KB).
+  // Checked against the very room upa_full_lds grants, before anything is launched
   const size_t lds = (size_t)WAVES * 64 * (gb + gcp) * 16;
   dim3 grid((unsigned)((total + WAVES * 64 - 1) / (WAVES * 64)));
   hipStream_t s = (hipStream_t)stream;
   if (dtype == UPA_BF16) {
     auto kern = detect_decode_kernel<bf16_t, 16, WAVES>;
+    const size_t room = (size_t)upa_full_lds_room<detect_decode_kernel<bf16_t, 16, WAVES>>();
+    UPA_CHECK_ARG(lds <= room, "detect_decode: nc = %d (bf16) needs %zu bytes of LDS per workgroup, the CU has %zu", nc, lds, room);
     (void)upa_full_lds<detect_decode_kernel<bf16_t, 16, WAVES>>();
     hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), lds, s, (const char*)box, ldb, (const char*)cls, ldc, n, h, w, nc,
                        stride_px, y, a_total, a0);
   } else {
     auto kern = detect_decode_kernel<float, 16, WAVES>;
+    const size_t room = (size_t)upa_full_lds_room<detect_decode_kernel<float, 16, WAVES>>();
+    UPA_CHECK_ARG(lds <= room, "detect_decode: nc = %d (f32) needs %zu bytes of LDS per workgroup, the CU has %zu", nc, lds, room);
     (void)upa_full_lds<detect_decode_kernel<float, 16, WAVES>>();
     hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), lds, s, (const char*)box, ldb, (const char*)cls, ldc, n, h, w, nc,
                        stride_px, y, a_total, a0);
