@@ -442,5 +442,5 @@ def test_pose_cat_out_switch():
             m.model[-1].cat_out = True
     torch.cuda.synchronize()
     assert y.shape == (1, 5, 2100) and cat.shape == (1, 56, 2100) and kpt.shape == (1, 51, 2100)
-    assert torch.equal(cat[:, :5], y) and torch.equal(cat[:, 5:], y._upa_pose) and torch.equal(kpt, kpt2)
+    assert torch.equal(cat[:, :5], y) and torch.equal(cat[:, 5:], y._upa_parts[1]) and torch.equal(kpt, kpt2)
     assert int(r_cat[1].sum()) > 0 and torch.equal(r_cat[0], r_y[0]) and torch.equal(r_cat[1], r_y[1])

@@ -21,6 +21,18 @@ def _branch(ctx, seq, name, op=ConvT, first=None):
             op(ctx, seq[2], None, L.ACT_NONE, name + ".2")]
 
 
+def _chain_backward(ctx, seq, dy, dx, acc, key):
+    """Backward of a chain of ops from its output gradient dy: the inner gradients get one buffer per op input (`key + (j,)`), the first
+    op writes (`acc`: accumulates) into dx."""
+    g = dy
+    for j in range(len(seq) - 1, 0, -1):
+        vt = R.view_of(seq[j].x)
+        d = _new(vt.n, vt.c, vt.h, vt.w, ctx.dtype, ctx.device, key + (j,))
+        seq[j].backward(g, d, False)
+        g = d
+    seq[0].backward(g, dx, acc)
+
+
 class DetectT:
     """Train-mode Detect (head.py:116-126 returns the raw per-level maps) + v8DetectionLoss + its gradient."""
 
@@ -109,7 +121,7 @@ class DetectT:
         first()
         main.wait_event(done)
 
-    # the hooks of a head with more branches on the same level inputs (`SegmentT`)
+    # the hooks of a head with more branches on the same level inputs (`ExtraDetectT`)
     def _level_more(self, i, x):
         """Further train-mode branches of level i's input x, run on that level's stream."""
 
@@ -174,13 +186,7 @@ class DetectT:
             src = tr.nodes[self.m.f[i]]
             dx, acc = tr._grad_of(src)
             for k, (seq, dy) in enumerate(zip(self.br[i], (graw[:, :nb], graw[:, nb:]))):
-                g = dy
-                for j in range(len(seq) - 1, 0, -1):  # the chain's inner gradients: one buffer per op input
-                    vt = R.view_of(seq[j].x)
-                    d = _new(vt.n, vt.c, vt.h, vt.w, c.dtype, dev, (id(self), "d", i, k, j))
-                    seq[j].backward(g, d, False)
-                    g = d
-                seq[0].backward(g, dx, acc or k > 0)
+                _chain_backward(c, seq, dy, dx, acc or k > 0, (id(self), "d", i, k))
             self._level_more_bwd(i, dx)
 
         # as in the forward pass: the small levels' chains beside the 80 x 80 level's (they write the gradients of different neck outputs)
@@ -193,93 +199,19 @@ class DetectT:
         return items
 
 
-class SegmentT(DetectT):
-    """Train-mode Segment (head.py:790-837 returns the raw maps, the mask coefficients and the prototypes) + v8SegmentationLoss
-    (utils/loss.py:531-709) + its gradient: `DetectT` with, per level, the cv4 chain (Conv 3x3, Conv 3x3, Conv2d 1x1 -> nm) and, on
-    level 0's input, `ProtoT`.  The mask term is upa_mask_loss on the detection loss's workspace (the per-anchor assignment is read in
-    place); cv4 and Proto backpropagate into the same neck gradients as cv2 / cv3.  Loss items: (box, seg, cls, dfl)."""
+class ExtraDetectT(DetectT):
+    """Train-mode head with one more per-level branch: `DetectT` with, per level, the cv4 chain (Conv 3x3, Conv 3x3, Conv2d 1x1) on
+    ops of `conv_op`, whose maps (`self.extra`) feed a second loss term.  That term (a subclass's `_more_losses`) runs on the detection
+    loss's workspace - the per-anchor assignment is read in place -, writes the maps' gradients (`self.dextra`, buffers under
+    `grad_key`) and its loss items between box and [cls, dfl]; cv4 backpropagates into the same neck gradients as cv2 / cv3."""
 
-    def __init__(self, ctx, m: H.Segment, name, trainer):
+    conv_op, first = ConvT, None  # `_branch`'s op type and the first op's keyword arguments
+    grad_key = None
+
+    def __init__(self, ctx, m, name, trainer):
         super().__init__(ctx, m, name, trainer)
-        self.nm = m.nm
-        self.cv4 = [_branch(ctx, seq, f"{name}.cv4.{i}") for i, seq in enumerate(m.cv4)]
-        self.proto = ProtoT(ctx, m.proto, name + ".proto")
-        self.mc = [None] * m.nl
-        self.p = None
-
-    def convs(self):
-        return super().convs() + [cv for seq in self.cv4 for cv in seq] + self.proto.convs()
-
-    def _level_more(self, i, x):
-        t = x
-        for op in self.cv4[i]:
-            t = op.forward(t)
-        self.mc[i] = t
-        if i == 0:
-            self.p = self.proto.forward(x)
-
-    def _more_losses(self, items, wsb, batch_size, n_anchors, max_gt):
-        c, tr, lib = self.ctx, self.tr, L.lib()
-        dev = c.device
-        nl = self.nl
-        vp = R.view_of(self.p)
-        self.dmc = [_new(*[int(v) for v in t.shape], c.dtype, dev, (id(self), "dmc", i)) for i, t in enumerate(self.mc)]
-        self.dp = _new(vp.n, vp.c, vp.h, vp.w, c.dtype, dev, (id(self), "dproto"))
-        vdp = R.view_of(self.dp)
-        vm, vd = [R.view_of(t) for t in self.mc], [R.view_of(t) for t in self.dmc]
-        FP, IA = C.c_void_p * nl, C.c_int * nl
-        coefs, dcoefs = FP(*[v.ptr for v in vm]), FP(*[v.ptr for v in vd])
-        hs, ws = IA(*[v.h for v in vm]), IA(*[v.w for v in vm])
-        lds, ldds = IA(*[v.ld for v in vm]), IA(*[v.ld for v in vd])
-        masks_d, mid_d = tr.masks_d, tr.mid_d
-        if tuple(masks_d.shape) != (batch_size, vp.h, vp.w) or tuple(mid_d.shape) != (batch_size, max_gt):
-            raise L.UpaError(f"mask buffers {tuple(masks_d.shape)} / {tuple(mid_d.shape)} do not match the step: prototypes "
-                             f"{(batch_size, vp.h, vp.w)}, gt rows {(batch_size, max_gt)}")
-        asg = lib.upa_detection_loss_assignment(wsb.data_ptr(), batch_size, n_anchors, max_gt)
-        nws = lib.upa_mask_loss_workspace_bytes(batch_size, n_anchors)
-        mws = tr.pool.get(("mask_loss_ws", batch_size, n_anchors), (nws,), torch.uint8, dev)
-        items4 = tr.pool.get(("loss_items4",), (4,), torch.float32, dev)
-        imgsz_h, imgsz_w = tr._imgsz
-        L.check(lib.upa_mask_loss(vp.ptr, batch_size, vp.h, vp.w, self.nm, vp.ld, C.cast(coefs, C.c_void_p), C.cast(dcoefs, C.c_void_p),
-                                  C.cast(hs, C.c_void_p), C.cast(ws, C.c_void_p), C.cast(lds, C.c_void_p), C.cast(ldds, C.c_void_p), nl,
-                                  asg, 2, tr.gt_d.data_ptr(), tr.ngt_d.data_ptr(), max_gt, mid_d.data_ptr(), masks_d.data_ptr(),
-                                  imgsz_h, imgsz_w, tr.hyp["box"], 1.0, tr.scaler.ptr(), items4.data_ptr() + 4, vdp.ptr, vdp.ld,
-                                  mws.data_ptr(), nws, c.code, _s(dev)), "mask_loss")
-        # (box, seg, cls, dfl), loss.py:541: box and [cls, dfl] of the detection items around the seg item written above
-        L.check(lib.upa_copy_rows(items.data_ptr(), 1, 1, 3, items4.data_ptr(), 4, _s(dev)), "copy_rows")
-        L.check(lib.upa_copy_rows(items.data_ptr() + 4, 1, 2, 3, items4.data_ptr() + 8, 4, _s(dev)), "copy_rows")
-        return items4
-
-    def _level_more_bwd(self, i, dx):
-        c = self.ctx
-        seq, g = self.cv4[i], self.dmc[i]
-        for j in range(len(seq) - 1, 0, -1):
-            vt = R.view_of(seq[j].x)
-            d = _new(vt.n, vt.c, vt.h, vt.w, c.dtype, c.device, (id(self), "d4", i, j))
-            seq[j].backward(g, d, False)
-            g = d
-        seq[0].backward(g, dx, True)
-        if i == 0:
-            self.proto.backward(self.dp, dx, True)
-
-
-class PoseT(DetectT):
-    """Train-mode Pose (head.py:1208-1273 returns the raw maps and the raw keypoint maps) + v8PoseLoss (utils/loss.py:712-870) + its
-    gradient: `DetectT` with, per level, the cv4 chain (Conv 3x3, Conv 3x3, Conv2d 1x1 -> nk) on `PadConvT` - c4 and nk (51 for the
-    17 x 3 skeleton) are no 16-byte multiples, the chain runs at the channel counts rounded up to `Pose.PAD` with zero pad channels.
-    The keypoint terms are upa_kpt_loss on the detection loss's workspace (the per-anchor assignment is read in place); it reads the
-    padded raw map in the trainer's dtype and writes zero pad columns, so every pad gradient of the chain is an exact zero.  Loss
-    items: (box, pose, kobj, cls, dfl)."""
-
-    def __init__(self, ctx, m: H.Pose, name, trainer):
-        super().__init__(ctx, m, name, trainer)
-        self.nkpt, self.ndim = (int(v) for v in m.kpt_shape)
-        self.nk = self.nkpt * self.ndim
-        self.cv4 = [_branch(ctx, seq, f"{name}.cv4.{i}", op=PadConvT, first=dict(pad_cin=False)) for i, seq in enumerate(m.cv4)]
-        self.kp = [None] * m.nl
-        from ...utils.metrics import OKS_SIGMA
-        sig = OKS_SIGMA if tuple(m.kpt_shape) == (17, 3) else [1.0 / self.nkpt] * self.nkpt  # loss.py:720-722
-        self.sigma = (C.c_float * self.nkpt)(*[float(v) for v in sig])
+        self.cv4 = [_branch(ctx, seq, f"{name}.cv4.{i}", op=self.conv_op, first=self.first) for i, seq in enumerate(m.cv4)]
+        self.extra = [None] * m.nl
 
     def convs(self):
         return super().convs() + [cv for seq in self.cv4 for cv in seq]
@@ -288,46 +220,122 @@ class PoseT(DetectT):
         t = x
         for op in self.cv4[i]:
             t = op.forward(t)
-        self.kp[i] = t
+        self.extra[i] = t
+
+    def _level_more_bwd(self, i, dx):
+        _chain_backward(self.ctx, self.cv4[i], self.dextra[i], dx, True, (id(self), "d4", i))
+
+    def _level_tables(self):
+        """Fresh gradient buffers of the cv4 maps and the per-level tables an extra loss takes: (views of the maps, [maps, gradients,
+        hs, ws, lds, ldds] as void pointers)."""
+        c = self.ctx
+        self.dextra = [_new(*[int(v) for v in t.shape], c.dtype, c.device, (id(self), self.grad_key, i)) for i, t in enumerate(self.extra)]
+        vm, vd = [R.view_of(t) for t in self.extra], [R.view_of(t) for t in self.dextra]
+        FP, IA = C.c_void_p * self.nl, C.c_int * self.nl
+        tabs = [FP(*[v.ptr for v in vm]), FP(*[v.ptr for v in vd]), IA(*[v.h for v in vm]), IA(*[v.w for v in vm]),
+                IA(*[v.ld for v in vm]), IA(*[v.ld for v in vd])]
+        return vm, [C.cast(t, C.c_void_p) for t in tabs]  # (a cast keeps its array alive)
+
+    def _loss_workspaces(self, loss: str, wsb, batch_size, n_anchors, max_gt):
+        """(the per-anchor assignment inside the detection loss's workspace `wsb`, the workspace of upa_<loss>, its bytes)."""
+        lib = L.lib()
+        asg = lib.upa_detection_loss_assignment(wsb.data_ptr(), batch_size, n_anchors, max_gt)
+        nws = getattr(lib, f"upa_{loss}_workspace_bytes")(batch_size, n_anchors)
+        return asg, self.tr.pool.get((loss + "_ws", batch_size, n_anchors), (nws,), torch.uint8, self.ctx.device), nws
+
+    def _items_out(self, k: int):
+        """The (3 + k,) buffer of the step's loss items: the extra loss writes its k items at [1, 1 + k)."""
+        return self.tr.pool.get((f"loss_items{3 + k}",), (3 + k,), torch.float32, self.ctx.device)
+
+    def _splice_items(self, items, out):
+        """box and [cls, dfl] of the detection `items` around the extra items of `out`."""
+        lib, st, n = L.lib(), _s(self.ctx.device), int(out.numel())
+        L.check(lib.upa_copy_rows(items.data_ptr(), 1, 1, 3, out.data_ptr(), n, st), "copy_rows")
+        L.check(lib.upa_copy_rows(items.data_ptr() + 4, 1, 2, 3, out.data_ptr() + 4 * (n - 2), n, st), "copy_rows")
+        return out
+
+
+class SegmentT(ExtraDetectT):
+    """Train-mode Segment (head.py:790-837 returns the raw maps, the mask coefficients and the prototypes) + v8SegmentationLoss
+    (utils/loss.py:531-709) + its gradient: the cv4 chains end in nm coefficients and level 0's input also feeds `ProtoT`.  The mask
+    term is upa_mask_loss; Proto backpropagates into level 0's neck gradient.  Loss items: (box, seg, cls, dfl)."""
+
+    grad_key = "dmc"
+
+    def __init__(self, ctx, m: H.Segment, name, trainer):
+        super().__init__(ctx, m, name, trainer)
+        self.nm = m.nm
+        self.proto = ProtoT(ctx, m.proto, name + ".proto")
+        self.p = None
+
+    def convs(self):
+        return super().convs() + self.proto.convs()
+
+    def _level_more(self, i, x):
+        super()._level_more(i, x)
+        if i == 0:
+            self.p = self.proto.forward(x)
 
     def _more_losses(self, items, wsb, batch_size, n_anchors, max_gt):
         c, tr, lib = self.ctx, self.tr, L.lib()
         dev = c.device
-        nl = self.nl
-        self.dkp = [_new(*[int(v) for v in t.shape], c.dtype, dev, (id(self), "dkp", i)) for i, t in enumerate(self.kp)]
-        vk, vd = [R.view_of(t) for t in self.kp], [R.view_of(t) for t in self.dkp]
-        FP, IA = C.c_void_p * nl, C.c_int * nl
-        kpts, dkpts = FP(*[v.ptr for v in vk]), FP(*[v.ptr for v in vd])
-        hs, ws = IA(*[v.h for v in vk]), IA(*[v.w for v in vk])
-        lds, ldds = IA(*[v.ld for v in vk]), IA(*[v.ld for v in vd])
-        strides = (C.c_float * nl)(*[float(s) for s in self.m.stride])
+        vp = R.view_of(self.p)
+        _, (coefs, dcoefs, hs, ws, lds, ldds) = self._level_tables()
+        self.dp = _new(vp.n, vp.c, vp.h, vp.w, c.dtype, dev, (id(self), "dproto"))
+        vdp = R.view_of(self.dp)
+        masks_d, mid_d = tr.masks_d, tr.mid_d
+        if tuple(masks_d.shape) != (batch_size, vp.h, vp.w) or tuple(mid_d.shape) != (batch_size, max_gt):
+            raise L.UpaError(f"mask buffers {tuple(masks_d.shape)} / {tuple(mid_d.shape)} do not match the step: prototypes "
+                             f"{(batch_size, vp.h, vp.w)}, gt rows {(batch_size, max_gt)}")
+        asg, mws, nws = self._loss_workspaces("mask_loss", wsb, batch_size, n_anchors, max_gt)
+        items4 = self._items_out(1)
+        imgsz_h, imgsz_w = tr._imgsz
+        L.check(lib.upa_mask_loss(vp.ptr, batch_size, vp.h, vp.w, self.nm, vp.ld, coefs, dcoefs, hs, ws, lds, ldds, self.nl,
+                                  asg, 2, tr.gt_d.data_ptr(), tr.ngt_d.data_ptr(), max_gt, mid_d.data_ptr(), masks_d.data_ptr(),
+                                  imgsz_h, imgsz_w, tr.hyp["box"], 1.0, tr.scaler.ptr(), items4.data_ptr() + 4, vdp.ptr, vdp.ld,
+                                  mws.data_ptr(), nws, c.code, _s(dev)), "mask_loss")
+        return self._splice_items(items, items4)  # (box, seg, cls, dfl), loss.py:541
+
+    def _level_more_bwd(self, i, dx):
+        super()._level_more_bwd(i, dx)
+        if i == 0:
+            self.proto.backward(self.dp, dx, True)
+
+
+class PoseT(ExtraDetectT):
+    """Train-mode Pose (head.py:1208-1273 returns the raw maps and the raw keypoint maps) + v8PoseLoss (utils/loss.py:712-870) + its
+    gradient: the cv4 chains end in nk keypoint values and run on `PadConvT` - c4 and nk (51 for the 17 x 3 skeleton) are no 16-byte
+    multiples, the chain runs at the channel counts rounded up to `Pose.PAD` with zero pad channels.  The keypoint terms are
+    upa_kpt_loss; it reads the padded raw map in the trainer's dtype and writes zero pad columns, so every pad gradient of the chain is
+    an exact zero.  Loss items: (box, pose, kobj, cls, dfl)."""
+
+    conv_op, first = PadConvT, dict(pad_cin=False)
+    grad_key = "dkp"
+
+    def __init__(self, ctx, m: H.Pose, name, trainer):
+        super().__init__(ctx, m, name, trainer)
+        self.nkpt, self.ndim = (int(v) for v in m.kpt_shape)
+        self.nk = self.nkpt * self.ndim
+        from ...utils.metrics import OKS_SIGMA
+        sig = OKS_SIGMA if tuple(m.kpt_shape) == (17, 3) else [1.0 / self.nkpt] * self.nkpt  # loss.py:720-722
+        self.sigma = (C.c_float * self.nkpt)(*[float(v) for v in sig])
+
+    def _more_losses(self, items, wsb, batch_size, n_anchors, max_gt):
+        c, tr, lib = self.ctx, self.tr, L.lib()
+        dev = c.device
+        vk, (kpts, dkpts, hs, ws, lds, ldds) = self._level_tables()
+        strides = (C.c_float * self.nl)(*[float(s) for s in self.m.stride])
         kpt_d = tr.kpt_d
         if kpt_d is None or tuple(kpt_d.shape) != (batch_size, max_gt, self.nkpt, 3):
             raise L.UpaError(f"keypoint buffer {None if kpt_d is None else tuple(kpt_d.shape)} does not match the step: "
                              f"{(batch_size, max_gt, self.nkpt, 3)}")
-        asg = lib.upa_detection_loss_assignment(wsb.data_ptr(), batch_size, n_anchors, max_gt)
-        nws = lib.upa_kpt_loss_workspace_bytes(batch_size, n_anchors)
-        kws = tr.pool.get(("kpt_loss_ws", batch_size, n_anchors), (nws,), torch.uint8, dev)
-        items5 = tr.pool.get(("loss_items5",), (5,), torch.float32, dev)
-        L.check(lib.upa_kpt_loss(C.cast(kpts, C.c_void_p), C.cast(dkpts, C.c_void_p), C.cast(hs, C.c_void_p), C.cast(ws, C.c_void_p),
-                                 C.cast(lds, C.c_void_p), C.cast(ldds, C.c_void_p), nl, batch_size, vk[0].c, self.nkpt, self.ndim, asg, 2,
+        asg, kws, nws = self._loss_workspaces("kpt_loss", wsb, batch_size, n_anchors, max_gt)
+        items5 = self._items_out(2)
+        L.check(lib.upa_kpt_loss(kpts, dkpts, hs, ws, lds, ldds, self.nl, batch_size, vk[0].c, self.nkpt, self.ndim, asg, 2,
                                  tr.gt_d.data_ptr(), tr.ngt_d.data_ptr(), max_gt, kpt_d.data_ptr(), C.cast(strides, C.c_void_p),
                                  C.cast(self.sigma, C.c_void_p), tr.hyp["pose"], tr.hyp["kobj"], 1.0, tr.scaler.ptr(),
                                  items5.data_ptr() + 4, kws.data_ptr(), nws, c.code, _s(dev)), "kpt_loss")
-        # (box, pose, kobj, cls, dfl), loss.py:727: box and [cls, dfl] of the detection items around the two items written above
-        L.check(lib.upa_copy_rows(items.data_ptr(), 1, 1, 3, items5.data_ptr(), 5, _s(dev)), "copy_rows")
-        L.check(lib.upa_copy_rows(items.data_ptr() + 4, 1, 2, 3, items5.data_ptr() + 12, 5, _s(dev)), "copy_rows")
-        return items5
-
-    def _level_more_bwd(self, i, dx):
-        c = self.ctx
-        seq, g = self.cv4[i], self.dkp[i]
-        for j in range(len(seq) - 1, 0, -1):
-            vt = R.view_of(seq[j].x)
-            d = _new(vt.n, vt.c, vt.h, vt.w, c.dtype, c.device, (id(self), "d4", i, j))
-            seq[j].backward(g, d, False)
-            g = d
-        seq[0].backward(g, dx, True)
+        return self._splice_items(items, items5)  # (box, pose, kobj, cls, dfl), loss.py:727
 
 
 class ClassifyT:

@@ -33,20 +33,20 @@ class DetectionTrainer:
     `optimizer`: "SGD" (default: SGD-Nesterov), "Adam", "AdamW" (lr and beta1 = `momentum` from `hyp`, plus `beta2`, `adam_eps`) or
     "auto" with `iterations` (`resolve_optimizer`); `optimizer_name` is the resolved one."""
 
-    _segment_ok = False  # (SegmentationTrainer: True)
-    _pose_ok = False     # (PoseTrainer: True)
+    tail_type, tail_op = H.Detect, DetectT  # the head that ends the model and its op: H.Detect itself here, a trainer of another task names its own
+    _OTHER_TAILS = ((H.Segment, "segmentation models (Segment head) have no training path on HIP in DetectionTrainer (v8DetectionLoss only): "
+                                "train them with SegmentationTrainer"),
+                    (H.Pose, "pose models (Pose head) have no training path on HIP in DetectionTrainer (v8DetectionLoss only): pose "
+                             "training (v8PoseLoss) is PoseTrainer's"))
 
     def __init__(self, model, dtype=torch.bfloat16, hyp=None, device=None, world_size=1, ema=True, wgrad_streams: int = 1,
                  amp_scaler: bool = False, optimizer: str = "SGD", iterations=None, yolo11: bool = False):
         self.optimizer_name, opt_hyp, self._auto_optimizer = resolve_optimizer(
             optimizer, iterations, _head_nc(model) if str(optimizer).lower() == "auto" and iterations is not None else 0)
+        for head, refusal in self._OTHER_TAILS:  # a head with an extra branch trains under the trainer that names it
+            if not issubclass(self.tail_type, head) and any(isinstance(m, head) for m in model.modules()):
+                raise L.UpaError(refusal)
         # the non-legacy Detect head (YOLO11: depthwise class branch, `DWConvT`) trains on request only: `yolo11=True`
-        if not self._segment_ok and any(isinstance(m, H.Segment) for m in model.modules()):
-            raise L.UpaError("segmentation models (Segment head) have no training path on HIP in DetectionTrainer (v8DetectionLoss only): "
-                             "train them with SegmentationTrainer")
-        if not self._pose_ok and any(isinstance(m, H.Pose) for m in model.modules()):
-            raise L.UpaError("pose models (Pose head) have no training path on HIP in DetectionTrainer (v8DetectionLoss only): pose "
-                             "training (v8PoseLoss) is PoseTrainer's")
         for m in model.modules():
             if isinstance(m, H.Detect) and not m.legacy_cls:
                 if not yolo11:
@@ -200,9 +200,9 @@ class DetectionTrainer:
 
     def _tail_op(self, m, name):
         """The op of the module that ends the graph and owns the loss (`forward(x)`, `loss_backward(labels, batch_size)`), None for
-        every other module.  The hook a trainer of another task overrides (`ClassificationTrainer`)."""
-        if isinstance(m, H.Detect):
-            return DetectT(self.ctx, m, name, self)
+        every other module: `tail_op` for a `tail_type`.  (`ClassificationTrainer` overrides the hook.)"""
+        if isinstance(m, self.tail_type):
+            return self.tail_op(self.ctx, m, name, self)
         return None
 
     # ---- one step -----------------------------------------------------------------------------------------------------
@@ -727,39 +727,89 @@ class ClassificationTrainer(DetectionTrainer):
         self._label_ring.commit(torch.cuda.current_stream(self.device))
 
 
-class PoseTrainer(DetectionTrainer):
+class ExtraLabelsTrainer(DetectionTrainer):
+    """DetectionTrainer for a model whose head (`tail_type`) has an extra branch with a loss term of its own (`tail_op`) that reads more
+    labels than the gt rows.  Everything but the tail and the labels is DetectionTrainer's: the graph walk, `step`, `compile` / replay,
+    `set_schedule`, every optimizer, GradScaler, EMA and the multi-rank path.  The extra labels go up with the gt rows, through a pinned
+    ring of their own, into the device buffers the tail op reads as attributes of the trainer.  Every refusal - the constructor's (a
+    model that does not end in `tail_type`; a YOLO11 head, depthwise class branch, with or without yolo11=True: no golden pins it) and
+    the label upload's (`_check_extra`, `_pack_extra`) - comes before any launch or upload.
+
+    A subclass names `tail_type`, `tail_op` and `_yolo11_refusals` and states `_check_extra` and `_pack_extra`."""
+
+    _yolo11_refusals = None  # (without yolo11=True, with it)
+
+    def __init__(self, model, **kw):
+        self._extra_ring = PinnedRing()  # the extra labels' staging, beside the gt rows' `_label_ring`
+        super().__init__(model, **kw)
+
+    def _checked_tail(self, model, yolo11: bool):
+        """The model's tail, refused unless it is a yolov8 (legacy class branch) head of `tail_type`."""
+        tail = model.model[-1] if hasattr(model, "model") and len(model.model) else None
+        if not isinstance(tail, self.tail_type):
+            raise L.UpaError(f"{type(self).__name__} needs a model that ends in a {self.tail_type.__name__} head, got {type(tail).__name__}")
+        if not tail.legacy_cls:
+            raise L.UpaError(self._yolo11_refusals[bool(yolo11)])
+        return tail
+
+    def _check_extra(self, labels, batch_size):
+        """The host-side refusals of the extra labels; what it returns is handed to `_pack_extra`."""
+        raise NotImplementedError
+
+    def _pack_extra(self, labels, batch_size, most, checked):
+        """[(name of the trainer's device buffer, host tensor, per_label)]: a per_label tensor is (B, most, ...), one row per label of
+        the image with the most labels, and is laid out in the gt buffer's row count."""
+        raise NotImplementedError
+
+    def _upload_labels(self, labels, batch_size):
+        # every refusal comes before anything is uploaded: the extra labels are checked and packed (into as many rows as the image with
+        # the most labels has) first, then the gt rows go up, then the per-label tensors are laid out in the gt buffer's row count
+        checked = self._check_extra(labels, batch_size)
+        bi = labels["batch_idx"].view(-1).cpu().long()
+        most = max([int((bi == j).sum()) for j in range(batch_size)] + [1])
+        packed = self._pack_extra(labels, batch_size, most, checked)
+        super()._upload_labels(labels, batch_size)
+        rows = int(self.gt_d.shape[1])
+        shapes = [(batch_size, rows) + tuple(t.shape[2:]) if per_label else tuple(t.shape) for _, t, per_label in packed]
+        held = [getattr(self, name) for name, _, _ in packed]
+        if any(d is None or tuple(d.shape) != s for d, s in zip(held, shapes)):
+            if self._graphs is not None or self._capturing:
+                raise L.UpaError(f"{' / '.join(name for name, _, _ in packed)} of shapes {shapes} ({rows} gt rows, {batch_size} images) do "
+                                 f"not match the compiled step's buffers {[None if d is None else tuple(d.shape) for d in held]}")
+            for (name, t, _), s in zip(packed, shapes):
+                setattr(self, name, torch.zeros(s, dtype=t.dtype, device=self.device))
+        hosts = self._extra_ring.stage([(s, t.dtype) for (_, t, _), s in zip(packed, shapes)])
+        for h, (name, t, per_label) in zip(hosts, packed):
+            if per_label:
+                h[:, :min(rows, most)].copy_(t[:, :rows])
+                h[:, min(rows, most):].zero_()  # (never read - n_gt bounds the rows - but a reused slot must not carry an earlier batch)
+            else:
+                h.copy_(t)
+            getattr(self, name).copy_(h, non_blocking=True)
+        self._extra_ring.commit(torch.cuda.current_stream(self.device))
+
+
+class PoseTrainer(ExtraLabelsTrainer):
     """One-process-per-GPU trainer for a PoseModel (reference: models/yolo/pose/train.py on engine/trainer.py's loop; the loss is
-    v8PoseLoss, utils/loss.py:712-870).  Everything but the tail and the labels is DetectionTrainer's: the graph walk, `step`,
-    `compile` / replay, `set_schedule`, every optimizer, GradScaler, EMA and the multi-rank path.  The tail is `PoseT`; the labels
-    additionally carry `"keypoints"`, (n_labels, nkpt, ndim) normalised [x, y(, visibility)] in the rows of `"bboxes"`.  The gains
-    `pose` (12.0) and `kobj` (1.0) join the hyper-parameters here.  `step()` returns the (5,) loss items (box, pose, kobj, cls, dfl).
+    v8PoseLoss, utils/loss.py:712-870).  The tail is `PoseT`; the labels additionally carry `"keypoints"`, (n_labels, nkpt, ndim)
+    normalised [x, y(, visibility)] in the rows of `"bboxes"` (device buffer `kpt_d`).  The gains `pose` (12.0) and `kobj` (1.0) join the
+    hyper-parameters here.  `step()` returns the (5,) loss items (box, pose, kobj, cls, dfl).
     The cv4 chains' 51 channels train on `PadConvT`'s zero-padded staging: one gather launch in front of the weight repack and one
     scatter launch behind the head's backward, both inside the captured step.
-    Refused, by the constructor or the label upload, before any launch: a model that does not end in Pose; a YOLO11 Pose head
-    (depthwise class branch), with or without yolo11=True - no golden pins it; labels without "keypoints"; a keypoint tensor that is
-    not (n_labels, *kpt_shape); non-finite keypoints."""
+    Refused by the label upload: labels without "keypoints"; a keypoint tensor that is not (n_labels, *kpt_shape); non-finite
+    keypoints."""
 
-    _pose_ok = True
+    tail_type, tail_op = H.Pose, PoseT
+    _yolo11_refusals = ("Pose (YOLO11, non-legacy head with a depthwise class branch): PoseTrainer builds the yolov8 Pose head only, "
+                        "with or without yolo11=True - no golden record pins a YOLO11 pose step",) * 2
     POSE_HYP = dict(pose=12.0, kobj=1.0)  # cfg/default.yaml of the reference
 
     def __init__(self, model, dtype=torch.bfloat16, hyp=None, device=None, world_size=1, ema=True, wgrad_streams: int = 1,
                  amp_scaler: bool = False, optimizer: str = "SGD", iterations=None, yolo11: bool = False):
-        tail = model.model[-1] if hasattr(model, "model") and len(model.model) else None
-        if not isinstance(tail, H.Pose):
-            raise L.UpaError(f"PoseTrainer needs a model that ends in a Pose head, got {type(tail).__name__}")
-        if not tail.legacy_cls:
-            raise L.UpaError("Pose (YOLO11, non-legacy head with a depthwise class branch): PoseTrainer builds the yolov8 Pose head only, "
-                             "with or without yolo11=True - no golden record pins a YOLO11 pose step")
-        self.kpt_shape = tuple(int(v) for v in tail.kpt_shape)
+        self.kpt_shape = tuple(int(v) for v in self._checked_tail(model, yolo11).kpt_shape)
         self.kpt_d = None
-        self._kpt_ring = PinnedRing()
         super().__init__(model, dtype=dtype, hyp=dict(self.POSE_HYP, **(hyp or {})), device=device, world_size=world_size, ema=ema,
                          wgrad_streams=wgrad_streams, amp_scaler=amp_scaler, optimizer=optimizer, iterations=iterations, yolo11=yolo11)
-
-    def _tail_op(self, m, name):
-        if isinstance(m, H.Pose):
-            return PoseT(self.ctx, m, name, self)
-        return None
 
     @staticmethod
     def check_keypoints(labels, kpt_shape):
@@ -775,66 +825,38 @@ class PoseTrainer(DetectionTrainer):
             raise L.UpaError("keypoints hold non-finite values")
         return kp
 
-    def _upload_labels(self, labels, batch_size):
-        imgsz_h, imgsz_w = self._imgsz
-        # every refusal comes before anything is uploaded: the keypoints are checked and packed (into as many rows as the image with
-        # the most labels has) first, then the gt rows go up, then the keypoints are laid out in the gt buffer's row count
-        self.check_keypoints(labels, self.kpt_shape)
-        bi = labels["batch_idx"].view(-1).cpu().long()
-        most = max([int((bi == j).sum()) for j in range(batch_size)] + [1])
-        kp0 = pack_keypoints(labels, batch_size, imgsz_h, imgsz_w, most, self.kpt_shape)
-        super()._upload_labels(labels, batch_size)
-        rows = int(self.gt_d.shape[1])
-        shape = (batch_size, rows, self.kpt_shape[0], 3)
-        if self.kpt_d is None or tuple(self.kpt_d.shape) != shape:
-            if self._graphs is not None or self._capturing:
-                raise L.UpaError(f"keypoints of {rows} gt rows for {batch_size} images do not match the compiled step's buffer "
-                                 f"{None if self.kpt_d is None else tuple(self.kpt_d.shape)}")
-            self.kpt_d = torch.zeros(shape, dtype=torch.float32, device=self.device)
-        (h_kp,) = self._kpt_ring.stage([(shape, torch.float32)])
-        h_kp[:, :min(rows, most)].copy_(kp0[:, :rows])
-        h_kp[:, min(rows, most):].zero_()  # (never read - n_gt bounds the rows - but a reused slot must not carry an earlier batch)
-        self.kpt_d.copy_(h_kp, non_blocking=True)
-        self._kpt_ring.commit(torch.cuda.current_stream(self.device))
+    def _check_extra(self, labels, batch_size):
+        return self.check_keypoints(labels, self.kpt_shape)
+
+    def _pack_extra(self, labels, batch_size, most, checked):
+        return [("kpt_d", pack_keypoints(labels, batch_size, *self._imgsz, most, self.kpt_shape), True)]
 
 
-class SegmentationTrainer(DetectionTrainer):
+class SegmentationTrainer(ExtraLabelsTrainer):
     """One-process-per-GPU trainer for a SegmentationModel (reference: models/yolo/segment/train.py on engine/trainer.py's loop; the loss
-    is v8SegmentationLoss, utils/loss.py:531-709).  Everything but the tail and the labels is DetectionTrainer's: the graph walk, `step`,
-    `compile` / replay, `set_schedule`, every optimizer, GradScaler, EMA and the multi-rank path.  The tail is `SegmentT`; the labels
-    additionally carry `"masks"`, the (B, mh, mw) overlap mask at prototype resolution (instance p of an image painted as p + 1, later
-    instances over earlier ones - what the reference's dataset delivers with overlap_mask=True, mask_ratio=4).  `step()` returns the
-    (4,) loss items (box, seg, cls, dfl).
-    Refused, by the constructor or the label upload, before any launch: overlap_mask=False (per-instance mask stacks); masks that are not
-    at prototype resolution (the reference's F.interpolate fallback, loss.py:604-605, is not built); instance ids above 255 (the mask is
-    read as uint8); a YOLO11 Segment head (depthwise class branch), with or without yolo11=True."""
+    is v8SegmentationLoss, utils/loss.py:531-709).  The tail is `SegmentT`; the labels additionally carry `"masks"`, the (B, mh, mw)
+    overlap mask at prototype resolution (instance p of an image painted as p + 1, later instances over earlier ones - what the
+    reference's dataset delivers with overlap_mask=True, mask_ratio=4): device buffers `masks_d` and, per gt row, the instance id
+    `mid_d`.  `step()` returns the (4,) loss items (box, seg, cls, dfl).
+    Refused as well: overlap_mask=False (per-instance mask stacks); masks that are not at prototype resolution (the reference's
+    F.interpolate fallback, loss.py:604-605, is not built); instance ids above 255 (the mask is read as uint8)."""
 
-    _segment_ok = True
+    tail_type, tail_op = H.Segment, SegmentT
+    _yolo11_refusals = ("Segment (YOLO11, non-legacy head with a depthwise class branch) has no training path on HIP unless it is "
+                        "asked for with yolo11=True - and SegmentationTrainer does not build it yet",
+                        "Segment (YOLO11, non-legacy head with a depthwise class branch): SegmentationTrainer builds the yolov8 "
+                        "Segment head only")
 
     def __init__(self, model, dtype=torch.bfloat16, hyp=None, device=None, world_size=1, ema=True, wgrad_streams: int = 1,
                  amp_scaler: bool = False, optimizer: str = "SGD", iterations=None, yolo11: bool = False, overlap_mask: bool = True):
-        tail = model.model[-1] if hasattr(model, "model") and len(model.model) else None
-        if not isinstance(tail, H.Segment):
-            raise L.UpaError(f"SegmentationTrainer needs a model that ends in a Segment head, got {type(tail).__name__}")
+        tail = self._checked_tail(model, yolo11)
         if not overlap_mask:
             raise L.UpaError("overlap_mask=False (one mask plane per instance) has no training path on HIP: the mask loss reads the "
                              "overlap mask (overlap_mask=True, the reference's default)")
-        if not tail.legacy_cls:
-            if not yolo11:
-                raise L.UpaError("Segment (YOLO11, non-legacy head with a depthwise class branch) has no training path on HIP unless it is "
-                                 "asked for with yolo11=True - and SegmentationTrainer does not build it yet")
-            raise L.UpaError("Segment (YOLO11, non-legacy head with a depthwise class branch): SegmentationTrainer builds the yolov8 "
-                             "Segment head only")
         ConvTransposeT.check(tail.proto.upsample, f"model.{getattr(tail, 'i', '?')}.proto.upsample")
         self.masks_d = self.mid_d = None
-        self._mask_ring = PinnedRing()
         super().__init__(model, dtype=dtype, hyp=hyp, device=device, world_size=world_size, ema=ema, wgrad_streams=wgrad_streams,
                          amp_scaler=amp_scaler, optimizer=optimizer, iterations=iterations, yolo11=yolo11)
-
-    def _tail_op(self, m, name):
-        if isinstance(m, H.Segment):
-            return SegmentT(self.ctx, m, name, self)
-        return None
 
     @staticmethod
     def check_masks(labels, batch_size, mh, mw):
@@ -855,31 +877,14 @@ class SegmentationTrainer(DetectionTrainer):
                                  "reads the overlap mask as uint8)")
         return masks.to(torch.uint8).contiguous()
 
-    def _upload_labels(self, labels, batch_size):
+    def _check_extra(self, labels, batch_size):
         imgsz_h, imgsz_w = self._imgsz
         s0 = float(self.detect.m.stride[0])
-        mh, mw = int(imgsz_h / s0) * 2, int(imgsz_w / s0) * 2  # Proto doubles level 0's map
-        masks = self.check_masks(labels, batch_size, mh, mw)
-        # every refusal comes before anything is uploaded: the ids are packed (into as many rows as the image with the most labels has)
-        # and checked first, then the gt rows go up, then the ids are laid out in the gt buffer's row count
-        bi = labels["batch_idx"].view(-1).cpu().long()
-        most = max([int((bi == j).sum()) for j in range(batch_size)] + [1])
-        mid0 = pack_mask_ids(labels, batch_size, imgsz_h, imgsz_w, most)
-        if int(mid0.max()) > MASK_ID_MAX:
-            raise L.UpaError(f"an image has a label at position {int(mid0.max())}: instance ids above {MASK_ID_MAX} do not fit the uint8 "
+        return self.check_masks(labels, batch_size, int(imgsz_h / s0) * 2, int(imgsz_w / s0) * 2)  # Proto doubles level 0's map
+
+    def _pack_extra(self, labels, batch_size, most, masks):
+        mid = pack_mask_ids(labels, batch_size, *self._imgsz, most)
+        if int(mid.max()) > MASK_ID_MAX:
+            raise L.UpaError(f"an image has a label at position {int(mid.max())}: instance ids above {MASK_ID_MAX} do not fit the uint8 "
                              "overlap mask")
-        super()._upload_labels(labels, batch_size)
-        rows = int(self.gt_d.shape[1])
-        mid = torch.zeros(batch_size, rows, dtype=torch.int32)
-        mid[:, :min(rows, most)] = mid0[:, :rows]
-        if self.masks_d is None or tuple(self.masks_d.shape) != tuple(masks.shape) or tuple(self.mid_d.shape) != tuple(mid.shape):
-            if self._graphs is not None or self._capturing:
-                raise L.UpaError(f"masks {tuple(masks.shape)} / {rows} gt rows do not match the compiled step's buffers")
-            self.masks_d = torch.zeros(tuple(masks.shape), dtype=torch.uint8, device=self.device)
-            self.mid_d = torch.zeros(tuple(mid.shape), dtype=torch.int32, device=self.device)
-        h_masks, h_mid = self._mask_ring.stage([(masks.shape, torch.uint8), (mid.shape, torch.int32)])
-        h_masks.copy_(masks)
-        h_mid.copy_(mid)
-        self.masks_d.copy_(h_masks, non_blocking=True)
-        self.mid_d.copy_(h_mid, non_blocking=True)
-        self._mask_ring.commit(torch.cuda.current_stream(self.device))
+        return [("masks_d", masks, False), ("mid_d", mid, True)]

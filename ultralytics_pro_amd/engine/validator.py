@@ -20,14 +20,15 @@ from ..utils.nms import nms_raw
 
 
 class DetectionValidator:
-    accepts_segment = False  # a Segment head needs mask statistics next to the box ones: SegmentationValidator below
-    accepts_pose = False  # a Pose head needs keypoint (OKS) statistics next to the box ones: PoseValidator below
+    head = "Detect"  # the head type this validator takes: a head with an extra branch needs that branch's statistics next to the box ones
+    _OTHER_HEADS = {"Segment": "segmentation models (Segment head) cannot be validated by {}: use SegmentationValidator (box and mask mAP)",
+                    "Pose": "pose models (Pose head) cannot be validated by {}: use PoseValidator (box and pose mAP)"}
 
     def __init__(self, model=None, conf: float = 0.001, iou: float = 0.7, max_det: int = 300, max_gt: int = 64):
-        if model is not None and not self.accepts_segment and any(type(m).__name__ == "Segment" for m in model.modules()):
-            raise L.UpaError("segmentation models (Segment head) cannot be validated here: mask mAP is out of scope")
-        if model is not None and not self.accepts_pose and any(type(m).__name__ == "Pose" for m in model.modules()):
-            raise L.UpaError(f"pose models (Pose head) cannot be validated by {type(self).__name__}: use PoseValidator (box and pose mAP)")
+        for m in (model.modules() if model is not None else ()):
+            name = type(m).__name__
+            if name in self._OTHER_HEADS and name != self.head:
+                raise L.UpaError(self._OTHER_HEADS[name].format(type(self).__name__))
         self.model, self.conf, self.iou, self.max_det, self.max_gt = model, conf, iou, max_det, max_gt
         self.reset()
 
@@ -149,26 +150,54 @@ class DetectionValidator:
         return stats
 
 
-class SegmentationValidator(DetectionValidator):
+class ExtraValidator(DetectionValidator):
+    """Validation of a model whose head has an extra per-anchor branch (`head`): box statistics AND a second true-positive matrix of
+    what that branch predicts, under `tp_key` in the statistics and with its class metrics under `metrics_key`.  Per batch, all on the
+    device with fixed shapes and no host sync: val-mode NMS -> the kept anchors' extra columns (`upa_nms_gather_extra`) -> box true
+    positives (`upa_match_predictions`) -> the subclass's matching kernel.  The statistics rows are 22 wide: conf | cls | tp | tp_key."""
+
+    stat_cols = 22
+    tp_key = metrics_key = None
+
+    def reset(self):
+        super().reset()
+        self._tp2 = []
+
+    def add_batch_stats(self, out: torch.Tensor, counts: torch.Tensor, tp: torch.Tensor, gt: torch.Tensor, ngt: torch.Tensor,
+                        tp2: torch.Tensor):
+        """Statistics of a batch whose matching already ran (e.g. inside a captured step); `out`: (B, max_det, >= 6) rows."""
+        super().add_batch_stats(out[:, :, :6], counts, tp, gt, ngt)
+        self._tp2.append(tp2.clone())
+
+    def local_stats(self):
+        """As DetectionValidator.local_stats with (I, max_det, 22) rows: conf | cls | tp | tp_key."""
+        rows, cnt, gcls, ngt = super().local_stats()
+        return torch.cat([rows, torch.cat(self._tp2, 0).float()], 2).contiguous(), cnt, gcls, ngt
+
+    def get_stats(self):
+        """What DetectionValidator.get_stats returns for the boxes, plus `tp_key` and `metrics_key` = {p, r, f1, ap, classes, mean} of
+        the second matrix: the same `ap_per_class` on its true positives, as SegmentMetrics / PoseMetrics.process do (utils/metrics.py)."""
+        allr, tcls = self._gathered()
+        stats = dict(tp=allr[:, 2:12].astype(bool), conf=allr[:, 0], pred_cls=allr[:, 1], target_cls=tcls)
+        stats[self.tp_key] = allr[:, 12:22].astype(bool)
+        stats.update(self._class_metrics(stats["tp"], stats["conf"], stats["pred_cls"], tcls))
+        stats[self.metrics_key] = self._class_metrics(stats[self.tp_key], stats["conf"], stats["pred_cls"], tcls)
+        return stats
+
+
+class SegmentationValidator(ExtraValidator):
     """Validation of a Segment model: box AND mask P / R / mAP50 / mAP50-95 (models/yolo/segment/val.py:94-172, utils/metrics.py
-    SegmentMetrics.process).  Per batch, all on the device with fixed shapes and no host sync: val-mode NMS -> the kept anchors' mask
-    coefficients (`upa_nms_gather_extra`) -> box true positives (`upa_match_predictions`) -> mask true positives
-    (`upa_segment_match`: the predicted masks are assembled, ANDed and popcounted against the packed label masks on the chip; no
-    mask buffer exists).  The statistics rows are 22 wide: conf | cls | tp | tp_m.
+    SegmentMetrics.process).  The mask true positives are `upa_segment_match`'s: the predicted masks are assembled, ANDed and popcounted
+    against the packed label masks on the chip; no mask buffer exists.
 
     Scope: the validator's default mask path, `process_mask` at proto resolution.  `save_json` / `save_txt` (which switch the
     reference to `process_mask_native`), RLE export and plots are not provided."""
 
-    accepts_segment = True
-    stat_cols = 22
+    head, tp_key, metrics_key = "Segment", "tp_m", "seg"
 
     def __init__(self, model=None, conf: float = 0.001, iou: float = 0.7, max_det: int = 300, max_gt: int = 64, overlap_mask: bool = True):
         self.overlap_mask = overlap_mask
         super().__init__(model, conf, iou, max_det, max_gt)
-
-    def reset(self):
-        super().reset()
-        self._tpm = []
 
     # ---- per batch ------------------------------------------------------------------------------------------------------
     def pack_masks(self, labels: dict, batch_size: int, proto_hw, device):
@@ -209,14 +238,10 @@ class SegmentationValidator(DetectionValidator):
         """preds: the Segment model's eval output (y, (raw, mc, protos)); gt / ngt from `pack_labels`, gt_bits / gt_area from
         `pack_masks` of the same images.  `key` names the step's static buffers and `record = False` leaves the statistics to a later
         `add_batch_stats` when the call is captured into a graph.  Returns the step's device tensors (out, counts, tp, tp_m)."""
-        from ..engine import runtime as R
         from ..utils import ops
         y, mc, p = ops._seg_parts(preds, 0)
-        b, nm, a = mc.shape
-        out, counts, keep = nms_raw(y, self.conf, self.iou, multi_label=True, max_det=self.max_det, key=key)
-        rows = R.alloc_plain((b, self.max_det, 6 + nm), torch.float32, y.device, key=(key, "segval_rows") if key is not None else None)
-        L.check(L.lib().upa_nms_gather_extra(mc.data_ptr(), b, nm, a, keep.data_ptr(), counts.data_ptr(), int(self.max_det), out.data_ptr(),
-                                             rows.data_ptr(), 6 + nm, L.current_stream(y.device)), "nms_gather_extra")
+        out, rows, counts, _ = ops.nms_gather_extra(y, mc, (key, "segval_rows") if key is not None else None, self.conf, self.iou,
+                                                    multi_label=True, max_det=self.max_det, key=key)
         return self.update_detections(out, counts, gt, ngt, rows, ops._protos_nhwc(p), gt_bits, gt_area, key=key, record=record)
 
     def update_detections(self, out: torch.Tensor, counts: torch.Tensor, gt: torch.Tensor, ngt: torch.Tensor, rows: torch.Tensor,
@@ -233,38 +258,15 @@ class SegmentationValidator(DetectionValidator):
             self.add_batch_stats(out, counts, tp, gt, ngt, tp_m)
         return out, counts, tp, tp_m
 
-    def add_batch_stats(self, out: torch.Tensor, counts: torch.Tensor, tp: torch.Tensor, gt: torch.Tensor, ngt: torch.Tensor,
-                        tp_m: torch.Tensor):
-        """Statistics of a batch whose matching already ran (e.g. inside a captured step)."""
-        super().add_batch_stats(out[:, :, :6], counts, tp, gt, ngt)
-        self._tpm.append(tp_m.clone())
 
-    # ---- end of run -----------------------------------------------------------------------------------------------------
-    def local_stats(self):
-        """As DetectionValidator.local_stats with (I, max_det, 22) rows: conf | cls | tp | tp_m."""
-        rows, cnt, gcls, ngt = super().local_stats()
-        return torch.cat([rows, torch.cat(self._tpm, 0).float()], 2).contiguous(), cnt, gcls, ngt
-
-    def get_stats(self):
-        """What DetectionValidator.get_stats returns for the boxes, plus "tp_m" and "seg" = {p, r, f1, ap, classes, mean} of the
-        masks: the same `ap_per_class` on the mask true positives, as SegmentMetrics.process does (utils/metrics.py)."""
-        allr, tcls = self._gathered()
-        stats = dict(tp=allr[:, 2:12].astype(bool), tp_m=allr[:, 12:22].astype(bool), conf=allr[:, 0], pred_cls=allr[:, 1], target_cls=tcls)
-        stats.update(self._class_metrics(stats["tp"], stats["conf"], stats["pred_cls"], tcls))
-        stats["seg"] = self._class_metrics(stats["tp_m"], stats["conf"], stats["pred_cls"], tcls)
-        return stats
-
-
-class PoseValidator(DetectionValidator):
+class PoseValidator(ExtraValidator):
     """Validation of a Pose model: box AND pose P / R / mAP50 / mAP50-95 (models/yolo/pose/val.py:106-197, utils/metrics.py
-    PoseMetrics).  Per batch, all on the device with fixed shapes and no host sync: val-mode NMS -> the kept anchors' keypoints
-    (`upa_nms_gather_extra`) -> box true positives (`upa_match_predictions`) -> pose true positives (`upa_pose_match`: OKS of every
-    detection against the labels of its class and the claim step, one launch).  The statistics rows are 22 wide: conf | cls | tp | tp_p.
+    PoseMetrics).  The pose true positives are `upa_pose_match`'s: OKS of every detection against the labels of its class and the
+    claim step, one launch.
 
     Scope: `save_json` / `save_txt`, flip-index TTA and plots are not provided."""
 
-    accepts_pose = True
-    stat_cols = 22
+    head, tp_key, metrics_key = "Pose", "tp_p", "pose"
 
     def __init__(self, model=None, conf: float = 0.001, iou: float = 0.7, max_det: int = 300, max_gt: int = 64, kpt_shape=None):
         if kpt_shape is None:
@@ -273,10 +275,6 @@ class PoseValidator(DetectionValidator):
         nkpt = self.kpt_shape[0]
         self.sigma = M.OKS_SIGMA if self.kpt_shape == (17, 3) else np.ones(nkpt) / nkpt  # pose/val.py:114-116
         super().__init__(model, conf, iou, max_det, max_gt)
-
-    def reset(self):
-        super().reset()
-        self._tpp = []
 
     # ---- per batch ------------------------------------------------------------------------------------------------------
     def pack_keypoints(self, labels: dict, batch_size: int, device, imgsz_hw=None):
@@ -320,27 +318,6 @@ class PoseValidator(DetectionValidator):
         if record:
             self.add_batch_stats(out, counts, tp, gt, ngt, tp_p)
         return rows, counts, tp, tp_p
-
-    def add_batch_stats(self, out: torch.Tensor, counts: torch.Tensor, tp: torch.Tensor, gt: torch.Tensor, ngt: torch.Tensor,
-                        tp_p: torch.Tensor):
-        """Statistics of a batch whose matching already ran (e.g. inside a captured step); `out`: (B, max_det, >= 6) rows."""
-        super().add_batch_stats(out[:, :, :6], counts, tp, gt, ngt)
-        self._tpp.append(tp_p.clone())
-
-    # ---- end of run -----------------------------------------------------------------------------------------------------
-    def local_stats(self):
-        """As DetectionValidator.local_stats with (I, max_det, 22) rows: conf | cls | tp | tp_p."""
-        rows, cnt, gcls, ngt = super().local_stats()
-        return torch.cat([rows, torch.cat(self._tpp, 0).float()], 2).contiguous(), cnt, gcls, ngt
-
-    def get_stats(self):
-        """What DetectionValidator.get_stats returns for the boxes, plus "tp_p" and "pose" = {p, r, f1, ap, classes, mean} of the
-        keypoints: the same `ap_per_class` on the pose true positives, as PoseMetrics.process does (utils/metrics.py)."""
-        allr, tcls = self._gathered()
-        stats = dict(tp=allr[:, 2:12].astype(bool), tp_p=allr[:, 12:22].astype(bool), conf=allr[:, 0], pred_cls=allr[:, 1], target_cls=tcls)
-        stats.update(self._class_metrics(stats["tp"], stats["conf"], stats["pred_cls"], tcls))
-        stats["pose"] = self._class_metrics(stats["tp_p"], stats["conf"], stats["pred_cls"], tcls)
-        return stats
 
 
 class ClassificationValidator:

@@ -2,6 +2,7 @@
 
 from __future__ import annotations
 
+import itertools
 import math
 
 import torch
@@ -510,20 +511,106 @@ class Detect(nn.Module, _HipConvMixin):
         return super().train(mode)
 
 
-class Segment(Detect):
+class ExtraDetect(Detect):
+    """Detect plus one more per-level branch `cv4[l]` whose per-anchor output is laid into an `extra` (B, ne, A) f32 tensor: the
+    shared part of `Segment` (mask coefficients) and `Pose` (keypoints).
+
+    Eval forward returns the reference's `(cat([y, extra], 1), rest)`: y = Detect's (B, 4+nc, A) output, untouched (every fused Detect
+    form and NMS kernel keeps its image stride), each level's cv4 output written into its anchor range of `extra`.  With
+    `cat_out = False` the concatenated copy is not made and the first element is y itself.  Either way the first element carries
+    `_upa_parts = (y, extra)`: `utils.nms` runs on y and gathers the extra columns of the kept rows, and the postprocess of
+    `utils.ops` reads the parts.
+
+    Scheduling: a level's cv4 branch runs when `start_level` is called for it (the moment its feature map exists); levels the executor
+    did not start (a direct call, or the levels `Detect.forward` groups) run in `forward`.  Inference only: a train-mode forward raises
+    (`_train_refusal`), the train-mode head is the trainer's tail op.
+
+    A subclass states the width and the buffers (`_extra_alloc`), one level's work (`_extra_level`), what follows the first output
+    (`_result`) and `_train_refusal`."""
+
+    cat_out = True
+
+    def _extra_plans(self):
+        return self.__dict__.setdefault("_extra", {})
+
+    def begin(self, n: int, level_hw, dtype, device) -> None:
+        super().begin(n, level_hw, dtype, device)
+        det = self._plan()[R.current_tag()]
+        self._extra_begin(det["n"], det["hw"], det["a0"], det["a_total"], device)
+
+    def _extra_begin(self, n: int, hw, a0, a_total: int, device):
+        """The forward's plan of the cv4 branches: Detect's anchor ranges, the buffers of `_extra_alloc`, the levels done so far."""
+        plan = dict(n=n, hw=hw, a0=a0, a_total=a_total, done=set(), **self._extra_alloc(n, a_total, device))
+        self._extra_plans()[R.current_tag()] = plan
+        return plan
+
+    @staticmethod
+    def _extra_fits(plan, i, x) -> bool:
+        return plan["n"] == int(x.shape[0]) and plan["hw"][i] == (int(x.shape[2]), int(x.shape[3])) and plan["extra"].device == x.device
+
+    def start_level(self, i: int, x: torch.Tensor, defer_ok: bool = True) -> None:
+        super().start_level(i, x, defer_ok)
+        plan = self._extra_plans().get(R.current_tag())
+        if plan is not None and i not in plan["done"] and self._extra_fits(plan, i, x):
+            self._extra_level(plan, i, x)
+            plan["done"].add(i)
+
+    def forward(self, x):
+        if self.training:
+            raise L.UpaError(self._train_refusal)
+        det = super().forward(x)
+        y, raw = (det, None) if self.export else det
+        tag = R.current_tag()
+        plan = self._extra_plans().get(tag)
+        if plan is None or not all(self._extra_fits(plan, i, x[i]) for i in range(self.nl)):
+            # a plan for other sizes, with Detect's own already consumed: the anchor ranges of the sizes that came
+            hw = [(int(t.shape[2]), int(t.shape[3])) for t in x]
+            ends = list(itertools.accumulate(h * w for h, w in hw))
+            plan = self._extra_begin(int(x[0].shape[0]), hw, [0] + ends[:-1], ends[-1], x[0].device)
+        for i in range(self.nl):
+            if i not in plan["done"]:
+                self._extra_level(plan, i, x[i])
+        self._extra_plans().pop(tag, None)
+        extra = plan["extra"]
+        if self.cat_out or self.export:
+            out = self._cat(y, extra)
+        else:
+            out = y
+            y._upa_parts = (y, extra)
+        return self._result(out, raw, plan)
+
+    def _cat(self, y: torch.Tensor, extra: torch.Tensor) -> torch.Tensor:
+        """(B, 4+nc+ne, A) = cat([y, extra], 1) with two strided copies: `upa_copy_view` over one 'pixel' per image when every row is
+        a 16-byte multiple, else `upa_copy_rows` (any A)."""
+        n, cy, a = y.shape
+        ne = int(extra.shape[1])
+        ct = cy + ne
+        cat = R.alloc_plain((n, ct, a), torch.float32, y.device, key=(id(self), "cat"))
+        stream = L.current_stream(y.device)
+        lib = L.lib()
+        for src, c, dst in ((y, cy, cat), (extra, ne, cat[:, cy:])):
+            if (cy * a) % 4 == 0 and (ne * a) % 4 == 0:
+                L.check(lib.upa_copy_view(src.data_ptr(), n, 1, 1, c * a, c * a, dst.data_ptr(), ct * a, L.UPA_F32, stream), "copy_view")
+            else:
+                L.check(lib.upa_copy_rows(src.data_ptr(), n, c * a, c * a, dst.data_ptr(), ct * a, stream), "copy_rows")
+        cat._upa_parts = (y, extra)
+        return cat
+
+    def train(self, mode: bool = True):
+        self.__dict__.pop("_extra", None)
+        return super().train(mode)
+
+
+class Segment(ExtraDetect):
     """YOLO Segment head (head.py:790-837): Detect + `proto = Proto(ch[0], npr, nm)` + per-level mask-coefficient branches
     `cv4[l] = Conv3x3 -> Conv3x3 -> nn.Conv2d(c4, nm, 1)`, c4 = max(ch[0] // 4, nm).
 
-    Eval forward returns the reference's `(cat([y, mc], 1), (raw, mc, p))`: y = Detect's (B, 4+nc, A) output, untouched (every fused
-    Detect form and NMS kernel keeps its image stride), mc = (B, nm, A) f32 coefficients (`upa_mask_coef_rows` writes each level's
-    map into its anchor range), p = the (B, nm, 2H0, 2W0) protos as an NHWC view.  With `cat_out = False` the concatenated copy is
-    not made and the first element is y itself; `utils.ops.segment_postprocess_raw` reads y, mc and p either way.  The
-    concatenated tensor carries `_upa_parts = (y, mc)`, so `utils.nms` runs on y and gathers the coefficients of the kept rows.
+    Eval forward returns `(cat([y, mc], 1), (raw, mc, p))`: mc = (B, nm, A) f32 coefficients (`upa_mask_coef_rows` writes each level's
+    map into its anchor range), p = the (B, nm, 2H0, 2W0) protos as an NHWC view; Proto runs with level 0.
+    `utils.ops.segment_postprocess_raw` reads y, mc and p."""
 
-    Scheduling: a level's cv4 branch runs when `start_level` is called for it (the moment its feature map exists), and Proto with
-    level 0; levels the executor did not start (a direct call, or the levels `Detect.forward` groups) run in `forward`."""
-
-    cat_out = True
+    _train_refusal = ("training-mode Segment.forward is not on the HIP path: train a segmentation model with engine.trainer.SegmentationTrainer (its "
+                      "SegmentT op holds the train-mode head)")
 
     def __init__(self, nc: int = 80, nm: int = 32, npr: int = 256, ch: tuple = ()):
         super().__init__(nc, ch)
@@ -533,33 +620,10 @@ class Segment(Detect):
         c4 = max(ch[0] // 4, self.nm)
         self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.nm, 1)) for x in ch)
 
-    def _seg_plans(self):
-        return self.__dict__.setdefault("_seg", {})
+    def _extra_alloc(self, n, a_total, device):
+        return dict(extra=R.alloc_plain((n, self.nm, a_total), torch.float32, device, key=(id(self), "mc")), p=None)
 
-    def begin(self, n: int, level_hw, dtype, device) -> None:
-        super().begin(n, level_hw, dtype, device)
-        self._seg_begin(n, level_hw, device)
-
-    def _seg_begin(self, n, level_hw, device):
-        a0, tot = [], 0
-        for (h, w) in level_hw:
-            a0.append(tot)
-            tot += int(h) * int(w)
-        mc = R.alloc_plain((int(n), self.nm, tot), torch.float32, device, key=(id(self), "mc"))
-        self._seg_plans()[R.current_tag()] = dict(mc=mc, a0=a0, a_total=tot, n=int(n), hw=[(int(h), int(w)) for h, w in level_hw],
-                                                  done=set(), p=None)
-
-    def start_level(self, i: int, x: torch.Tensor, defer_ok: bool = True) -> None:
-        super().start_level(i, x, defer_ok)
-        plan = self._seg_plans().get(R.current_tag())
-        if plan is not None and i not in plan["done"] and self._seg_fits(plan, i, x):
-            self._seg_level(plan, i, x)
-
-    @staticmethod
-    def _seg_fits(plan, i, x) -> bool:
-        return plan["n"] == int(x.shape[0]) and plan["hw"][i] == (int(x.shape[2]), int(x.shape[3])) and plan["mc"].device == x.device
-
-    def _seg_level(self, plan, i: int, x: torch.Tensor) -> None:
+    def _extra_level(self, plan, i: int, x: torch.Tensor) -> None:
         """cv4[i] into mc[:, :, a0_i : a0_i + H_i W_i] (and Proto, for level 0)."""
         x = R.to_nhwc(x, x.dtype)
         seq = self.cv4[i]
@@ -567,75 +631,30 @@ class Segment(Detect):
         pk = self._packed(seq[2], None, x.device, x.dtype, False)
         c = hip_conv2d(t, pk, 1, 0, L.ACT_NONE, key=(id(self), "mc_map", i))
         vc = R.view_of(c)
-        L.check(L.lib().upa_mask_coef_rows(vc.ptr, vc.n, vc.h, vc.w, vc.c, vc.ld, vc.dtype, plan["mc"].data_ptr(), self.nm, 0,
+        L.check(L.lib().upa_mask_coef_rows(vc.ptr, vc.n, vc.h, vc.w, vc.c, vc.ld, vc.dtype, plan["extra"].data_ptr(), self.nm, 0,
                                            plan["a_total"], plan["a0"][i], L.current_stream(x.device)), "mask_coef_rows")
-        plan["done"].add(i)
         if i == 0:
             plan["p"] = self.proto(x)
 
-    def forward(self, x):
-        if self.training:
-            raise L.UpaError("training-mode Segment.forward is not on the HIP path: train a segmentation model with engine.trainer.SegmentationTrainer (its "
-                             "SegmentT op holds the train-mode head)")
-        det = super().forward(x)
-        y, raw = (det, None) if self.export else det
-        tag = R.current_tag()
-        plan = self._seg_plans().get(tag)
-        if plan is None or not all(self._seg_fits(plan, i, x[i]) for i in range(self.nl)):
-            self._seg_begin(x[0].shape[0], [(t.shape[2], t.shape[3]) for t in x], x[0].device)
-            plan = self._seg_plans()[tag]
-        for i in range(self.nl):
-            if i not in plan["done"]:
-                self._seg_level(plan, i, x[i])
-        self._seg_plans().pop(tag, None)
-        mc, p = plan["mc"], plan["p"]
-        if self.cat_out or self.export:
-            out = self._cat(y, mc)
-        else:
-            out = y
-        return (out, p) if self.export else (out, (raw, mc, p))
-
-    def _cat(self, y: torch.Tensor, mc: torch.Tensor) -> torch.Tensor:
-        """(B, 4+nc+nm, A) = cat([y, mc], 1) with two strided copies: `upa_copy_view` over one 'pixel' per image when every row is
-        a 16-byte multiple, else `upa_copy_rows` (any A)."""
-        n, cy, a = y.shape
-        ne = int(mc.shape[1])  # nm (Segment) or nk (Pose, which shares this method)
-        ct = cy + ne
-        cat = R.alloc_plain((n, ct, a), torch.float32, y.device, key=(id(self), "cat"))
-        stream = L.current_stream(y.device)
-        lib = L.lib()
-        for src, c, dst in ((y, cy, cat), (mc, ne, cat[:, cy:])):
-            if (cy * a) % 4 == 0 and (ne * a) % 4 == 0:
-                L.check(lib.upa_copy_view(src.data_ptr(), n, 1, 1, c * a, c * a, dst.data_ptr(), ct * a, L.UPA_F32, stream), "copy_view")
-            else:
-                L.check(lib.upa_copy_rows(src.data_ptr(), n, c * a, c * a, dst.data_ptr(), ct * a, stream), "copy_rows")
-        cat._upa_parts = (y, mc)
-        return cat
-
-    def train(self, mode: bool = True):
-        self.__dict__.pop("_seg", None)
-        return super().train(mode)
+    def _result(self, out, raw, plan):
+        return (out, plan["p"]) if self.export else (out, (raw, plan["extra"], plan["p"]))
 
 
-class Pose(Detect):
+class Pose(ExtraDetect):
     """YOLO Pose head (head.py:1208-1273): Detect + per-level keypoint branches `cv4[l] = Conv3x3 -> Conv3x3 -> nn.Conv2d(c4, nk, 1)`,
     nk = kpt_shape[0] * kpt_shape[1], c4 = max(ch[0] // 4, nk).
 
-    Eval forward returns the reference's `(cat([y, pred_kpt], 1), (raw, kpt))`: y = Detect's (B, 4+nc, A) output, untouched,
-    pred_kpt = (B, nk, A) f32 decoded keypoints and kpt the undecoded ones (None with `keep_raw = False`): one `upa_kpt_decode_rows`
-    launch per level writes both into the level's anchor range.  With `cat_out = False` the concatenated copy is not made and the first
-    element is y itself (`utils.ops.pose_postprocess_raw` reads the parts either way); the concatenated tensor carries
-    `_upa_parts = (y, pred_kpt)`, so `utils.nms` runs on y and gathers the keypoints of the kept rows.
+    Eval forward returns `(cat([y, pred_kpt], 1), (raw, kpt))`: pred_kpt = (B, nk, A) f32 decoded keypoints and kpt the undecoded
+    ones (None with `keep_raw = False`): one `upa_kpt_decode_rows` launch per level writes both into the level's anchor range.
+    `utils.ops.pose_postprocess_raw` reads y and pred_kpt.
 
     51 channels: nk = 17 * 3 (and c4, for the n / s / m scales) is no multiple of the convolutions' 16-byte channel rule.  The
     state_dict keeps the reference's shapes; the PACKED weights are padded to multiples of 8 channels (`_packed_pad`): padded output
     channels have zero filters and zero folded bias (SiLU(0) = 0, so they stay zero), the next conv's padded input channels have zero
-    filters (their products add exact zeros: the real channels are bit-identical to an unpadded convolution).
+    filters (their products add exact zeros: the real channels are bit-identical to an unpadded convolution)."""
 
-    Scheduling follows Segment: a level's cv4 branch runs when `start_level` is called for it, the rest in `forward`.  Inference only:
-    a train-mode forward raises (pose training, v8PoseLoss, is `engine.trainer.PoseTrainer`'s: its `PoseT` op holds the train-mode head)."""
-
-    cat_out = True
+    _train_refusal = ("training-mode Pose.forward is not on the HIP path: pose training (v8PoseLoss) goes through "
+                      "engine.trainer.PoseTrainer (its PoseT op holds the train-mode head)")
     PAD = 8  # channels per 16 bytes of bf16; a multiple of f32's 4, so one padded layout serves both dtypes
 
     def __init__(self, nc: int = 80, kpt_shape: tuple = (17, 3), ch: tuple = ()):
@@ -693,70 +712,25 @@ class Pose(Detect):
         c = hip_conv2d(t1, pk2, 1, 0, L.ACT_NONE, key=(id(self), "kpt_map", i))
         return t0, t1, c
 
-    def _pose_plans(self):
-        return self.__dict__.setdefault("_pose", {})
+    def _extra_alloc(self, n, a_total, device):
+        shape = (n, self.nk, a_total)
+        return dict(extra=R.alloc_plain(shape, torch.float32, device, key=(id(self), "pred_kpt")),
+                    kpt=R.alloc_plain(shape, torch.float32, device, key=(id(self), "kpt")) if self.keep_raw else None)
 
-    def begin(self, n: int, level_hw, dtype, device) -> None:
-        super().begin(n, level_hw, dtype, device)
-        self._pose_begin(n, level_hw, device)
-
-    def _pose_begin(self, n, level_hw, device):
-        a0, tot = [], 0
-        for (h, w) in level_hw:
-            a0.append(tot)
-            tot += int(h) * int(w)
-        pk = R.alloc_plain((int(n), self.nk, tot), torch.float32, device, key=(id(self), "pred_kpt"))
-        kpt = R.alloc_plain((int(n), self.nk, tot), torch.float32, device, key=(id(self), "kpt")) if self.keep_raw else None
-        self._pose_plans()[R.current_tag()] = dict(pk=pk, kpt=kpt, a0=a0, a_total=tot, n=int(n), hw=[(int(h), int(w)) for h, w in level_hw],
-                                                   done=set())
-
-    def start_level(self, i: int, x: torch.Tensor, defer_ok: bool = True) -> None:
-        super().start_level(i, x, defer_ok)
-        plan = self._pose_plans().get(R.current_tag())
-        if plan is not None and i not in plan["done"] and self._pose_fits(plan, i, x):
-            self._pose_level(plan, i, x)
-
-    @staticmethod
-    def _pose_fits(plan, i, x) -> bool:
-        return plan["n"] == int(x.shape[0]) and plan["hw"][i] == (int(x.shape[2]), int(x.shape[3])) and plan["pk"].device == x.device
-
-    def _pose_level(self, plan, i: int, x: torch.Tensor) -> None:
+    def _extra_level(self, plan, i: int, x: torch.Tensor) -> None:
         """cv4[i] decoded into pred_kpt[:, :, a0_i : a0_i + H_i W_i] (and the undecoded values into kpt)."""
         _, _, c = self.kpt_chain(i, x)
         vc = R.view_of(c)
         kpt = plan["kpt"]
         nkpt, ndim = (int(v) for v in self.kpt_shape)
         L.check(L.lib().upa_kpt_decode_rows(vc.ptr, vc.n, vc.h, vc.w, vc.c, vc.ld, vc.dtype, nkpt, ndim, float(self.stride[i]),
-                                            plan["pk"].data_ptr(), plan["a_total"], plan["a0"][i],
+                                            plan["extra"].data_ptr(), plan["a_total"], plan["a0"][i],
                                             None if kpt is None else kpt.data_ptr(), L.current_stream(x.device)), "kpt_decode_rows")
-        plan["done"].add(i)
 
-    def forward(self, x):
-        if self.training:
-            raise L.UpaError("training-mode Pose.forward is not on the HIP path: pose training (v8PoseLoss) goes through "
-                             "engine.trainer.PoseTrainer (its PoseT op holds the train-mode head)")
-        det = super().forward(x)
-        y, raw = (det, None) if self.export else det
-        tag = R.current_tag()
-        plan = self._pose_plans().get(tag)
-        if plan is None or not all(self._pose_fits(plan, i, x[i]) for i in range(self.nl)):
-            self._pose_begin(x[0].shape[0], [(t.shape[2], t.shape[3]) for t in x], x[0].device)
-            plan = self._pose_plans()[tag]
-        for i in range(self.nl):
-            if i not in plan["done"]:
-                self._pose_level(plan, i, x[i])
-        self._pose_plans().pop(tag, None)
-        pk, kpt = plan["pk"], plan["kpt"]
-        out = self._cat(y, pk) if (self.cat_out or self.export) else y
-        if out is y:
-            y._upa_pose = pk  # the parts travel with y: pose_postprocess_raw needs no second return value
-        return out if self.export else (out, (raw, kpt))
-
-    _cat = Segment._cat
-
-    def train(self, mode: bool = True):
-        self.__dict__.pop("_pose", None)
-        return super().train(mode)
+    def _result(self, out, raw, plan):
+        if not (self.cat_out or self.export):
+            out._upa_pose = plan["extra"]  # what `_upa_parts[1]` was called on y before every head shared one convention: kept for its readers
+        return out if self.export else (out, (raw, plan["kpt"]))
 
 
 class Classify(nn.Module):

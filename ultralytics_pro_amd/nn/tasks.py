@@ -541,8 +541,8 @@ class DetectionModel(BaseModel):
 
 
 class SegmentationModel(DetectionModel):
-    """YOLO segmentation model (tasks.py:1343-1365): a DetectionModel whose head is `Segment`.  Inference only: training
-    (v8SegmentationLoss) and mask mAP are not on the HIP path."""
+    """YOLO segmentation model (tasks.py:1343-1365): a DetectionModel whose head is `Segment`.  Inference here; validation
+    (box and mask mAP) is `engine.validator.SegmentationValidator`, training (v8SegmentationLoss) `engine.trainer.SegmentationTrainer`."""
 
     def __init__(self, cfg="yolov8n-seg.yaml", ch=3, nc=None, verbose=False):
         super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
@@ -552,7 +552,8 @@ class SegmentationModel(DetectionModel):
 
 class PoseModel(DetectionModel):
     """YOLO pose model (tasks.py:1368-1395): a DetectionModel whose head is `Pose`.  `data_kpt_shape` overrides the YAML's `kpt_shape`
-    as in the reference.  Inference and validation (`engine.validator.PoseValidator`); pose training (v8PoseLoss) is not built."""
+    as in the reference.  Inference here; validation (box and pose mAP) is `engine.validator.PoseValidator`, training (v8PoseLoss)
+    `engine.trainer.PoseTrainer`."""
 
     def __init__(self, cfg="yolov8n-pose.yaml", ch=3, nc=None, data_kpt_shape=(None, None), verbose=False):
         if not isinstance(cfg, dict):

@@ -23,6 +23,8 @@ def nms_raw(prediction: torch.Tensor, conf_thres=0.25, iou_thres=0.45, classes=N
         prediction = prediction[0]
     L.require_gpu(prediction, "non_max_suppression")
     parts = getattr(prediction, "_upa_parts", None)
+    if parts is not None and parts[0] is prediction:  # y itself (a head with `cat_out = False`): plain NMS, as on any Detect output
+        parts = None
     if parts is not None or (nc and prediction.dim() == 3 and prediction.shape[1] > 4 + nc):
         if parts is not None:
             y, extra = parts

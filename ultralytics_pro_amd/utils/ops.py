@@ -142,21 +142,43 @@ def process_mask_native(protos, masks_in, bboxes, shape):
     return _single_image_masks(p, masks_in, bboxes, out, True, (1.0, 1.0), scale_masks_window(int(mh), int(mw), out))
 
 
-def _seg_parts(preds, nc: int):
-    """(y (B, 4+nc, A), mc (B, nm, A), protos) from a Segment head's eval output `(y | cat([y, mc], 1), (raw, mc, p))`."""
-    first, second = preds[0], preds[1]
-    if not (isinstance(second, (list, tuple)) and len(second) == 3):
-        raise L.UpaError("segment postprocess expects a Segment head's eval output (y, (raw, mc, protos))")
-    _, mc, p = second
+def _extra_parts(preds, nc: int):
+    """(y (B, 4+nc, A), extra (B, ne, A)) from the eval output `(y | cat([y, extra], 1), rest)` of a head with an extra per-anchor
+    branch (Segment: mask coefficients, Pose: decoded keypoints), or from its first element: the parts that travel with it
+    (`_upa_parts`); without them a Segment output's own mc next to y or the detection rows of the concatenated tensor, else the two
+    halves of a (B, 4+nc+ne, A) tensor with nc given."""
+    first, rest = (preds[0], preds[1] if len(preds) > 1 else None) if isinstance(preds, (list, tuple)) else (preds, None)
     parts = getattr(first, "_upa_parts", None)
     if parts is not None:
-        y = parts[0]
-    else:
-        y = first
+        return parts
+    if isinstance(rest, (list, tuple)) and len(rest) == 3:  # (raw, mc, protos)
+        mc = rest[1]
         nc = nc or (int(first.shape[1]) - 4 - int(mc.shape[1]))
-        if first.shape[1] != 4 + nc:  # a concatenated tensor without its parts: the detection rows as a contiguous copy
-            y = first[:, :4 + nc].contiguous()
-    return y, mc, p
+        # (a concatenated tensor without its parts: the detection rows as a contiguous copy)
+        return (first if first.shape[1] == 4 + nc else first[:, :4 + nc].contiguous()), mc
+    if not nc or first.dim() != 3 or first.shape[1] <= 4 + nc:
+        raise L.UpaError("pose postprocess expects a Pose head's eval output (or a (B, 4+nc+nk, A) tensor with nc given)")
+    return first[:, :4 + nc].contiguous(), first[:, 4 + nc:].contiguous()
+
+
+def _seg_parts(preds, nc: int):
+    """(y (B, 4+nc, A), mc (B, nm, A), protos) from a Segment head's eval output `(y | cat([y, mc], 1), (raw, mc, p))`."""
+    if not (isinstance(preds[1], (list, tuple)) and len(preds[1]) == 3):
+        raise L.UpaError("segment postprocess expects a Segment head's eval output (y, (raw, mc, protos))")
+    return _extra_parts(preds, nc)[0], preds[1][1], preds[1][2]
+
+
+def nms_gather_extra(y, extra, rows_key, conf_thres, iou_thres, classes=None, agnostic=False, multi_label=False, max_det=300, key=None):
+    """NMS on y (B, 4+nc, A), then the kept anchors' columns of extra (B, ne, A) behind their detections: (out (B, max_det, 6), rows
+    (B, max_det, 6 + ne) under the buffer key `rows_key`, counts (B,), keep (B, max_det)), no host synchronisation."""
+    from ..engine import runtime as R
+    from .nms import nms_raw
+    b, ne, a = extra.shape
+    out, counts, keep = nms_raw(y, conf_thres, iou_thres, classes, agnostic, multi_label, max_det, int(y.shape[1]) - 4, key=key)
+    rows = R.alloc_plain((b, max_det, 6 + ne), torch.float32, y.device, key=rows_key)
+    L.check(L.lib().upa_nms_gather_extra(extra.data_ptr(), b, ne, a, keep.data_ptr(), counts.data_ptr(), int(max_det), out.data_ptr(),
+                                         rows.data_ptr(), 6 + ne, L.current_stream(y.device)), "nms_gather_extra")
+    return out, rows, counts, keep
 
 
 def segment_postprocess_raw(preds, conf_thres: float = 0.25, iou_thres: float = 0.7, classes=None, agnostic: bool = False,
@@ -173,15 +195,10 @@ def segment_postprocess_raw(preds, conf_thres: float = 0.25, iou_thres: float = 
     proto map, which is what Proto produces from the stride-8 level), or orig_shape with `retina_masks` (process_mask_native).  One
     `orig_shape` for the whole batch."""
     from ..engine import runtime as R
-    from .nms import nms_raw
     y, mc, p = _seg_parts(preds, nc)
-    nc = int(y.shape[1]) - 4
-    b, nm, a = mc.shape
+    b, nm, _ = mc.shape
     dev = y.device
-    out, counts, keep = nms_raw(y, conf_thres, iou_thres, classes, agnostic, multi_label, max_det, nc, key=key)
-    rows = R.alloc_plain((b, max_det, 6 + nm), torch.float32, dev, key=(key, "seg_rows"))
-    L.check(L.lib().upa_nms_gather_extra(mc.data_ptr(), b, nm, a, keep.data_ptr(), counts.data_ptr(), int(max_det), out.data_ptr(),
-                                         rows.data_ptr(), 6 + nm, L.current_stream(dev)), "nms_gather_extra")
+    _, rows, counts, _ = nms_gather_extra(y, mc, (key, "seg_rows"), conf_thres, iou_thres, classes, agnostic, multi_label, max_det, key)
     pv = _protos_nhwc(p)
     mh, mw = int(pv.shape[2]), int(pv.shape[3])
     ih, iw = (4 * mh, 4 * mw) if imgsz is None else (int(imgsz[0]), int(imgsz[1]))
@@ -259,34 +276,13 @@ def scale_coords(img1_shape, coords: torch.Tensor, img0_shape, ratio_pad=None, n
     return coords
 
 
-def _pose_parts(preds, nc: int):
-    """(y (B, 4+nc, A), pred_kpt (B, nk, A)) from a Pose head's eval output `(y | cat([y, pred_kpt], 1), (raw, kpt))` or its first
-    element."""
-    first = preds[0] if isinstance(preds, (list, tuple)) else preds
-    parts = getattr(first, "_upa_parts", None)
-    if parts is not None:
-        return parts
-    pk = getattr(first, "_upa_pose", None)
-    if pk is not None:
-        return first, pk
-    if not nc or first.dim() != 3 or first.shape[1] <= 4 + nc:
-        raise L.UpaError("pose postprocess expects a Pose head's eval output (or a (B, 4+nc+nk, A) tensor with nc given)")
-    return first[:, :4 + nc].contiguous(), first[:, 4 + nc:].contiguous()
-
-
 def pose_postprocess_raw(preds, conf_thres: float = 0.25, iou_thres: float = 0.7, classes=None, agnostic: bool = False,
                          max_det: int = 300, nc: int = 0, key=None, multi_label: bool = False):
     """Device-side pose postprocess with no host synchronisation (capturable in `compile(post=...)` and `PipelinedRunner`): NMS ->
     keypoint gather (`upa_nms_gather_extra`).  Returns (rows (B, max_det, 6 + nk) [box, conf, cls, keypoints], counts (B,), keep
     (B, max_det)): in network-input pixels, rows past counts zero."""
-    from ..engine import runtime as R
-    from .nms import nms_raw
-    y, pk = _pose_parts(preds, nc)
-    b, nk, a = pk.shape
-    out, counts, keep = nms_raw(y, conf_thres, iou_thres, classes, agnostic, multi_label, max_det, int(y.shape[1]) - 4, key=key)
-    rows = R.alloc_plain((b, max_det, 6 + nk), torch.float32, y.device, key=(key, "pose_rows"))
-    L.check(L.lib().upa_nms_gather_extra(pk.data_ptr(), b, nk, a, keep.data_ptr(), counts.data_ptr(), int(max_det), out.data_ptr(),
-                                         rows.data_ptr(), 6 + nk, L.current_stream(y.device)), "nms_gather_extra")
+    y, pk = _extra_parts(preds, nc)
+    _, rows, counts, keep = nms_gather_extra(y, pk, (key, "pose_rows"), conf_thres, iou_thres, classes, agnostic, multi_label, max_det, key)
     return rows, counts, keep
 
 
