@@ -153,6 +153,18 @@ def payload_of_two(bufs, n, c, what, **kw):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the zero pass of the loss kernels (csrc/segment_train.hip ml_zero_bg_kernel, csrc/pose_train.hip kl_zero_bg_kernel)
+# ---------------------------------------------------------------------------------------------------------------------
+ZERO_PASS_ITEMS = 2048 * 256                 # the pass's grid cap x its workgroup: past this many 16-byte stores the grid strides
+ZERO_PASS_LEVELS = ((64, 64), (8, 8), (2, 2))  # A = 4164: the levels of the cases that reach the stride
+
+
+def zero_pass_items(rows, width, dtype):
+    """The 16-byte stores of a zero pass over `rows` gradient rows of `width` elements of `dtype`."""
+    return rows * (width // (16 // torch.empty((), dtype=dtype).element_size()))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the fault latch: one per process
 # ---------------------------------------------------------------------------------------------------------------------
 _FAULTED = []

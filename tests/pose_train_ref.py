@@ -5,6 +5,8 @@ formulas, and the case builders.  CPU only."""
 import torch
 import torch.nn.functional as F
 
+from tests.kernel_check import ZERO_PASS_ITEMS, ZERO_PASS_LEVELS
+from tests.kernel_check import zero_pass_items as _zero_pass_items
 from tests.loss_ref import HW, STRIDES
 
 U32 = 2.0 ** -24
@@ -163,22 +165,53 @@ CASES = {  # name: (kpt_shape, c, variant)
     "one3d": ((1, 3), 8, "base"),
     "all_fg": ((17, 3), 56, "all"),
     "none_fg": ((17, 3), 56, "none"),
+    "all_wide": ((17, 3), 56, "all"),
+    "stride": ((17, 3), 56, "stride"),
 }
+# Cases off the default geometry.  "all_wide": the anchor kernel launches min((min(10 G, A) + 3) / 4, 128) workgroups per image, so the
+# clamp needs 10 G >= 510 AND A >= 510 - on the default levels (A = 315) G = 60 gives 79 workgroups and no clamp; these levels have
+# A = 630: 150 clamped to 128, and the 158 four-slot groups of an all-foreground image give workgroups 0..29 a second turn.
+# "stride": c = 56 on tests/kernel_check's ZERO_PASS_LEVELS with the smallest b at which b A (c / vec) is past the zero pass's
+# ZERO_PASS_ITEMS: 9 images in f32 (37476 x 14), 18 in bf16 (74952 x 7).
+WIDE_HW = ((20, 24), (10, 12), (5, 6))
 
 
-def kpt_case(name, dtype=torch.float32, hw=HW, strides=STRIDES):
-    """The kernel test's inputs (values representable in `dtype`), b = 3 on tests/loss_ref's default levels (A = 315, past one
-    256-thread workgroup).  variant "base": image 0 - gt 0 on two anchors of level 0 and one of level 1 (the area is taken at two
-    strides), gt 1 on a level-1 anchor (index past 256) and a level-2 anchor, gt 2 with EVERY keypoint invisible, gt 3 unassigned;
+def geometry(name, dtype=torch.float32):
+    """(b, G, hw) of a case."""
+    if name == "all_wide":
+        return 3, 60, WIDE_HW
+    if name == "stride":
+        return (18 if dtype == torch.bfloat16 else 9), 6, ZERO_PASS_LEVELS
+    return 3, 6, HW
+
+
+def anchor_groups(case):
+    """(workgroups per image that upa_kpt_loss launches, the count before the clamp to 128)."""
+    A, G = case["assign"].shape[1], case["gt"].shape[1]
+    want = (min(10 * G, A) + 3) // 4
+    return min(want, 128), want
+
+
+def zero_pass_items(case, dtype):
+    return _zero_pass_items(case["assign"].numel(), case["c"], dtype)
+
+
+def kpt_case(name, dtype=torch.float32, hw=None, strides=STRIDES, b=None, G=None):
+    """The kernel test's inputs (values representable in `dtype`); b, G and the levels default to `geometry(name, dtype)`: b = 3, G = 6
+    on tests/loss_ref's default levels (A = 315, past one 256-thread workgroup) for every case but "all_wide" and "stride".
+    variant "base": image 0 - gt 0 on two anchors of level 0 and one of level 1 (the area is taken at two strides), gt 1 on a level-1 anchor (index past 256) and a level-2 anchor, gt 2 with EVERY keypoint invisible, gt 3 unassigned;
     image 1 - an anchor assigned to row 2 >= n_gt = 2 and one to row -5 (background both), one real assignment; image 2 - assignments
     but n_gt = 0.  Keypoints lie around the first anchor of their gt (so 1 - exp(-e) is neither 0 nor 1 there), some outside their box,
-    some with visibility 0 or 2.  "all": every anchor foreground; "none": no anchor."""
+    some with visibility 0 or 2.  "all": every anchor foreground; "none": no anchor; "stride": image i has the boxes of image i % 3, the
+    first image is foreground at anchors 0, 1 and the last of level 0, the last image at the first anchors of levels 1 and 2 and at the
+    very last anchor."""
     from ultralytics_pro_amd.utils import procedural as P
     from ultralytics_pro_amd.utils.metrics import OKS_SIGMA
     kpt_shape, c, variant = CASES[name]
     nkpt, ndim = kpt_shape
     nk = nkpt * ndim
-    b, G = 3, 6
+    gb, gG, ghw = geometry(name, dtype)
+    b, G, hw = gb if b is None else b, gG if G is None else G, ghw if hw is None else hw
 
     def rnd(key, shape, lo, hi):
         return P.uniform(f"pose_train:{name}:{key}", shape, lo, hi)
@@ -186,10 +219,10 @@ def kpt_case(name, dtype=torch.float32, hw=HW, strides=STRIDES):
     A = sum(h * w for h, w in hw)
     a1, a2 = hw[0][0] * hw[0][1], hw[0][0] * hw[0][1] + hw[1][0] * hw[1][1]
     gt = torch.zeros(b, G, 5)
-    for i, rows in enumerate(_BOXES):
-        for g, bx in enumerate(rows):
+    for i in range(b):
+        for g, bx in enumerate(_BOXES[i % 3]):
             gt[i, g, 1:] = torch.tensor(bx)
-    n_gt = torch.tensor([4, 2, 0], dtype=torch.int32)
+    n_gt = torch.tensor([(4, 2, 0)[i % 3] for i in range(b)], dtype=torch.int32)
     assign = torch.full((b, A), -1, dtype=torch.int32)
     if variant == "base":
         w0, w1, w2 = hw[0][1], hw[1][1], hw[2][1]
@@ -205,9 +238,13 @@ def kpt_case(name, dtype=torch.float32, hw=HW, strides=STRIDES):
         assign[2, 3] = 0                    # n_gt = 0: background whatever the array says
         assign[2, a2 + 4] = 0
     elif variant == "all":
-        n_gt = torch.tensor([4, 2, 1], dtype=torch.int32)
+        n_gt = torch.tensor([(4, 2, 1)[i % 3] for i in range(b)], dtype=torch.int32)
         for i in range(b):
             assign[i] = (torch.arange(A) * 7 + i) % int(n_gt[i])
+    elif variant == "stride":
+        n_gt = torch.tensor([(4, 2, 1)[i % 3] for i in range(b)], dtype=torch.int32)
+        assign[0, 0], assign[0, 1], assign[0, a1 - 1] = 0, 1, 3
+        assign[b - 1, a1], assign[b - 1, a2], assign[b - 1, A - 1] = 0, 0, 0
     # keypoints of gt (i, g): around the decoded prediction of the first anchor assigned to it, up to 0.6 cells away
     cells = _cells(hw)
     gt_kpt = torch.zeros(b, G, nkpt, 3)
@@ -216,7 +253,7 @@ def kpt_case(name, dtype=torch.float32, hw=HW, strides=STRIDES):
     for i in range(b):
         for g in range(G):
             x1, y1, x2, y2 = (float(v) for v in gt[i, g, 1:])
-            first = [a for a in range(A) if int(assign[i, a]) == g]
+            first = (assign[i] == g).nonzero().flatten().tolist()
             if first:
                 x, y, l = cells[first[0]]
                 v = kpts[l][i, y, x, :nk].view(nkpt, ndim)

@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 BF16, F32 = torch.bfloat16, torch.float32
 U32, U16 = 2.0 ** -24, 2.0 ** -8  # unit roundoffs (half an ulp, relative) of round to nearest: f32 (24-bit significand), bf16 (8-bit)
 CONVT_SHAPES = [(2, 5, 7, 16, 16), (1, 20, 20, 64, 64), (3, 9, 4, 32, 64)]
+CONVT_CASES = [(s, d) for d in (F32, BF16) for s in CONVT_SHAPES + SR.CONVT_EXTRA[d]]
 
 
 def _es(dtype):
@@ -59,15 +60,23 @@ def _convt_run(shape, dtype, accumulate, x, dy, wt, prev):
 
 
 @pytest.mark.parametrize("accumulate", [False, True], ids=["write", "accumulate"])
-@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("shape", CONVT_SHAPES, ids=lambda s: "x".join(str(v) for v in s))
+@pytest.mark.parametrize("shape,dtype", CONVT_CASES, ids=lambda v: "x".join(str(k) for k in v) if isinstance(v, tuple) else {F32: "f32", BF16: "bf16"}[v])
 @KC.stop_after_fault
 def test_conv_transpose_bwd_matches_float64(shape, dtype, accumulate):
     """dx, dW, db on strided views with guard bands, two runs bit for bit.  Bounds: products of the (exactly representable) operands are
     exact in f32; a K-term f32 accumulation in any order errs by at most (K + 8) u32 sum|products| (K = 4 cout for dx, n h w for dW,
     4 n h w for db; the split-K combine adds at most 64 more terms); plus the rounding of the stored value (bf16 for dx in bf16 mode)
-    and, when accumulating, of the sum with the previous value."""
+    and, when accumulating, of the sum with the previous value.
+    Past the three one-tile shapes (SR.CONVT_EXTRA): cin 72 / 80 - two cin tiles, the second partial (blockIdx.y = 1 with ci < cin in
+    force); (24, 8) - 4 cout = 32, one partial row tile and a partial 16-channel tile; (40, 24) - 4 cout = 96, the tap changes inside a
+    64-row tile off a wave boundary; (128, 128) - full second tiles with K = 9 pixels below one split; 1023 pixels - 8 splits, the
+    last one pixel short of kc = 128; 8192 pixels - the 64-split cap."""
     n, h, w, cin, cout = shape
+    splits, kc = SR.ctb_splits(cin, cout, n * h * w, 32 if dtype == BF16 else 4)
+    if n * h * w == 1023:
+        assert splits == 8 and kc == 128 and n * h * w % kc
+    if n * h * w == 8192:
+        assert splits == 64
     x, dy, wt, prev = _convt_inputs(shape, dtype)
     E = 16 // _es(dtype)
     (dx, dw, db), (mx, mw_, mb) = SR.convt_bwd_ref(x, dy, wt)
@@ -102,8 +111,9 @@ def test_conv_transpose_bwd_refusals_leave_the_outputs_untouched():
 
 
 # ---- 2. upa_mask_loss -----------------------------------------------------------------------------------------------------------------
-def _mask_run(case, dtype, stride=1, nm_arg=None, dev_scale=None):
-    """One call on strided views with guard bands; returns (rc, item buffer, dproto buffer, [dcoef buffers])."""
+def _mask_run(case, dtype, stride=1, nm_arg=None, dev_scale=None, **ov):
+    """One call on strided views with guard bands; returns (rc, item buffer, dproto buffer, [dcoef buffers]).  `ov` overrides single
+    arguments for the refusal test: n_levels, daddr_add (bytes), ldd_add (elements), ws_short (bytes), hs (the whole array)."""
     DEV, L, lib, st = KC.env()
     E, es = 16 // _es(dtype), _es(dtype)
     proto, coefs = case["proto"], case["coefs"]
@@ -122,26 +132,31 @@ def _mask_run(case, dtype, stride=1, nm_arg=None, dev_scale=None):
     item = KC.out_buf((1,), 9, F32, 1)
     nws = lib.upa_mask_loss_workspace_bytes(b, A)
     ws = torch.full((nws + 64,), 0xAB, dtype=torch.uint8, device=DEV)
-    FP, IA = C.c_void_p * nl, C.c_int * nl
+    na = max(nl, ov.get("n_levels", nl))  # the ABI arrays have exactly n_levels entries (the last level again past the case's own)
+    FP, IA = C.c_void_p * na, C.c_int * na
+    up = (lambda v: list(v) + [v[-1]] * (na - nl))
     ld = nm + 2 * E
     gsd = None if dev_scale is None else torch.tensor([dev_scale], dtype=F32, device=DEV)
     rc = lib.upa_mask_loss(pb.data_ptr() + E * es, b, mh, mw, nm if nm_arg is None else nm_arg, ld,
-                           C.cast(FP(*[t.data_ptr() + E * es for t in cbs]), C.c_void_p),
-                           C.cast(FP(*[t.data_ptr() + E * es for t in dcbs]), C.c_void_p),
-                           C.cast(IA(*[c.shape[1] for c in coefs]), C.c_void_p), C.cast(IA(*[c.shape[2] for c in coefs]), C.c_void_p),
-                           C.cast(IA(*[ld] * nl), C.c_void_p), C.cast(IA(*[ld] * nl), C.c_void_p), nl, asg.data_ptr(), stride,
+                           C.cast(FP(*up([t.data_ptr() + E * es for t in cbs])), C.c_void_p),
+                           C.cast(FP(*up([t.data_ptr() + E * es + ov.get("daddr_add", 0) for t in dcbs])), C.c_void_p),
+                           C.cast(IA(*up(ov.get("hs", [c.shape[1] for c in coefs]))), C.c_void_p),
+                           C.cast(IA(*up([c.shape[2] for c in coefs])), C.c_void_p),
+                           C.cast(IA(*[ld] * na), C.c_void_p), C.cast(IA(*[ld + ov.get("ldd_add", 0)] * na), C.c_void_p),
+                           ov.get("n_levels", nl), asg.data_ptr(), stride,
                            gt.data_ptr(), ngt.data_ptr(), int(gt.shape[1]), mid.data_ptr(), masks.data_ptr(), case["imgsz_h"],
                            case["imgsz_w"], case["gain"], case["scale"], None if gsd is None else gsd.data_ptr(), item.data_ptr() + 16, dpb.data_ptr() + E * es, ld,
-                           ws.data_ptr(), nws, L.dtype_code(dtype), st)
+                           ws.data_ptr(), nws - ov.get("ws_short", 0), L.dtype_code(dtype), st)
     torch.cuda.synchronize()
     assert bool((ws[nws:] == 0xAB).all()), "wrote past the workspace"
     return rc, item, dpb, dcbs
 
 
-def _mask_check(case, dtype, runs, dev_scale=1.0):
+def _mask_check(case, dtype, runs, dev_scale=1.0, ref=None):
+    """ref: the case's own reference where it is kept (SR.reference), else computed here."""
     E = 16 // _es(dtype)
     b, mh, mw, nm = case["proto"].shape
-    ref = SR.mask_loss_ref(**dict(case, scale=case["scale"] * dev_scale))
+    ref = SR.mask_loss_ref(**dict(case, scale=case["scale"] * dev_scale)) if ref is None else ref
     u_out = U16 if dtype == BF16 else U32
     item = KC.payload_of_two([r[1] for r in runs], 1, 1, "item", offset=4).double().reshape(())
     KC.check_bound(item, torch.tensor(ref["item"], dtype=torch.float64), torch.tensor(ref["item_err"] + U32 * abs(ref["item"]),
@@ -193,7 +208,7 @@ def test_device_weight_packing_gives_the_host_packing_bits(dtype):
     """upa_pack_conv_transpose2x2_weight_dev against upa_pack_conv_transpose2x2_weight (host code): every byte, the zero fill of the
     padded depth included, for a depth that is a multiple of the MFMA depth and one that is not; nothing past the buffer."""
     DEV, L, lib, st = KC.env()
-    for cin, cout in ((64, 64), (24, 16)):
+    for cin, cout in ((64, 64), (24, 16), (72, 24), (128, 128)):
         w = P.uniform("ctb:pack", (cin, cout, 2, 2), -1.0, 1.0).contiguous()
         nb = lib.upa_conv_transpose2x2_packed_weight_bytes(cin, cout, L.dtype_code(dtype))
         host = torch.full((nb,), 0xCD, dtype=torch.uint8)
@@ -227,6 +242,68 @@ def test_mask_loss_refuses_depths_it_does_not_build():
         rc, item, dpb, dcbs = _mask_run(case, BF16, nm_arg=nm_arg)
         assert rc in (L.UPA_EUNSUPPORTED, L.UPA_EINVAL), (nm_arg, rc)
         assert all(bool(torch.isnan(t.float()).all()) for t in [item, dpb] + dcbs)
+
+
+FAMILY_RUNS = [(n, d) for d in (F32, BF16) for n in SR.family_names(d) if not n.endswith("_permuted")]
+_IDS = (lambda v: v if isinstance(v, str) else {F32: "f32", BF16: "bf16"}[v])
+
+
+@pytest.mark.parametrize("name,dtype", FAMILY_RUNS, ids=_IDS)
+@KC.stop_after_fault
+def test_mask_loss_families_match_float64(name, dtype):
+    """The families of tests/segment_train_ref.py (what each holds is asserted on the CPU, tests/test_segment_train_ref.py) through the
+    default scene's path: strided views with guard bands, NaN-prefilled outputs with spare rows, the workspace tail, two runs bit for
+    bit, every element inside the reference's bound and the reference's zeros exact.  No element is left out: the reference takes the
+    crop decisions in float32 itself.
+      turns    A = 525: three compaction turns with the carry in use, foreground on both sides of 255 / 256 and of the level starts, an
+               empty first turn, 525 slots on 40 lanes (13 or 14 turns per workgroup), three strides of the item's sum, every 8 x 8
+               tile met by more than a hundred records, a box inside one tile, the whole mask (960 pixels), 486 pixels
+      clamp    525 slots on the 512 lanes the grid is clamped to
+      depthN   nm = 4, 12, 20, 64, 128 (f32), 8, 24, 64, 128 (bf16): the k < nm guards, every register slot live at 128
+      levelsN  one and two levels: ABI arrays of exactly n_levels entries
+      stride   the zero pass past its 2048-workgroup grid: a row it missed is still NaN
+      edges    box edges on, one float32 below and one above an integer mask coordinate; two boxes outside the mask
+    The error model at these sizes: a coefficient gradient is summed per thread over npx / 64 pixels (15 for the whole mask), then over
+    the 64 pixel lanes in one order - npx / 64 + 64 terms, inside (npx / 64 + 72) u; the loss term likewise; a dproto element is one
+    running sum over the image's records that keep the pixel, at most per_img = 525 terms, inside (per_img + 8) u; the item is summed
+    in double.  So 525 records and 960-pixel boxes change the counts the model already carries, not its form."""
+    case = SR.family(name, dtype)
+    runs = [_mask_run(case, dtype) for _ in range(2)]
+    assert runs[0][0] == 0 and runs[1][0] == 0
+    ref = _mask_check(case, dtype, runs, ref=SR.reference(name, dtype))
+    assert ref["n_fg"] == sum(len(f) for f in SR.foreground(case)) > 0 and ref["item"] > 0
+    if name == "turns":
+        other = _mask_run(case, dtype, stride=2)
+        assert other[0] == 0 and KC.same_bits(other[1], runs[0][1]) and KC.same_bits(other[2], runs[0][2])
+        assert all(KC.same_bits(a, b) for a, b in zip(other[3], runs[0][3]))
+
+
+@pytest.mark.parametrize("name", ["turns", "clamp"])
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@KC.stop_after_fault
+def test_mask_loss_follows_a_permuted_assignment(name, dtype):
+    """The same foreground anchors on other gts: item, dproto and every coefficient gradient against the reference of the permuted
+    scene - a slot / anchor mix-up that the symmetric assignment hides would show here."""
+    base, perm = SR.family(name, dtype), SR.family(name + "_permuted", dtype)
+    assert SR.foreground(base) == SR.foreground(perm)
+    runs = [_mask_run(perm, dtype) for _ in range(2)]
+    assert runs[0][0] == 0 and runs[1][0] == 0
+    ref = _mask_check(perm, dtype, runs, ref=SR.reference(name + "_permuted", dtype))
+    assert ref["n_fg"] == SR.reference(name, dtype)["n_fg"] and ref["item"] != SR.reference(name, dtype)["item"]
+
+
+@KC.stop_after_fault
+def test_mask_loss_refusals_leave_the_outputs_untouched():
+    _, L, _, _ = KC.env()
+    assert SR.refusals_precede_launches()  # asked before sizes that a build without the checks would read out of range with
+    case = SR.mask_case(dtype=F32)
+    table = [(L.UPA_EINVAL, F32, dict(n_levels=0)), (L.UPA_EINVAL, F32, dict(n_levels=4)), (L.UPA_EUNSUPPORTED, F32, dict(daddr_add=4)),
+             (L.UPA_EUNSUPPORTED, F32, dict(ldd_add=1)), (L.UPA_EUNSUPPORTED, BF16, dict(ldd_add=4)), (L.UPA_EINVAL, F32, dict(ws_short=1)),
+             (L.UPA_EUNSUPPORTED, F32, dict(hs=[4, 2, 32768]))]  # 20 + 6 + 65536 anchors
+    for want, dtype, ov in table:
+        rc, item, dpb, dcbs = _mask_run(case if dtype == F32 else SR.mask_case(dtype=BF16), dtype, **ov)
+        assert rc == want, (ov, rc)
+        assert all(bool(torch.isnan(t.float()).all()) for t in [item, dpb] + dcbs), ov
 
 
 # ---- 3. whole steps ---------------------------------------------------------------------------------------------------------------------

@@ -48,6 +48,24 @@ def test_base_case_holds_what_it_is_there_for():
     assert float(ref["dkpts"][1][0, 1, 2].abs().max()) > 0 and float(ref["dkpts"][0][0, 2, 3].abs().max()) > 0
 
 
+def test_wide_and_stride_cases_reach_the_clamp_and_the_zero_pass_stride():
+    """On the default levels min(10 G, A) = 315 whatever G is: 79 workgroups, no clamp.  "all_wide" has A = 630 and G = 60."""
+    assert PR.anchor_groups(PR.kpt_case("all_fg", G=60)) == (79, 79)
+    wide = PR.kpt_case("all_wide")
+    A = wide["assign"].shape[1]
+    groups, want = PR.anchor_groups(wide)
+    assert A == 630 and wide["gt"].shape[1] == 60 and (groups, want) == (128, 150)
+    n_img = ((wide["assign"] >= 0) & (wide["assign"] < wide["n_gt"].view(-1, 1))).sum(1).tolist()
+    assert n_img == [A] * 3 and -(-A // 4) - groups == 30  # workgroups 0..29 take a second turn
+    for dtype, b_want in ((F32, 9), (BF16, 18)):
+        case = PR.kpt_case("stride", dtype)
+        b, A = case["assign"].shape
+        items = PR.zero_pass_items(case, dtype)
+        assert b == b_want and A == 4164 and items > PR.ZERO_PASS_ITEMS >= items // b * (b - 1)  # the smallest b
+        fg = ((case["assign"] >= 0) & (case["assign"] < case["n_gt"].view(-1, 1))).nonzero().tolist()
+        assert fg == [[0, 0], [0, 1], [0, 4095], [b - 1, 4096], [b - 1, 4160], [b - 1, A - 1]]
+
+
 def _labels(boxes, kpts, bi):
     return dict(batch_idx=torch.tensor(bi, dtype=torch.float32), cls=torch.zeros(len(bi)), bboxes=torch.tensor(boxes, dtype=torch.float32),
                 keypoints=kpts)

@@ -16,7 +16,7 @@ ROOT = Path(__file__).resolve().parents[1]
 CONVT_SHAPES = [(2, 5, 7, 16, 16), (1, 20, 20, 64, 64), (3, 9, 4, 32, 64)]
 
 
-@pytest.mark.parametrize("shape", CONVT_SHAPES, ids=lambda s: "x".join(str(v) for v in s))
+@pytest.mark.parametrize("shape", CONVT_SHAPES + sorted(set(sum(SR.CONVT_EXTRA.values(), []))), ids=lambda s: "x".join(str(v) for v in s))
 def test_conv_transpose_reference_is_autograd_of_conv_transpose2d(shape):
     n, h, w, cin, cout = shape
     x = P.uniform("ctb:x", (n, h, w, cin), -1.0, 1.0).double()
@@ -45,6 +45,119 @@ def test_mask_loss_reference_is_autograd_of_the_reference_formula():
     assert float(ref["dcoefs"][0][0, 1, 1].abs().max()) > 0 and float(ref["dcoefs"][0][0, 1, 2].abs().max()) > 0  # anchors 6 and 7
     assert float(ref["dproto"][1].abs().max()) == 0.0 and float(ref["dproto"][2].abs().max()) == 0.0
     assert float(ref["dproto"][0].abs().max()) > 0
+
+
+F32, BF16 = torch.float32, torch.bfloat16
+# every family in f32; in bf16 those whose shape follows the dtype (the depths, the zero pass's stride)
+FAMILY_CASES = [(n, F32) for n in SR.family_names(F32)] + [(n, BF16) for n in SR.family_names(BF16) if n.startswith(("depth", "stride"))]
+
+
+@pytest.mark.parametrize("name,dtype", FAMILY_CASES, ids=lambda v: v if isinstance(v, str) else str(v).split(".")[-1])
+def test_family_reference_is_autograd_of_the_reference_formula(name, dtype):
+    """The default scene's tolerances on every family: 1e-12 of the item, 1e-12 of dproto's largest element for the gradients."""
+    case, ref = SR.family(name, dtype), SR.reference(name, dtype)
+    item, dproto, dcoefs = SR.mask_loss_autograd(**case)
+    assert ref["n_fg"] == sum(len(f) for f in SR.foreground(case)) > 0
+    assert abs(ref["item"] - item) <= 1e-12 * abs(item) and item > 0
+    assert float((ref["dproto"] - dproto).abs().max()) <= 1e-12 * float(dproto.abs().max())
+    for a, b in zip(ref["dcoefs"], dcoefs):
+        assert float((a - b).abs().max()) <= 1e-12 * float(dproto.abs().max())
+
+
+def _crops(case, i):
+    """(G, mh, mw) bool: the reference's own float32 crop decisions for the gt rows of image i."""
+    mh, mw = case["masks"].shape[1:]
+    mbox, _ = SR.mask_boxes(case["gt"], case["imgsz_h"], case["imgsz_w"], mh, mw)
+    xs, ys = torch.arange(mw, dtype=torch.float32).view(1, 1, -1), torch.arange(mh, dtype=torch.float32).view(1, -1, 1)
+    x1, y1, x2, y2 = (mbox[i, :, k].view(-1, 1, 1) for k in range(4))
+    return (xs >= x1) & (xs < x2) & (ys >= y1) & (ys < y2)
+
+
+def test_turns_family_holds_its_turns():
+    case = SR.family("turns")
+    fg, A = SR.foreground(case), case["assign"].shape[1]
+    starts = [0, 400, 500]
+    assert A == 525 and -(-A // 256) == 3 and A % 256 == 13 and starts == [0, 20 * 20, 20 * 20 + 10 * 10]
+    assert fg[0] == [0, 255, 256, 399, 400, 499, 500, 524]          # both sides of 255 / 256 and of each level start, the last anchor
+    assert min(fg[1]) == 256 and max(fg[1]) == 511 and len(fg[1]) == 6 and int(case["assign"][1, 7]) >= int(case["n_gt"][1])
+    assert fg[2] == list(range(A))
+    lanes = SR.anchor_lanes(case)
+    assert lanes == 40 and -(-len(fg[2]) // lanes) == 14 and len(fg[2]) // lanes == 13   # every workgroup takes 13 or 14 turns
+    assert -(-len(fg[2]) // 256) == 3                                                   # ml_finish_kernel's strides
+    crops = _crops(case, 2)
+    npx = crops.flatten(1).sum(1).tolist()
+    assert npx[1] == 24 * 40 and npx[2] > 4 * 64 and npx[2] % 64 != 0
+    ys, xs = crops[0].nonzero(as_tuple=True)
+    assert len(ys) > 0 and len(set((ys // 8).tolist())) == 1 and len(set((xs // 8).tolist())) == 1   # wholly inside one 8 x 8 tile
+    assert bool(crops[3][:, -1].any()) and bool(crops[3][-1].any())                                   # reaches the right / bottom edge
+    # records per 8 x 8 tile of image 2: every tile is met by the whole-mask box's records at least
+    per_gt = torch.bincount(case["assign"][2].long(), minlength=4)
+    tiles = crops.view(4, 3, 8, 5, 8).any(4).any(2)  # (gt, tile row, tile column)
+    assert int((tiles * per_gt.view(4, 1, 1)).sum(0).min()) >= 100
+
+
+def test_clamp_family_fills_the_clamped_grid():
+    case = SR.family("clamp")
+    fg, A, G = SR.foreground(case), case["assign"].shape[1], case["gt"].shape[1]
+    assert G == 52 and 10 * G > 512 and A > 512 and SR.anchor_lanes(case) == 512
+    assert fg[0] == list(range(A)) and len(fg[0]) - 512 == 13 and len(fg[1]) == 3
+    assert len(set(case["assign"][0].tolist())) == 52
+    for perm in ("turns_permuted", "clamp_permuted"):
+        base, other = SR.family(perm.split("_")[0]), SR.family(perm)
+        assert SR.foreground(base) == SR.foreground(other) and not torch.equal(base["assign"], other["assign"])
+
+
+def test_depth_level_and_stride_families_hold_their_shapes():
+    for dtype, vec in ((F32, 4), (BF16, 8)):
+        assert all(nm % vec == 0 and nm <= 128 for nm in SR.DEPTHS[dtype]) and 128 in SR.DEPTHS[dtype] and min(SR.DEPTHS[dtype]) == vec
+        assert all(SR.family(f"depth{nm}", dtype)["proto"].shape[3] == nm for nm in SR.DEPTHS[dtype])
+        case = SR.family("stride", dtype)
+        b, A = case["assign"].shape
+        assert SR.zero_pass_items(case, dtype) > SR.ZERO_PASS_ITEMS >= SR.zero_pass_items(case, dtype) // b * (b - 1)   # the smallest b
+        fg = SR.foreground(case)
+        assert all(f == [0, 1, 4095, 4096, 4160, 4163] for f in fg) and A == 4164 and fg[-1][-1] == A - 1
+    one, two = SR.family("levels1"), SR.family("levels2")
+    assert len(one["coefs"]) == 1 and one["assign"].shape[1] == 20 and SR.reference("levels1")["n_fg"] == 3
+    assert len(two["coefs"]) == 2 and two["assign"].shape[1] == 26 and SR.reference("levels2")["n_fg"] == 4
+
+
+def test_edges_family_decides_every_pixel_as_float32_does_and_sees_a_reciprocal_multiply():
+    """Sizes 96 x 80 -> 24 x 20: v / 96 and v / 80 are inexact in float32.  A numpy float32 emulation of the crop rule gives the
+    reference's decision at every pixel of every box; with the divide replaced by a multiply with the float32 reciprocal at least one
+    pixel is decided the other way, so a kernel that did that would leave the reference's exact zeros."""
+    case = SR.family("edges")
+    rows = case["edge_rows"]
+    assert {(e, kind) for _, e, kind, _, _ in rows} == {(e, kind) for e in range(4) for kind in (-1, 0, 1)} and len(rows) == 24
+    assert SR.foreground(case) == [list(range(26))] and int(case["n_gt"][0]) == 26
+    mh, mw = SR.EDGE_MASK
+    mbox, _ = SR.mask_boxes(case["gt"], case["imgsz_h"], case["imgsz_w"], mh, mw)
+    for g, e, kind, k, _ in rows:  # the built boxes carry the searched kinds
+        want = np.float32(k) if kind == 0 else np.nextafter(np.float32(k), np.float32(kind * np.inf))
+        assert np.float32(mbox[0, g, e]) == want, (g, e, kind, k)
+    ref_crops = _crops(case, 0).numpy()
+    boxes = case["gt"][0, :, 1:5]
+    assert np.array_equal(SR.crop_decisions(boxes, case["imgsz_h"], case["imgsz_w"], mh, mw), ref_crops)
+    other = SR.crop_decisions(boxes, case["imgsz_h"], case["imgsz_w"], mh, mw, reciprocal=True)
+    assert int((other != ref_crops).sum()) >= 1 and any(f for *_, f in rows)
+    # the two boxes outside the mask: exactly-zero terms
+    ref = SR.reference("edges")
+    flat = torch.cat([d.reshape(1, -1, 32) for d in ref["dcoefs"]], 1)[0]
+    ferr = torch.cat([d.reshape(1, -1, 32) for d in ref["dcoefs_err"]], 1)[0]
+    zero = [a for a in range(26) if float(flat[a].abs().max()) == 0.0 and float(ferr[a].max()) == 0.0]
+    assert zero == [24, 25] and not ref_crops[24:].any() and all(ref_crops[g].any() for g in range(24))
+
+
+def test_split_arithmetic_of_the_new_conv_transpose_shapes():
+    assert SR.ctb_splits(16, 16, 1023, 4) == (8, 128) and SR.ctb_splits(16, 16, 1023, 32) == (8, 128) and 1023 % 128 != 0
+    assert SR.ctb_splits(16, 16, 8192, 4)[0] == 64 and SR.ctb_splits(16, 16, 8192, 32)[0] == 64
+    assert SR.ctb_splits(128, 128, 9, 4)[0] == 1 and SR.ctb_splits(64, 64, 400, 4)[0] == 4
+    for dtype, vec in ((F32, 4), (BF16, 8)):
+        assert all(s[3] % vec == 0 and s[4] % vec == 0 for s in SR.CONVT_EXTRA[dtype])
+        assert any(s[3] > 64 and s[3] % 64 for s in SR.CONVT_EXTRA[dtype]) and any(4 * s[4] % 64 for s in SR.CONVT_EXTRA[dtype])
+
+
+def test_mask_loss_refusals_stand_before_the_first_launch():
+    assert SR.refusals_precede_launches()
 
 
 def test_mask_loss_reference_without_foreground_is_zero():
